@@ -10,6 +10,12 @@ Metric (BASELINE.json): MParams/s SVD+RTVQ compressed, ViT-L-14 x 8 tasks.
   No disk I/O, no H2D of inputs, no Python dict assembly.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--model ViT-L-14] [--tasks 8] [--scaling strong|weak]
+                  [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing more: inputs, plan, the one-time output placement (tune_placement,
+which `value` is measured after), W warm-up steps, K timed steps, the JSON line.  --full adds every other figure
+(marked "--full" below), each measured by runs of its own.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (float32 / float64; the inputs are seeded, so two builds can be compared array by array).
 
 N > 1: one rank per GPU over RCCL.  `python bench.py --gpus N` started WITHOUT a launcher spawns the N ranks itself
 (a parent process that never touches the GPU runs `python -m torch.distributed.run ... bench.py`); started by
@@ -20,16 +26,18 @@ sets, so the exchange travels behind the next step's compute; sizes were exchang
 completed before the clock stops); the fp16 bases stay on their owning GPU and the cost of gathering them is measured
 and reported separately.
   "strong" (default for N > 1, BASELINE configs[3]): ONE model's tensors LPT-partitioned over the ranks.
-  "weak": every rank processes one full model's worth of tensors (also measured and printed as `weak` when N > 1).
+  "weak": every rank processes one full model's worth of tensors (--full: also measured and printed as `weak` when
+  N > 1, with the separately timed `basis_gather`).
 
 The JSON line also carries
   roofline      for the dominant kernel (k_basis_project): algorithmic bytes D*(4N + 2N + 4) per row
-                (read every delta once, write U fp16, write mean fp32) / its HIP-event time; the box's measured copy /
-                read ceilings; the fraction any two-pass schedule could reach at that ceiling
-  cpu_baseline  the CPU oracle (reference op sequence on torch-CPU/LAPACK) timed on a bounded sample
-  untuned       the same K steps on the first output allocation as it comes, timed before the one-time
+                (read every delta once, write U fp16, write mean fp32) / its HIP-event time; with --full the box's
+                measured copy / read ceilings and the fraction any two-pass schedule could reach at that ceiling
+  cpu_baseline  --full: the CPU oracle (reference op sequence on torch-CPU/LAPACK) timed on a bounded sample
+  untuned       --full: the same K steps on the first output allocation as it comes, timed before the one-time
                 CompressPlan.tune_placement (which HBM region each stream lives in decides 2.72 vs 3.1 ms for pass 2:
                 DESIGN.md section 5); `value` is measured after it (--placement-candidates 1 turns it off)
+  ms_per_step_incl_small_d2h  --full: three more steps, each followed by the D2H of the small artifacts
 """
 import argparse
 import json
@@ -109,9 +117,18 @@ def parse():
                     help="one GPU: compress only rank 0's share of a strong-scaling run over this many ranks (what one "
                          "GPU of the multi-GPU run does per step; with SVDQ_DIST_SINGLE=1 including the RCCL exchange)")
     ap.add_argument("--shard-rank", type=int, default=0, help="--shard-of: which rank's share (default 0)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baseline, HBM ceiling probes, the untuned "
+                         "steps, the steps with the small-artifact D2H, and for N > 1 the basis gather and the weak leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64; "
+                         "fixed seeded row samples of the large buffers; rank 0's share when N > 1)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launching ranks
@@ -300,6 +317,70 @@ def cpu_merge_baseline(names, rows, n_tasks, args):
             "cpu_model": cpu_model(),
             "sample": f"the {done} largest tensors of {args.model} x {n_tasks} tasks, {scalars / 1e6:.1f} M scalars in "
                       f"{spent:.2f} s (oracle: per task dequantize, weighted average, U c + mean, base + delta on torch-CPU)"}
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET_BYTES = 32 << 20      # per sampled buffer (two at most per run: well inside 64 MB in all)
+
+
+def sample_rows(p: int, n: int, m: int):
+    """A fixed sample of at most m of the n rows of parameter p (sorted; the same for every run and build)."""
+    import numpy as np
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng([20251015, p]).choice(n, m, replace=False)).astype(np.int64)
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype in (np.float64, np.int64) else np.float32)
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+
+
+def compress_outputs(plan, sm):
+    """What a caller of the compression path receives: the small artifacts whole, and the fp16 basis and the mean at a
+    fixed sample of rows of every parameter (the whole basis is GBs).  basis_sample row i holds U_high | U_low of
+    parameter sample_index[i, 0] at row sample_index[i, 1], zero beyond its r columns."""
+    import numpy as np
+    N = plan.N
+    m = max(1, min(1024, DUMP_BUDGET_BYTES // (4 * N * max(plan.P, 1))))
+    U, mean, idx = [], [], []
+    for p in range(plan.P):
+        n, k, r = int(sm.rows[p]), int(sm.k[p]), int(sm.r[p])
+        rows = sample_rows(p, n, m)
+        if rows.size == 0:
+            continue
+        U_high, U_low, mu = plan.basis_tensors(p, k, r, n)
+        sel = torch.from_numpy(rows).to(plan.device)
+        u = torch.zeros((rows.size, N), dtype=torch.float32, device=plan.device)
+        u[:, :k] = U_high.index_select(0, sel).float()
+        u[:, k:r] = U_low.index_select(0, sel).float()
+        U.append(u)
+        if mu is not None:
+            mean.append(mu.index_select(0, sel).view(-1))
+        idx.append(np.stack([np.full(rows.size, p, dtype=np.int64), rows], axis=1))
+    out = {f: getattr(sm, f) for f in ("sigma", "k", "r", "energy", "rows", "c_high", "codes", "scale", "zero_point",
+                                       "residual_norm", "coef")}
+    out["basis_sample"] = torch.cat(U).cpu().numpy() if U else np.zeros((0, N), np.float32)
+    if plan.center:
+        out["mean_sample"] = torch.cat(mean).cpu().numpy() if mean else np.zeros(0, np.float32)
+    out["sample_index"] = np.concatenate(idx) if idx else np.zeros((0, 2), np.int64)
+    return out
+
+
+def merge_outputs(plan, buf, offs):
+    """--merge: the merged tensors (base + merged delta) at a fixed sample of elements of every parameter."""
+    import numpy as np
+    m = max(1, min(4096, DUMP_BUDGET_BYTES // (4 * max(plan.P, 1))))
+    vals, idx = [], []
+    for p, (o, n) in enumerate(zip(offs, plan.rows)):
+        rows = sample_rows(p, n, m)
+        vals.append(buf[o:o + n].index_select(0, torch.from_numpy(rows).to(buf.device)))
+        idx.append(np.stack([np.full(rows.size, p, dtype=np.int64), rows], axis=1))
+    return {"merged_sample": torch.cat(vals).cpu().numpy(), "sample_index": np.concatenate(idx)}
 
 
 # ------------------------------------------------------------------------------------------------ one workload
@@ -554,6 +635,8 @@ def merge_leg(wl, args, dev):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kms = [sum(ev[s_][i].elapsed_time(ev[s_][i + 1]) for s_ in range(steps)) / steps for i in range(2)]
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, merge_outputs(plan, buf, offs))
     sumD = float(sum(wl.rows))
     # algorithmic bytes of the streaming launch: U fp16 (2 N) + mean + base read, fp32 out written
     rec_bytes = sumD * (2 * N + 12)
@@ -604,11 +687,13 @@ def diagnostics_leg(wl, args, dev):
     t0 = time.perf_counter()
     ev[0].record()
     for s_ in range(args.steps):
-        step()
+        diag = step()
         ev[s_ + 1].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kms = sum(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)) / args.steps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"diagnostics": diag.cpu().numpy()})
     sumD = float(sum(wl.rows))
     sel = float(wl.rows_dev.sum().item()) if masked else sumD
     # the N deltas at every source row (+ the mask byte), the fp16 basis at every selected row; no mean
@@ -712,23 +797,25 @@ def main():
         if world > 1 or args.from_base != "off":
             sys.exit("bench.py --merge: one GPU, task vectors resident")
         out = merge_leg(wl, args, dev)
-        if not args.no_cpu and args.masks == "none":      # the oracle's merge restatement has no mask scatter
+        if args.full and not args.no_cpu and args.masks == "none":      # the oracle's merge restatement has no mask scatter
             out["cpu_baseline"] = cpu_merge_baseline(names, rows, N, args)
         print(json.dumps(out), flush=True)
         return
     # after the inputs exist: the probe walks through device memory and leaves holes in several regions behind, which
     # later allocations would be scattered over
-    try:
-        ceilings = measured_ceilings(dev, walk=args.placement_candidates > 1) if rank == 0 else None
-    except Exception:
-        torch.cuda.empty_cache()
-        ceilings = None
+    ceilings = None
+    if args.full and rank == 0:
+        try:
+            ceilings = measured_ceilings(dev, walk=args.placement_candidates > 1)
+        except Exception:
+            torch.cuda.empty_cache()
     untuned = None
     if args.placement_candidates > 1 and not on_cpu:      # (gloo rehearsal: several ranks share one card's memory)
-        e0, sc0, kms0 = wl.timed(dist, args.steps, args.warmup)
-        untuned = {"ms_per_step": round(e0 / args.steps * 1e3, 4), "value": round(sc0 / (e0 / args.steps) / 1e6, 1),
-                   "k_basis_project_ms": round(kms0[2], 4) if kms0[2] == kms0[2] else None,
-                   "what": "the same K steps before tune_placement: outputs in the first allocation as it comes"}
+        if args.full:
+            e0, sc0, kms0 = wl.timed(dist, args.steps, args.warmup)
+            untuned = {"ms_per_step": round(e0 / args.steps * 1e3, 4), "value": round(sc0 / (e0 / args.steps) / 1e6, 1),
+                       "k_basis_project_ms": round(kms0[2], 4) if kms0[2] == kms0[2] else None,
+                       "what": "the same K steps before tune_placement: outputs in the first allocation as it comes"}
         try:
             wl.tune()
         except Exception as e:      # never lose the measurement over the one-time tuning: fall back to the untuned outputs
@@ -745,6 +832,8 @@ def main():
         per_rank = gathered
     plan = wl.plan
     sm = plan.fetch_small()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, compress_outputs(plan, sm))
     k_mean = float(sm.k.mean())
     n_units = int(plan.sizes.n_units)
     placement_ms = list(wl.placement_ms)
@@ -754,7 +843,7 @@ def main():
     # also the time to "small artifacts on the host" (one D2H of the packed buffer per step, which
     # synchronises the stream); never the headline value
     d2h_ms = None
-    if world == 1:
+    if args.full and world == 1:
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         for _ in range(3):
@@ -764,12 +853,12 @@ def main():
 
     # the two extra figures must never cost the main line (every rank takes the same path: the guards are symmetric)
     try:
-        bgather = basis_gather_ms(plan, dist, dev, on_cpu) if multi else None
+        bgather = basis_gather_ms(plan, dist, dev, on_cpu) if multi and args.full else None
     except torch.cuda.OutOfMemoryError:
         bgather = None
 
     weak = None
-    if world > 1 and scaling == "strong" and not args.no_weak:
+    if args.full and world > 1 and scaling == "strong" and not args.no_weak:
         del wl, plan, sm
         torch.cuda.empty_cache()
         wlw = Workload(args, rows_all, dev, 1234 + rank, world, on_cpu)
@@ -846,7 +935,7 @@ def main():
             out["basis_gather"] = bgather
         if weak is not None:
             out["weak"] = weak
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             try:
                 cb = cpu_baseline([names[i] for i in mine], rows, N, args)
                 if cb["cores"] > 8:      # also at 8 threads, on a shorter sample; the faster of the

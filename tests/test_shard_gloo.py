@@ -252,7 +252,7 @@ def test_bench_one_rank_world_over_rccl():
                SVDQ_DIST_SINGLE="1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "ViT-B-32", "--steps", "3", "--warmup", "1",
-                        "--no-cpu"], capture_output=True, text=True, env=env, timeout=600)
+                        "--no-cpu", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-1500:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["value"] > 0

@@ -12,12 +12,12 @@ for l in open(sys.argv[1]):
         d=json.loads(l); print(f"[{sys.argv[2]}]", d["ms_per_step"], round(d["value"]/1e3), "k", d["kernels_ms"], "path", d["path_roofline_frac"], "untuned", d.get("untuned", {}).get("ms_per_step"))
 PY
 done <<'CFGS'
---model ViT-B-32
---model ViT-B-16 --masks union --stages 4
---model ViT-L-14 --masks union
---from-base fused
---tasks 2
---tasks 4
---tasks 12
---tasks 16
+--full --model ViT-B-32
+--full --model ViT-B-16 --masks union --stages 4
+--full --model ViT-L-14 --masks union
+--full --from-base fused
+--full --tasks 2
+--full --tasks 4
+--full --tasks 12
+--full --tasks 16
 CFGS

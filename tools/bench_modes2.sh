@@ -1,5 +1,5 @@
 set -o pipefail
-for cfg in "--from-base ingest" "--model ViT-B-16 --masks union --masks-packed" "--model ViT-B-16 --masks majority" "--model ViT-B-16 --masks union --masks-compact" "--model ViT-B-16 --masks union --from-base fused"; do
+for cfg in "--full --from-base ingest" "--full --model ViT-B-16 --masks union --masks-packed" "--full --model ViT-B-16 --masks majority" "--full --model ViT-B-16 --masks union --masks-compact" "--full --model ViT-B-16 --masks union --from-base fused"; do
   tag=$(echo "$cfg" | tr -d ' -')
   timeout -k 10 300 python bench.py --no-cpu --steps 5 $cfg > gpurun_out/bm2_$tag.log 2>&1 || { tail -n 8 gpurun_out/bm2_$tag.log; exit 1; }
   python - "gpurun_out/bm2_$tag.log" "$cfg" <<'PY'

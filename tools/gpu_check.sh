@@ -8,7 +8,7 @@ timeout -k 10 1000 python -m pytest "${sel[@]}" -m gpu -x -q > gpurun_out/pytest
 rc=$?
 tail -n 15 gpurun_out/pytest_gpu.log
 [ $rc -ne 0 ] && exit $rc
-for cfg in "" "--tasks 20 --steps 10"; do
+for cfg in "--full" "--full --tasks 20 --steps 10"; do
   tag=$(echo "$cfg" | tr -d ' -')
   timeout -k 10 300 python bench.py --no-cpu $cfg > gpurun_out/bench_$tag.log 2>&1 || { tail -n 5 gpurun_out/bench_$tag.log; exit 1; }
   python - "gpurun_out/bench_$tag.log" "$cfg" <<'PY'

@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out
 O=gpurun_out
 # 1. the default bench line (with the CPU baseline), as the driver runs it
-timeout -k 10 400 python bench.py > $O/r03_bench_default.log 2>&1 || { tail -n 5 $O/r03_bench_default.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/r03_bench_default.log 2>&1 || { tail -n 5 $O/r03_bench_default.log; exit 1; }
 grep '^{' $O/r03_bench_default.log > $O/r03_bench_line.json; cut -c1-260 $O/r03_bench_line.json
 # 2. kernel statistics + timed-region averages: headline, masked (walk and index lists), N = 20, merge
 bash tools/r03_prof1.sh bench || exit 1
@@ -25,7 +25,7 @@ for cfg in "b32 --model ViT-B-32" "b16 --model ViT-B-16 --stages 4" "masked_pack
            "masked_frombase --model ViT-B-16 --masks union --stages 4 --from-base fused" "frombase --from-base fused" \
            "n2 --tasks 2" "n4 --tasks 4" "n12 --tasks 12 --steps 10" "n16 --tasks 16 --steps 10" "n24 --tasks 24 --steps 8" "n32 --tasks 32 --steps 6"; do
   set -- $cfg; tag=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu "$@" > $O/r03_line_$tag.log 2>&1 || { tail -n 5 $O/r03_line_$tag.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu "$@" > $O/r03_line_$tag.log 2>&1 || { tail -n 5 $O/r03_line_$tag.log; exit 1; }
   python - $O/r03_line_$tag.log "$tag" <<'PY'
 import json,sys
 for l in open(sys.argv[1]):

@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 O=gpurun_out
 # 1. the default bench line (with the CPU baseline), as the driver runs it
-timeout -k 10 400 python bench.py > $O/r04_bench_default.log 2>&1 || { tail -n 5 $O/r04_bench_default.log; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/r04_bench_default.log 2>&1 || { tail -n 5 $O/r04_bench_default.log; exit 1; }
 grep '^{' $O/r04_bench_default.log > $O/r04_bench_line.json; cut -c1-260 $O/r04_bench_line.json
 # 2. kernel statistics + timed-region averages: headline, masked config #3, N = 20
 bash tools/r04_prof1.sh bench || exit 1
@@ -22,7 +22,7 @@ for cfg in "b32 --model ViT-B-32" "b16 --model ViT-B-16 --stages 4" "masked_vitb
            "n2 --tasks 2" "n4 --tasks 4" "n12 --tasks 12 --steps 10" "n16 --tasks 16 --steps 10" "n20 --tasks 20 --steps 10" \
            "n24 --tasks 24 --steps 8" "n32 --tasks 32 --steps 6"; do
   set -- $cfg; tag=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu "$@" 2>/dev/null | grep '^{' >> $O/r04_other_configs.jsonl || { echo "$tag failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu "$@" 2>/dev/null | grep '^{' >> $O/r04_other_configs.jsonl || { echo "$tag failed"; exit 1; }
 done
 python3 - <<'PY'
 import json

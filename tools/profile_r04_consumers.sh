@@ -5,7 +5,7 @@
 set -o pipefail
 O=gpurun_out; mkdir -p $O
 : > $O/r04_consumers.jsonl
-run() { timeout -k 10 300 python3 bench.py "$@" --steps 20 2>/dev/null | tail -1 >> $O/r04_consumers.jsonl || exit 1; }
+run() { timeout -k 10 300 python3 bench.py --full "$@" --steps 20 2>/dev/null | tail -1 >> $O/r04_consumers.jsonl || exit 1; }
 run --diagnostics
 run --diagnostics --tasks 3 --no-cpu
 run --diagnostics --tasks 12 --no-cpu

@@ -5,7 +5,7 @@ R=$PWD
 mkdir -p $R/gpurun_out
 out=$R/gpurun_out/r03_consumers.jsonl
 : > $out
-run() { timeout -k 10 300 python3 $R/bench.py "$@" --steps 20 2>/dev/null | tail -1 >> $out || exit 1; }
+run() { timeout -k 10 300 python3 $R/bench.py --full "$@" --steps 20 2>/dev/null | tail -1 >> $out || exit 1; }
 run --merge
 run --merge --model ViT-B-16 --stages 4
 run --merge --model ViT-B-16 --stages 4 --masks union
