@@ -41,6 +41,10 @@ enum {
 
 enum { SVDQ_MASK_UNION = 0, SVDQ_MASK_INTERSECTION = 1, SVDQ_MASK_MAJORITY = 2 };
 
+/* Element type of the task / fine-tuned / base tensors a plan's streaming entry points read
+ * (svdq_plan_set_input_type). */
+enum { SVDQ_INPUT_F32 = 0, SVDQ_INPUT_F16 = 1, SVDQ_INPUT_BF16 = 2 };
+
 /* Run-wide settings; field names follow SVDHybridConfig (reference src/svd_hybrid/config.py:157-205). */
 typedef struct svdq_config {
     float   energy_threshold;  /* svd_energy_threshold, (0,1]                       */
@@ -104,6 +108,16 @@ void svdq_plan_destroy(svdq_plan *plan);
  * per run (compress.py:180-183); BASELINE config #5's "mixed 8-bit / 2-bit" run is two quantizer instances over
  * a partition of the parameters, which this expresses inside one plan. */
 int  svdq_plan_set_low_bits(svdq_plan *plan, const int32_t *bits);
+/* Element type of every tensor the plan's streaming entry points read as task, fine-tuned or base tensors:
+ * SVDQ_INPUT_F32 (the default), SVDQ_INPUT_F16 or SVDQ_INPUT_BF16.  Half elements are converted to fp32 in
+ * registers (exactly) and the fp32 arithmetic follows unchanged, so every output -- small artifacts, basis, mean,
+ * task Gram, diagnostics -- is byte-identical to the same call on the tensors converted to fp32 first.  Half tensors
+ * must start on an 8-byte boundary (fp32 ones, as always, on 16 bytes).  Covered: svdq_gram_center[_range],
+ * svdq_eig_rank_select[_range], svdq_basis_project[_range], svdq_compress, svdq_compress_gather,
+ * svdq_compress_from_base, svdq_compress_gather_from_base, svdq_task_gram, svdq_diagnostics (N <= 32).  The mask walk
+ * (svdq_compress_masked[_from_base], svdq_diagnostics_masked), svdq_ingest and svdq_tvq_* read fp32 only and return
+ * SVDQ_EUNSUPPORTED on a plan whose input type is not SVDQ_INPUT_F32.  Any other code: SVDQ_EINVAL. */
+int  svdq_plan_set_input_type(svdq_plan *plan, int32_t type);
 int  svdq_plan_sizes(const svdq_plan *plan, svdq_sizes *out);
 int  svdq_plan_small_layout(const svdq_plan *plan, svdq_small_layout *out);
 /* Per parameter: byte offset of its slab in the packed basis buffer and float offset of its

@@ -16,6 +16,7 @@ _CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("SVDQ_LIB_PATH") or os.path.join(_PKG_DIR, "libsvdq_hip.so")
 
 SVDQ_OK, SVDQ_EINVAL, SVDQ_EHIP, SVDQ_EUNSUPPORTED = 0, -1, -2, -3
+SVDQ_INPUT_F32, SVDQ_INPUT_F16, SVDQ_INPUT_BF16 = 0, 1, 2
 MASK_STRATEGIES = {"union": 0, "intersection": 1, "majority": 2}
 MAX_TASKS = 32
 MAX_STAGES = 8
@@ -45,6 +46,7 @@ SIGNATURES = {
     "svdq_plan_create": (c_int32, [POINTER(c_void_p), c_int32, c_int32, POINTER(c_int64), POINTER(SvdqConfig)]),
     "svdq_plan_destroy": (None, [c_void_p]),
     "svdq_plan_set_low_bits": (c_int32, [c_void_p, POINTER(c_int32)]),
+    "svdq_plan_set_input_type": (c_int32, [c_void_p, c_int32]),
     "svdq_plan_sizes": (c_int32, [c_void_p, POINTER(SvdqSizes)]),
     "svdq_plan_small_layout": (c_int32, [c_void_p, POINTER(SvdqSmallLayout)]),
     "svdq_plan_basis_layout": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),

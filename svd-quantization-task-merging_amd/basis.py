@@ -17,7 +17,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _native as nat
-from .pipeline import (CompressPlan, basis_dict, compress_batch, prepare_vector, resolve_device, wants_cpu)
+from .pipeline import (CompressPlan, basis_dict, compress_batch, native_input_dtype, prepare_input, prepare_vector,
+                       resolve_device, wants_cpu)
 
 
 def stack_and_center(vectors: List[torch.Tensor], center: bool = True
@@ -57,7 +58,8 @@ def select_rank(singular_values: torch.Tensor, energy_threshold: float = 0.90, m
 def _run_single(vectors: List[torch.Tensor], energy_threshold, max_rank, center, device, fp16=False,
                 low_bits=4, rtvq_stages=2):
     dev = resolve_device(device)
-    vs = [prepare_vector(v, dev) for v in vectors]
+    idt = native_input_dtype(vectors)      # all fp16 / all bf16: read as they are
+    vs = [prepare_input(v, dev, idt) for v in vectors]
     D = vs[0].numel()
     for v in vs[1:]:
         if v.numel() != D:

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .pipeline import CompressPlan, prepare_vector, resolve_device
+from .pipeline import CompressPlan, native_input_dtype, prepare_input, resolve_device
 
 
 def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *, process_group=None,
@@ -34,6 +34,8 @@ def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *
     names = sorted({n for tv in task_vectors.values() for n in tv.keys()})
     N = len(tasks)
     vectors, rows = [], []
+    # one plan for the whole model: all fp16 / all bf16 task tensors are read as they are, any mix as fp32 copies
+    idt = native_input_dtype(tv[n] for tv in task_vectors.values() for n in tv.keys())
     with torch.cuda.device(dev):
         for name in names:
             ref = next(tv[name] for tv in task_vectors.values() if name in tv)
@@ -42,13 +44,13 @@ def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *
             vs = []
             for t in tasks:
                 if name in task_vectors[t]:
-                    vs.append(prepare_vector(task_vectors[t][name], dev))
+                    vs.append(prepare_input(task_vectors[t][name], dev, idt))
                 else:
-                    vs.append(torch.zeros(ref.numel(), dtype=torch.float32, device=dev))
+                    vs.append(torch.zeros(ref.numel(), dtype=idt, device=dev))
             vectors.append(vs)
             rows.append(ref.numel())
         if vectors:
-            plan = CompressPlan(rows, N, center=False, device=dev, gram_only=True)
+            plan = CompressPlan(rows, N, center=False, device=dev, gram_only=True, input_dtype=idt)
             G = plan.task_gram(plan.pointer_table(vectors))
         else:
             G = torch.zeros((N, N), dtype=torch.float64, device=dev)

@@ -212,6 +212,23 @@ extern "C" int svdq_plan_set_low_bits(svdq_plan *pl, const int32_t *bits) {
     return SVDQ_OK;
 }
 
+int svdq_require_f32_input(const svdq_plan *pl, const char *who) {
+    if (pl->in_type == SVDQ_INPUT_F32) return SVDQ_OK;
+    svdq_set_error("%s reads fp32 task tensors only; this plan's input type is %s (svdq_plan_set_input_type)", who,
+                   pl->in_type == SVDQ_INPUT_F16 ? "SVDQ_INPUT_F16" : "SVDQ_INPUT_BF16");
+    return SVDQ_EUNSUPPORTED;
+}
+
+extern "C" int svdq_plan_set_input_type(svdq_plan *pl, int32_t type) {
+    if (!pl) return SVDQ_EINVAL;
+    if (type != SVDQ_INPUT_F32 && type != SVDQ_INPUT_F16 && type != SVDQ_INPUT_BF16) {
+        svdq_set_error("input type must be SVDQ_INPUT_F32 (0), SVDQ_INPUT_F16 (1) or SVDQ_INPUT_BF16 (2), got %d", type);
+        return SVDQ_EINVAL;
+    }
+    pl->in_type = type;
+    return SVDQ_OK;
+}
+
 extern "C" int svdq_plan_sizes(const svdq_plan *pl, svdq_sizes *out) {
     if (!pl || !out) return SVDQ_EINVAL;
     *out = pl->sizes;
@@ -489,6 +506,7 @@ extern "C" int svdq_compress_masked(const svdq_plan *pl, const void *ptrs, const
         svdq_set_error("svdq_compress_masked: plan, mask_ptrs, unit_start and rows_dev are required");
         return SVDQ_EINVAL;
     }
+    if (int rc = svdq_require_f32_input(pl, "svdq_compress_masked")) return rc;
     if (small)
         HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
                                (hipStream_t)stream));
@@ -511,6 +529,7 @@ extern "C" int svdq_compress_masked_from_base(const svdq_plan *pl, const void *f
         svdq_set_error("svdq_compress_masked_from_base: plan, base_ptrs, mask_ptrs, unit_start and rows_dev are required");
         return SVDQ_EINVAL;
     }
+    if (int rc = svdq_require_f32_input(pl, "svdq_compress_masked_from_base")) return rc;
     if (pl->ntp > 16) {
         svdq_set_error("the mask-walk mode covers N <= 16 tasks (got %d): use the index lists "
                        "(svdq_compress_gather_from_base)", pl->n_tasks);

@@ -50,6 +50,7 @@ struct svdq_plan {
     SvdqParam *d_params;
     SvdqUnit *d_units;
     int32_t *d_bits;  // optional per-parameter low_bits (svdq_plan_set_low_bits), NULL = cfg.low_bits everywhere
+    int32_t in_type;  // SVDQ_INPUT_*: element type of the task / fine-tuned / base tensors (svdq_plan_set_input_type)
 };
 
 __host__ __device__ static inline int64_t svdq_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
@@ -58,6 +59,9 @@ __host__ __device__ static inline int64_t svdq_align_up(int64_t x, int64_t a) { 
 static inline int svdq_ntp(int n) { return (n + 3) / 4 * 4; }
 
 void svdq_set_error(const char *fmt, ...);
+// SVDQ_OK for an fp32-input plan; otherwise SVDQ_EUNSUPPORTED with the error text naming `who` (entry points whose
+// kernels read task tensors as fp32 only)
+int svdq_require_f32_input(const svdq_plan *pl, const char *who);
 
 // launchers (defined in the .hip files)
 // idx: NULL, or a device table [n_params] of int32 index lists (gather mode, see svdq_compress_gather);

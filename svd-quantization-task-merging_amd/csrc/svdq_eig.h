@@ -3,6 +3,7 @@
 // completion column, closed-form coefficients) as a device function shared by k_eig and the fused kernel.
 #pragma once
 #include "svdq_common.h"
+#include "svdq_input.h"
 
 #define LDN 33  // padded leading dimension of N x N LDS matrices sized for N <= 32 (k_coeff)
 
@@ -78,7 +79,8 @@ __device__ __forceinline__ double chunk_sum(const double *__restrict__ part, int
 // The whole per-parameter eigen-stage as a device function over caller-provided LDS scratch, so that
 // the stand-alone kernel (k_eig) and the persistent fused kernel share it.  THREADS threads of ONE
 // workgroup must call it together (tid = thread index in [0, THREADS)).
-template <int THREADS, int NMAX>
+// TIN: element type of the task / base tensors (svdq_input.h); only row 0 is read here.
+template <int THREADS, int NMAX, typename TIN = float>
 __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
                           const float *const *__restrict__ ptrs, int NT, int center, float thr, int max_rank,
                           const double *__restrict__ gram_part2, float *__restrict__ Wtab,
@@ -321,8 +323,14 @@ __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
     // row 0 of every task (gather / walk mode: the first selected element of the tensor, row0_pos)
     if (tid < n && D > 0) {
         const int64_t i0 = row0_pos;
-        float x0 = ptrs[(size_t)p * n + tid][i0];
-        if (base_ptrs) x0 = x0 - base_ptrs[p][i0];   // minus-base mode: the delta is formed exactly as in the passes
+        float x0;
+        if constexpr (sizeof(TIN) == 4) {
+            x0 = ptrs[(size_t)p * n + tid][i0];
+            if (base_ptrs) x0 = x0 - base_ptrs[p][i0];   // minus-base mode: the delta is formed exactly as in the passes
+        } else {   // half inputs: widened exactly, then the same fp32 subtraction
+            x0 = SvdqIn<TIN>::cvt(reinterpret_cast<const uint16_t *>(ptrs[(size_t)p * n + tid])[i0]);
+            if (base_ptrs) x0 = x0 - SvdqIn<TIN>::cvt(reinterpret_cast<const uint16_t *>(base_ptrs[p])[i0]);
+        }
         lam[tid] = (double)x0;
     }
     phase_sync<THREADS>();

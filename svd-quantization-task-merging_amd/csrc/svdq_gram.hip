@@ -10,7 +10,8 @@
 // whole unit), which resolves singular values down to ~1e-6 sigma_0 like the reference's LAPACK path; the fp32 form
 // (fp32 sums inside a 256-row block) only reaches ~1e-3..1e-4 sigma_0.  Pass 1 is HBM-bound for N <= 16, so the fp64
 // form is the default there; N > 16 would become MFMA-bound and keeps fp32 products.
-template <int NTP, int MODE = 0, bool F64 = false, bool FULL = false>
+// TIN: element type of the task / base tensors (svdq_input.h), widened to fp32 by the loaders; float for the walk.
+template <int NTP, int MODE = 0, bool F64 = false, bool FULL = false, typename TIN = float>
 __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *__restrict__ params,
                                           const SvdqUnit *__restrict__ units,
                                           const float *const *__restrict__ ptrs,
@@ -23,6 +24,7 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
     constexpr bool GATHER = (MODE & 1) != 0, SUB = (MODE & 2) != 0, WALK = (MODE & 4) != 0;
     static_assert(!(GATHER && WALK), "index lists and the mask walk are alternatives");
     static_assert(!(MODE != 0 && SVDQ_PREFETCH2), "gather / minus-base support the one-block-ahead pipeline only");
+    static_assert(!WALK || sizeof(TIN) == 4, "the mask walk reads fp32 tensors only");
     const int NT = FULL ? NTP : NT_arg;      // FULL: the plan has exactly NTP tasks, the "task t is real" tests fold away
     constexpr int PACK = (NTP <= 8) ? 2 : 1;
     constexpr int NB = (NTP + 15) / 16;
@@ -62,9 +64,9 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
     int64_t r_end = r_begin + ud.nrows;
     if (r_end > D) r_end = D;
 
-    gfloat *bp[NTP];
+    gin<TIN> *bp[NTP];
 #pragma unroll
-    for (int t = 0; t < NTP; ++t) bp[t] = (gfloat *)ptrs[(size_t)p * NT + (t < NT ? t : NT - 1)];
+    for (int t = 0; t < NTP; ++t) bp[t] = (gin<TIN> *)ptrs[(size_t)p * NT + (t < NT ? t : NT - 1)];
 
     const int c = lane & 15, g = lane >> 4;
     double accd[NACC][4];
@@ -113,28 +115,28 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
     f32x4 v0[NTP];
     gint *gidx = nullptr;
     i32x4 ixn = {-1, -1, -1, -1};  // indices of the block after the one whose data is in flight
-    gfloat *gbase = nullptr;
+    gin<TIN> *gbase = nullptr;
     f32x4 vb = zero4();  // base rows of the block whose fine-tuned rows sit in v
-    if constexpr (SUB) gbase = (gfloat *)aux2[p];
+    if constexpr (SUB) gbase = (gin<TIN> *)aux2[p];
     if constexpr (WALK) {
         // loads are issued by the walk loop below
     } else if constexpr (GATHER) {
         gidx = (gint *)aux[p];
         if (r_begin < r_end) {
             const i32x4 ix0 = load_idx(gidx, r_begin, D, lane);
-            load_block_gather<NTP>(v0, bp, ix0, r_begin + SVDQ_BLK_ROWS <= D);
-            if constexpr (SUB) vb = load_base_gather(gbase, ix0, r_begin + SVDQ_BLK_ROWS <= D);
+            load_block_gather<NTP, TIN>(v0, bp, ix0, r_begin + SVDQ_BLK_ROWS <= D);
+            if constexpr (SUB) vb = load_base_gather<TIN>(gbase, ix0, r_begin + SVDQ_BLK_ROWS <= D);
             if (r_begin + SVDQ_BLK_ROWS < r_end) ixn = load_idx(gidx, r_begin + SVDQ_BLK_ROWS, D, lane);
         }
     } else {
-        if (r_begin < r_end) load_block<NTP>(v0, bp, r_begin, D, lane);
+        if (r_begin < r_end) load_block<NTP, TIN>(v0, bp, r_begin, D, lane);
         if constexpr (SUB) {
-            if (r_begin < r_end) vb = load_base(gbase, r_begin, D, lane);
+            if (r_begin < r_end) vb = load_base<TIN>(gbase, r_begin, D, lane);
         }
     }
 #if SVDQ_PREFETCH2
     f32x4 v1[NTP];
-    if (r_begin + SVDQ_BLK_ROWS < r_end) load_block<NTP>(v1, bp, r_begin + SVDQ_BLK_ROWS, D, lane);
+    if (r_begin + SVDQ_BLK_ROWS < r_end) load_block<NTP, TIN>(v1, bp, r_begin + SVDQ_BLK_ROWS, D, lane);
 #endif
 
     // the MFMA phase over the strip of one block (ends with the barrier that frees the strip)
@@ -335,12 +337,12 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
             wave_sync();
             if (rb + AHEAD * SVDQ_BLK_ROWS < r_end) {
                 if constexpr (GATHER) {
-                    load_block_gather<NTP>(v, bp, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
-                    if constexpr (SUB) vb = load_base_gather(gbase, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
+                    load_block_gather<NTP, TIN>(v, bp, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
+                    if constexpr (SUB) vb = load_base_gather<TIN>(gbase, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
                     if (rb + 2 * SVDQ_BLK_ROWS < r_end) ixn = load_idx(gidx, rb + 2 * SVDQ_BLK_ROWS, D, lane);
                 } else {
-                    load_block<NTP>(v, bp, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
-                    if constexpr (SUB) vb = load_base(gbase, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
+                    load_block<NTP, TIN>(v, bp, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
+                    if constexpr (SUB) vb = load_base<TIN>(gbase, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
                 }
             }
             compute();
@@ -455,7 +457,7 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
 #define SVDQ_GRAM64_WAVES16 3
 #endif
 SVDQ_STAMP_DECL(svdq_stamps_gram)
-template <int NTP, int MODE, bool F64, bool FULL>
+template <int NTP, int MODE, bool F64, bool FULL, typename TIN>
 __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) ? (NTP <= 8 ? SVDQ_GRAM64_WAVES8 : SVDQ_GRAM64_WAVES16) : 1) void k_gram(const SvdqParam *__restrict__ params,
                                              const SvdqUnit *__restrict__ units,
                                              const float *const *__restrict__ ptrs,
@@ -468,7 +470,7 @@ __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) 
     __shared__ __attribute__((aligned(16))) float X[NTP * XS];
     SVDQ_STAMP_BEGIN();
     const int uidx = unit0 + unit_of_block((int)blockIdx.x, (int)gridDim.x, order);
-    gram_unit<NTP, MODE, F64, FULL>(X, uidx, params, units, ptrs, rows_dev, NT, center, gram_part, aux, only, aux2, ustart);
+    gram_unit<NTP, MODE, F64, FULL, TIN>(X, uidx, params, units, ptrs, rows_dev, NT, center, gram_part, aux, only, aux2, ustart);
     SVDQ_STAMP_END(svdq_stamps_gram, uidx);
 }
 
@@ -476,14 +478,14 @@ __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) 
 // idx: NULL or the device table of index lists (gather mode); base: NULL or the device table of base tensors
 // (minus-base mode); both may be given (masked parameters straight from checkpoints).  ustart: NULL, or the per-unit
 // source start positions of the walk mode -- idx is then the device table of combined MASK byte tensors.
-template <int NTP>
+template <int NTP, typename TIN>
 static int launch_gram_t(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, double *gram_part,
                          int unit0, int nunits, int center, const void *idx, const void *base, int f64,
                          const int32_t *only, const int64_t *ustart, hipStream_t st) {
     auto pp = reinterpret_cast<const float *const *>(ptrs);
     auto ai = (const void *const *)idx, ab = (const void *const *)base;
 #define SVDQ_LAUNCH_GRAM_(M, F, FULL_)                                                                                     \
-    hipLaunchKernelGGL((k_gram<NTP, M, F, FULL_>), dim3(nunits), dim3(64), 0, st, pl->d_params, pl->d_units, pp, rows_dev, \
+    hipLaunchKernelGGL((k_gram<NTP, M, F, FULL_, TIN>), dim3(nunits), dim3(64), 0, st, pl->d_params, pl->d_units, pp, rows_dev, \
                        pl->n_tasks, center, gram_part, unit0, ai, only, ab, pl->cfg.reserved & 4, ustart)
     // the plain and the mask-walk mode have a variant for plans with exactly NTP tasks
 #define SVDQ_LAUNCH_GRAM(M, F)                                                                                       \
@@ -497,7 +499,12 @@ static int launch_gram_t(const svdq_plan *pl, const void *ptrs, const int64_t *r
         SVDQ_LAUNCH_GRAM_(M, F, false);                                                                              \
     } while (0)
     const int mode = ustart ? (4 | (base ? 2 : 0)) : ((idx ? 1 : 0) | (base ? 2 : 0));
-    if constexpr (NTP <= 16) {
+    if constexpr (sizeof(TIN) != 4) {   // half inputs: modes 0..3 only (the walk is instantiated for fp32)
+        if (mode & 4) {
+            svdq_set_error("the mask walk reads fp32 task tensors only");
+            return SVDQ_EUNSUPPORTED;
+        }
+    } else if constexpr (NTP <= 16) {
         if (mode & 4) {      // walk mode exists for the one-wave kernels (N <= 16), always with the default Gram
             if (f64) {
                 if (mode == 4) SVDQ_LAUNCH_GRAM(4, true); else SVDQ_LAUNCH_GRAM(6, true);
@@ -513,7 +520,9 @@ static int launch_gram_t(const svdq_plan *pl, const void *ptrs, const int64_t *r
                            "(svdq_compress_gather_from_base)", pl->n_tasks);
             return SVDQ_EUNSUPPORTED;
         }
-        if (f64) SVDQ_LAUNCH_GRAM_(4, true, false); else SVDQ_LAUNCH_GRAM_(4, false, false);
+        if constexpr (sizeof(TIN) == 4) {
+            if (f64) SVDQ_LAUNCH_GRAM_(4, true, false); else SVDQ_LAUNCH_GRAM_(4, false, false);
+        }
         return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
     }
     if (f64) {
@@ -542,11 +551,11 @@ int svdq_launch_gram(const svdq_plan *pl, const void *ptrs, const int64_t *rows_
                      int unit0, int nunits, int center, const void *idx, const void *base, int f64,
                      const int32_t *only, hipStream_t st, const int64_t *ustart) {
 #define SVDQ_GRAM_CASE(n) \
-    case n: return launch_gram_t<n>(pl, ptrs, rows_dev, gram_part, unit0, nunits, center, idx, base, f64, only, ustart, st)
-    switch (pl->ntp) {
+    case n: return launch_gram_t<n, TIN>(pl, ptrs, rows_dev, gram_part, unit0, nunits, center, idx, base, f64, only, ustart, st)
+    SVDQ_DISPATCH_INPUT(pl, TIN, switch (pl->ntp) {
         SVDQ_GRAM_CASE(4); SVDQ_GRAM_CASE(8); SVDQ_GRAM_CASE(12); SVDQ_GRAM_CASE(16);
         SVDQ_GRAM_CASE(20); SVDQ_GRAM_CASE(24); SVDQ_GRAM_CASE(28); SVDQ_GRAM_CASE(32);
-    }
+    });
 #undef SVDQ_GRAM_CASE
     svdq_set_error("unsupported padded task count %d", pl->ntp);
     return SVDQ_EUNSUPPORTED;

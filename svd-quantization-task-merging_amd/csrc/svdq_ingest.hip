@@ -396,6 +396,7 @@ extern "C" int svdq_ingest(const svdq_plan *pl, const void *base_ptrs, const voi
         svdq_set_error("null argument");
         return SVDQ_EINVAL;
     }
+    if (int rc = svdq_require_f32_input(pl, "svdq_ingest")) return rc;
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto fp = reinterpret_cast<const float *const *>(finetuned_ptrs);
     auto dp = reinterpret_cast<float *const *>(delta_ptrs);
@@ -412,6 +413,7 @@ extern "C" int svdq_tvq_quantize(const svdq_plan *pl, const void *x_ptrs, int32_
                                  const void *code_ptrs, float *scale, float *zero_point, void *work,
                                  int32_t stats_ready, void *stream) {
     if (int rc = tvq_check(pl, mode, bits)) return rc;
+    if (int rc = svdq_require_f32_input(pl, "svdq_tvq_quantize")) return rc;
     if (!x_ptrs || !code_ptrs || !scale || !work || (mode == 0 && !zero_point)) {
         svdq_set_error("null argument");
         return SVDQ_EINVAL;
@@ -437,6 +439,8 @@ extern "C" int svdq_tvq_quantize(const svdq_plan *pl, const void *x_ptrs, int32_
 extern "C" int svdq_tvq_dequantize(const svdq_plan *pl, const void *code_ptrs, int32_t mode, const float *scale,
                                    const float *zero_point, const void *add_ptrs, const void *out_ptrs,
                                    void *stream) {
+    if (pl)
+        if (int rc = svdq_require_f32_input(pl, "svdq_tvq_dequantize")) return rc;
     if (mode == 2) {  // absmax with int16 codes
         if (!pl || !code_ptrs || !scale || !out_ptrs) {
             svdq_set_error("null argument");

@@ -24,6 +24,7 @@
 // (the diagnostics' sums run in another order: equal to the last digits of the fp64 accumulators).
 
 #include "svdq_common.h"
+#include "svdq_input.h"
 #include <hip/hip_fp16.h>
 
 #define MRG_MAX_SETS 8
@@ -543,7 +544,8 @@ template <bool B> struct DiagBool { static constexpr bool value = B; };
 #else
 #define SVDQ_DIAG_ATTR
 #endif
-template <int NTP, int RPL_, int SETS, bool FULL, bool U16, bool WALK>
+// TIN: element type of the task tensors (svdq_input.h), widened to fp32 by the loads; float for the walk.
+template <int NTP, int RPL_, int SETS, bool FULL, bool U16, bool WALK, typename TIN = float>
 __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__restrict__ params, const SvdqUnit *__restrict__ units,
                                              const float *const *__restrict__ ptrs,
                                              const uint8_t *const *__restrict__ mask_ptrs,
@@ -555,6 +557,7 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
     using T = typename UElem<U16>::type;
     using G = DiagGeom<NTP, RPL_, SETS>;
     static_assert(SETS == 1 || (RPL_ == 4 && NTP * SETS <= 16), "packed row sets: 16 / SETS tasks each, 256-row blocks");
+    static_assert(!WALK || sizeof(TIN) == 4, "the mask walk reads fp32 tensors only");
     constexpr bool PACK = SETS > 1;
     constexpr int TPS = 16 / SETS;      // tasks (and K slots) per row set
     constexpr int SPS = 4 / SETS;       // K steps per row set
@@ -620,9 +623,9 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
         const uint8_t *gUl = slab + svdq_align_up(D * (int64_t)k * ES, 256);
         mg_gfloat *gmean = (add_mean && meanbuf) ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
         mg_gbyte *gmask = WALK ? (mg_gbyte *)mask_ptrs[p] : nullptr;
-        mg_gfloat *dp[NTP];
+        gin<TIN> *dp[NTP];
 #pragma unroll
-        for (int t = 0; t < NTP; ++t) dp[t] = (mg_gfloat *)ptrs[(size_t)p * n + (t < n ? t : 0)];
+        for (int t = 0; t < NTP; ++t) dp[t] = (gin<TIN> *)ptrs[(size_t)p * n + (t < n ? t : 0)];
         int64_t src = cpos, src_hi = cend;      // plain: source rows = compacted rows
         int inv = 0;
         if constexpr (WALK) {
@@ -668,13 +671,13 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                     for (int t = 0; t < NTP; ++t)
                         if (t < n) {
                             if constexpr (RPL == 4) {
-                                const f32x4 v = *reinterpret_cast<mg_gf32x4 *>(dp[t] + r0);
+                                const f32x4 v = in_load4<TIN>(dp[t] + r0);
                                 xpf[t][0] = v.x, xpf[t][1] = v.y, xpf[t][2] = v.z, xpf[t][3] = v.w;
                             } else if constexpr (RPL == 2) {
-                                const f32x2 v = *reinterpret_cast<mg_gf32x2 *>(dp[t] + r0);
+                                const f32x2 v = in_load2<TIN>(dp[t] + r0);
                                 xpf[t][0] = v.x, xpf[t][1] = v.y;
                             } else {
-                                xpf[t][0] = dp[t][r0];
+                                xpf[t][0] = in_load1<TIN>(dp[t] + r0);
                             }
                         }
                 } else {
@@ -682,7 +685,7 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                     for (int t = 0; t < NTP; ++t)
                         if (t < n) {
 #pragma unroll
-                            for (int e = 0; e < RPL; ++e) xpf[t][e] = (r0 + e < src_hi) ? dp[t][r0 + e] : 0.f;
+                            for (int e = 0; e < RPL; ++e) xpf[t][e] = (r0 + e < src_hi) ? in_load1<TIN>(dp[t] + (r0 + e)) : 0.f;
                         }
                 }
             }
@@ -1096,7 +1099,7 @@ __global__ void k_one_hot(int n, float *w) {
 #ifndef SVDQ_DIAG_RPL_MID
 #define SVDQ_DIAG_RPL_MID 2      // rows per lane and block of the 9..24-task variants (A/B builds)
 #endif
-template <int NTP, int RPL, int SETS, bool FULL>
+template <int NTP, int RPL, int SETS, bool FULL, typename TIN>
 static void launch_diag(const svdq_plan *pl, const void *ptrs, const void *mask_ptrs, const int64_t *unit_start,
                         const int64_t *rows_dev, const int32_t *kk, const int32_t *rr, const uint8_t *basis,
                         const float *mean, int add_mean, const float *ctask, DiagPart *part, hipStream_t st) {
@@ -1107,9 +1110,12 @@ static void launch_diag(const svdq_plan *pl, const void *ptrs, const void *mask_
     const size_t lds = (size_t)svdq_align_up((int64_t)G::RB * n * es + 48, 16) +
                        (size_t)(NTP + 1) * diag_xs(G::RB, mp != nullptr) * 4;
 #define SVDQ_DIAG_LAUNCH(F16, WALK_)                                                                                   \
-    hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK_>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params, \
-                       pl->d_units, pp, mp, unit_start, rows_dev, n, kk, rr, basis, mean, add_mean, ctask, part)
-    if (pl->cfg.fp16) {
+    hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK_, TIN>), dim3(pl->n_units), dim3(64), lds, st,           \
+                       pl->d_params, pl->d_units, pp, mp, unit_start, rows_dev, n, kk, rr, basis, mean, add_mean, ctask,  \
+                       part)
+    if constexpr (sizeof(TIN) != 4) {   // half inputs: the plain form only (svdq_diagnostics_masked rejects them)
+        if (pl->cfg.fp16) SVDQ_DIAG_LAUNCH(true, false); else SVDQ_DIAG_LAUNCH(false, false);
+    } else if (pl->cfg.fp16) {
         if (mp) SVDQ_DIAG_LAUNCH(true, true); else SVDQ_DIAG_LAUNCH(true, false);
     } else {
         if (mp) SVDQ_DIAG_LAUNCH(false, true); else SVDQ_DIAG_LAUNCH(false, false);
@@ -1142,10 +1148,9 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
     // exactly that many tasks
 #define SVDQ_DIAG_ARGS pl, delta_ptrs, mask_ptrs, unit_start, rows_dev, kk, rr, bs, mean, add_mean, ctask, part, st
 #define SVDQ_DIAG_PICK(NTP_, RPL_, PACK_)                                                                              \
-    do {                                                                                                               \
-        if (n == NTP_) launch_diag<NTP_, RPL_, PACK_, true>(SVDQ_DIAG_ARGS);                                            \
-        else launch_diag<NTP_, RPL_, PACK_, false>(SVDQ_DIAG_ARGS);                                                     \
-    } while (0)
+    SVDQ_DISPATCH_INPUT(pl, TIN,                                                                                       \
+        if (n == NTP_) launch_diag<NTP_, RPL_, PACK_, true, TIN>(SVDQ_DIAG_ARGS);                                       \
+        else launch_diag<NTP_, RPL_, PACK_, false, TIN>(SVDQ_DIAG_ARGS))
     if (n <= 4) SVDQ_DIAG_PICK(4, 4, 4);
     else if (n <= 8) SVDQ_DIAG_PICK(8, 4, 2);
     else if (n <= 12) SVDQ_DIAG_PICK(12, SVDQ_DIAG_RPL_MID, 1);
@@ -1179,6 +1184,8 @@ extern "C" int svdq_diagnostics_masked(const svdq_plan *pl, const void *delta_pt
         svdq_set_error("svdq_diagnostics_masked: mask_ptrs, unit_start and rows_dev are required");
         return SVDQ_EINVAL;
     }
+    if (pl)
+        if (int rc = svdq_require_f32_input(pl, "svdq_diagnostics_masked")) return rc;
     return run_diagnostics("svdq_diagnostics_masked", pl, delta_ptrs, mask_ptrs, unit_start, rows_dev, small, basis, mean,
                            add_mean, out, work, stream);
 }

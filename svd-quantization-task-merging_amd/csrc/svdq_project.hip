@@ -51,12 +51,12 @@ __device__ __forceinline__ f32x4 center_store_half(const f32x4 (&v)[HT], int t0,
 }
 
 // first block + one-block-ahead loads of one wave's HT tasks (contiguous or through the index list)
-template <int HT, int MODE>
+template <int HT, int MODE, typename TIN>
 struct HalfLoader {
     static constexpr bool GATHER = (MODE & 1) != 0, SUB = (MODE & 2) != 0;
-    gfloat *bp[HT];
+    gin<TIN> *bp[HT];
     gint *gidx;
-    gfloat *gbase;
+    gin<TIN> *gbase;
     i32x4 ixn;
     f32x4 vb;
     int64_t D, r_end;
@@ -73,23 +73,23 @@ struct HalfLoader {
         if (r_begin >= r_end) return;
         if constexpr (GATHER) {
             const i32x4 ix0 = load_idx(gidx, r_begin, D, lane);
-            load_block_gather<HT>(v, bp, ix0, r_begin + SVDQ_BLK_ROWS <= D);
-            if constexpr (SUB) vb = load_base_gather(gbase, ix0, r_begin + SVDQ_BLK_ROWS <= D);
+            load_block_gather<HT, TIN>(v, bp, ix0, r_begin + SVDQ_BLK_ROWS <= D);
+            if constexpr (SUB) vb = load_base_gather<TIN>(gbase, ix0, r_begin + SVDQ_BLK_ROWS <= D);
             if (r_begin + SVDQ_BLK_ROWS < r_end) ixn = load_idx(gidx, r_begin + SVDQ_BLK_ROWS, D, lane);
         } else {
-            if constexpr (SUB) vb = load_base(gbase, r_begin, D, lane);
-            load_block<HT>(v, bp, r_begin, D, lane);
+            if constexpr (SUB) vb = load_base<TIN>(gbase, r_begin, D, lane);
+            load_block<HT, TIN>(v, bp, r_begin, D, lane);
         }
     }
     __device__ __forceinline__ void next(f32x4 (&v)[HT], int64_t rb) {  // data of block rb + 256
         if (rb + SVDQ_BLK_ROWS >= r_end) return;
         if constexpr (GATHER) {
-            load_block_gather<HT>(v, bp, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
-            if constexpr (SUB) vb = load_base_gather(gbase, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
+            load_block_gather<HT, TIN>(v, bp, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
+            if constexpr (SUB) vb = load_base_gather<TIN>(gbase, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
             if (rb + 2 * SVDQ_BLK_ROWS < r_end) ixn = load_idx(gidx, rb + 2 * SVDQ_BLK_ROWS, D, lane);
         } else {
-            load_block<HT>(v, bp, rb + SVDQ_BLK_ROWS, D, lane);
-            if constexpr (SUB) vb = load_base(gbase, rb + SVDQ_BLK_ROWS, D, lane);
+            load_block<HT, TIN>(v, bp, rb + SVDQ_BLK_ROWS, D, lane);
+            if constexpr (SUB) vb = load_base<TIN>(gbase, rb + SVDQ_BLK_ROWS, D, lane);
         }
     }
 };
@@ -104,7 +104,7 @@ __device__ __forceinline__ void copy_out_wg(const void *lds_src, uint8_t *gdst, 
         *reinterpret_cast<uint16_t *>(gdst + b) = *reinterpret_cast<const uint16_t *>(sb + b);
 }
 
-template <int NTP, bool OUT16, int MODE>
+template <int NTP, bool OUT16, int MODE, typename TIN>
 __global__ __launch_bounds__(128) void k_basis_project2(
     const SvdqParam *__restrict__ params, const SvdqUnit *__restrict__ units,
     const float *const *__restrict__ ptrs, const int64_t *__restrict__ rows_dev, int NT, int center,
@@ -132,11 +132,11 @@ __global__ __launch_bounds__(128) void k_basis_project2(
     const int k = k_dev[p], r = r_dev[p], nl = r - k;
     const int t0 = wv * HT;
 
-    HalfLoader<HT, MODE> ld;
+    HalfLoader<HT, MODE, TIN> ld;
 #pragma unroll
-    for (int i = 0; i < HT; ++i) ld.bp[i] = (gfloat *)ptrs[(size_t)p * NT + (t0 + i < NT ? t0 + i : NT - 1)];
+    for (int i = 0; i < HT; ++i) ld.bp[i] = (gin<TIN> *)ptrs[(size_t)p * NT + (t0 + i < NT ? t0 + i : NT - 1)];
     ld.gidx = GATHER ? (gint *)aux[p] : nullptr;
-    ld.gbase = (MODE & 2) ? (gfloat *)aux2[p] : nullptr;
+    ld.gbase = (MODE & 2) ? (gin<TIN> *)aux2[p] : nullptr;
     ld.D = D;
     ld.r_end = r_end;
     ld.lane = lane;
@@ -315,7 +315,7 @@ __device__ __forceinline__ s16x4 pack_bf16x4(const f32x4 &x) {
 // lane mask the compiler keeps in a scalar-register pair across the loop -- twenty of them, which is what pushed the
 // twenty task pointers out of the scalar registers (a v_readlane pair + a 64-bit vector add per load) and put a
 // v_cndmask on every value of the centring (round 3: ~200 of ~1 000 wave instructions per half block).
-template <int NTP, bool OUT16, int MODE, bool FULL>
+template <int NTP, bool OUT16, int MODE, bool FULL, typename TIN>
 __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
     const SvdqParam *__restrict__ params, const SvdqUnit *__restrict__ units,
     const float *const *__restrict__ ptrs, const int64_t *__restrict__ rows_dev, int NT_arg, int center,
@@ -353,11 +353,11 @@ __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
 #define SVDQ_Q_PTR_RELOAD 0   // measured: the scalar loads in front of every half block cost more than the readlanes
 #endif
     const float *const *ptab = ptrs + (size_t)p * NT;
-    gfloat *bp[NTP];
+    gin<TIN> *bp[NTP];
 #pragma unroll
-    for (int t = 0; t < NTP; ++t) bp[t] = (gfloat *)ptab[t < NT ? t : NT - 1];
+    for (int t = 0; t < NTP; ++t) bp[t] = (gin<TIN> *)ptab[t < NT ? t : NT - 1];
     gint *gidx = GATHER ? (gint *)aux[p] : nullptr;
-    gfloat *gbase = SUB ? (gfloat *)aux2[p] : nullptr;
+    gin<TIN> *gbase = SUB ? (gin<TIN> *)aux2[p] : nullptr;
 
     const int c = lane & 15, g = lane >> 4;     // 16x16 tile coordinates
     const int b4 = lane >> 2, j4 = lane & 3;    // 4x4 block, column inside the block
@@ -413,6 +413,12 @@ __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
     // loads of one half block: lane owns rows 2 lane, 2 lane + 1 (gather mode: rows lane, 64 + lane)
     f32x2 v[NTP];
     f32x2 vb = {0.f, 0.f};
+    // half inputs: a task's two elements stay packed in one 32-bit word (vr) until the half block is consumed, so the
+    // next half block's loads stay in flight behind the MFMA phase -- widened right at the load, they were waited for
+    // there (measured: pass 2 at N = 20 twice as slow as with fp32 inputs)
+    constexpr bool RAW = sizeof(TIN) != 4;
+    uint32_t vr[RAW ? NTP : 1];
+    uint32_t vbr = 0;
     int ixa = -1, ixb = -1;      // gather mode: source positions of the NEXT half block's two rows
     auto load_idx2 = [&](int64_t rb) {
         const int64_t ra = rb + lane, rc = rb + 64 + lane;
@@ -422,45 +428,72 @@ __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
     auto load_half = [&](int64_t rb) {
         // (the index depends on rb only formally: it keeps the pointer loads inside the loop)
         const int hop = (int)(rb >> 62);
-        if constexpr (GATHER) {
+        if constexpr (RAW) {
+            (void)hop;
+            typedef const __attribute__((address_space(1))) uint32_t g32;
+            auto pack = [](uint32_t lo, uint32_t hi) -> uint32_t { return lo | (hi << 16); };
+            if constexpr (GATHER) {
+#pragma unroll
+                for (int t = 0; t < NTP; ++t)
+                    vr[t] = pack(ixa >= 0 ? (uint32_t)bp[t][ixa] : 0u, ixb >= 0 ? (uint32_t)bp[t][ixb] : 0u);
+                if constexpr (SUB) vbr = pack(ixa >= 0 ? (uint32_t)gbase[ixa] : 0u, ixb >= 0 ? (uint32_t)gbase[ixb] : 0u);
+            } else {
+                const int64_t rr = rb + 2 * lane;
+                if (rb + HB <= D) {
+                    const uint32_t boff = ((uint32_t)(rb - r_begin) + 2u * (uint32_t)lane) * 2u;
+#pragma unroll
+                    for (int t = 0; t < NTP; ++t)
+                        vr[t] = *reinterpret_cast<g32 *>(
+                            reinterpret_cast<const __attribute__((address_space(1))) char *>(bp[t] + r_begin) + boff);
+                    if constexpr (SUB) vbr = *reinterpret_cast<g32 *>(gbase + rr);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < NTP; ++t)
+                        vr[t] = pack(rr < D ? (uint32_t)bp[t][rr] : 0u, rr + 1 < D ? (uint32_t)bp[t][rr + 1] : 0u);
+                    if constexpr (SUB)
+                        vbr = pack(rr < D ? (uint32_t)gbase[rr] : 0u, rr + 1 < D ? (uint32_t)gbase[rr + 1] : 0u);
+                }
+            }
+        } else if constexpr (GATHER) {
 #pragma unroll
             for (int t = 0; t < NTP; ++t) {
-                gfloat *bt = SVDQ_Q_PTR_RELOAD ? (gfloat *)ptab[(t < NT ? t : NT - 1) + hop] : bp[t];
+                gin<TIN> *bt = SVDQ_Q_PTR_RELOAD ? (gin<TIN> *)ptab[(t < NT ? t : NT - 1) + hop] : bp[t];
                 f32x2 o = {0.f, 0.f};
-                if (ixa >= 0) o.x = bt[ixa];
-                if (ixb >= 0) o.y = bt[ixb];
+                if (ixa >= 0) o.x = in_load1<TIN>(bt + ixa);
+                if (ixb >= 0) o.y = in_load1<TIN>(bt + ixb);
                 v[t] = o;
             }
             if constexpr (SUB) {
                 vb = f32x2{0.f, 0.f};
-                if (ixa >= 0) vb.x = gbase[ixa];
-                if (ixb >= 0) vb.y = gbase[ixb];
+                if (ixa >= 0) vb.x = in_load1<TIN>(gbase + ixa);
+                if (ixb >= 0) vb.y = in_load1<TIN>(gbase + ixb);
             }
         } else {
             const int64_t rr = rb + 2 * lane;
             // BYTE offset past the unit's first row, 32 bits: scalar base + 32-bit vector offset is an addressing mode
             // of global_load (a 64-bit element offset makes every load a 64-bit vector add first)
-            const uint32_t boff = ((uint32_t)(rb - r_begin) + 2u * (uint32_t)lane) * 4u;
+            const uint32_t boff = ((uint32_t)(rb - r_begin) + 2u * (uint32_t)lane) * (uint32_t)sizeof(*bp[0]);
             if (rb + HB <= D) {
 #pragma unroll
                 for (int t = 0; t < NTP; ++t) {
-                    gfloat *bt = (SVDQ_Q_PTR_RELOAD ? (gfloat *)ptab[(t < NT ? t : NT - 1) + hop] : bp[t]) + r_begin;
-                    v[t] = *reinterpret_cast<gf32x2 *>(reinterpret_cast<const __attribute__((address_space(1))) char *>(bt) + boff);
+                    gin<TIN> *bt = (SVDQ_Q_PTR_RELOAD ? (gin<TIN> *)ptab[(t < NT ? t : NT - 1) + hop] : bp[t]) + r_begin;
+                    v[t] = in_load2<TIN>(reinterpret_cast<gin<TIN> *>(
+                        reinterpret_cast<const __attribute__((address_space(1))) char *>(bt) + boff));
                 }
-                if constexpr (SUB) vb = *reinterpret_cast<gf32x2 *>(gbase + rr);
+                if constexpr (SUB) vb = in_load2<TIN>(gbase + rr);
             } else {
 #pragma unroll
                 for (int t = 0; t < NTP; ++t) {
-                    gfloat *bt = SVDQ_Q_PTR_RELOAD ? (gfloat *)ptab[(t < NT ? t : NT - 1) + hop] : bp[t];
+                    gin<TIN> *bt = SVDQ_Q_PTR_RELOAD ? (gin<TIN> *)ptab[(t < NT ? t : NT - 1) + hop] : bp[t];
                     f32x2 o = {0.f, 0.f};
-                    if (rr < D) o.x = bt[rr];
-                    if (rr + 1 < D) o.y = bt[rr + 1];
+                    if (rr < D) o.x = in_load1<TIN>(bt + rr);
+                    if (rr + 1 < D) o.y = in_load1<TIN>(bt + (rr + 1));
                     v[t] = o;
                 }
                 if constexpr (SUB) {
                     vb = f32x2{0.f, 0.f};
-                    if (rr < D) vb.x = gbase[rr];
-                    if (rr + 1 < D) vb.y = gbase[rr + 1];
+                    if (rr < D) vb.x = in_load1<TIN>(gbase + rr);
+                    if (rr + 1 < D) vb.y = in_load1<TIN>(gbase + (rr + 1));
                 }
             }
         }
@@ -480,6 +513,11 @@ __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
         for (int t = 0; t < NTP; ++t) w1r[q][t] = W1[t * N1 + 4 * q + j4];
 
     for (int64_t rb = r_begin; rb < r_end; rb += HB) {
+        if constexpr (RAW) {   // (zero words widen to 0.f in both half formats)
+#pragma unroll
+            for (int t = 0; t < NTP; ++t) v[t] = in_widen2<TIN>(vr[t]);
+            if constexpr (SUB) vb = in_widen2<TIN>(vbr);
+        }
         // ---- centre (same association as pass 1 at N > 16: two halves of the tasks), park the strip, write the mean
         if constexpr (SUB) {
 #pragma unroll
@@ -646,16 +684,21 @@ __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
 }
 
 // ------------------------------------------------------------------------------------ launchers
-template <int NTP, bool F16>
+template <int NTP, bool F16, typename TIN>
 static int launch_bp_mode(const svdq_plan *pl, const float *const *pp, const int64_t *rows_dev, const float *W,
                           const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart,
                           int unit0, int nunits, int reverse, const void *idx, const void *base,
                           const int64_t *ustart, hipStream_t st) {
     auto ai = (const void *const *)idx, ab = (const void *const *)base;
-    if (ustart) {
+    if constexpr (sizeof(TIN) != 4) {   // half inputs: modes 0..3 only (the walk is instantiated for fp32)
+        if (ustart) {
+            svdq_set_error("the mask walk reads fp32 task tensors only");
+            return SVDQ_EUNSUPPORTED;
+        }
+    } else if (ustart) {
         if constexpr (NTP <= 16) {
 #define SVDQ_LAUNCH_BPW(M, FULL_)                                                                                     \
-    hipLaunchKernelGGL((k_basis_project<NTP, F16, M, FULL_>), dim3(nunits), dim3(64), 0, st, pl->d_params, pl->d_units, \
+    hipLaunchKernelGGL((k_basis_project<NTP, F16, M, FULL_, float>), dim3(nunits), dim3(64), 0, st, pl->d_params, pl->d_units, \
                        pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean, cpart, unit0, reverse, \
                        ai, ab, ustart)
             if (pl->n_tasks == NTP) {
@@ -679,26 +722,26 @@ static int launch_bp_mode(const svdq_plan *pl, const float *const *pp, const int
         if constexpr (NTP == 20) {   /* N = 21..24: measured slower than the two-wave kernel (11.9 against 10.0 ms) */ \
             if (!(pl->cfg.reserved & 8)) {   /* bit 3: the two-wave kernel instead (A/B) */                           \
                 if (pl->n_tasks == NTP)                                                                               \
-                    hipLaunchKernelGGL((k_basis_project_q<NTP, F16, M, true>), dim3(nunits), dim3(64), 0, st,         \
+                    hipLaunchKernelGGL((k_basis_project_q<NTP, F16, M, true, TIN>), dim3(nunits), dim3(64), 0, st,         \
                                        pl->d_params, pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, \
                                        r_dev, basis, mean, cpart, unit0, reverse, ai, ab);                            \
                 else                                                                                                  \
-                    hipLaunchKernelGGL((k_basis_project_q<NTP, F16, M, false>), dim3(nunits), dim3(64), 0, st,        \
+                    hipLaunchKernelGGL((k_basis_project_q<NTP, F16, M, false, TIN>), dim3(nunits), dim3(64), 0, st,        \
                                        pl->d_params, pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, \
                                        r_dev, basis, mean, cpart, unit0, reverse, ai, ab);                            \
                 break;                                                                                                \
             }                                                                                                         \
         }                                                                                                             \
         if constexpr (NTP > 16)                                                                                       \
-            hipLaunchKernelGGL((k_basis_project2<NTP, F16, M>), dim3(nunits), dim3(128), 0, st, pl->d_params,         \
+            hipLaunchKernelGGL((k_basis_project2<NTP, F16, M, TIN>), dim3(nunits), dim3(128), 0, st, pl->d_params,         \
                                pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean,  \
                                cpart, unit0, reverse, ai, ab);                                                        \
         else if (pl->n_tasks == NTP)                                                                                  \
-            hipLaunchKernelGGL((k_basis_project<NTP, F16, M, true>), dim3(nunits), dim3(64), 0, st, pl->d_params,     \
+            hipLaunchKernelGGL((k_basis_project<NTP, F16, M, true, TIN>), dim3(nunits), dim3(64), 0, st, pl->d_params,     \
                                pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean,  \
                                cpart, unit0, reverse, ai, ab, (const int64_t *)nullptr);                              \
         else                                                                                                          \
-            hipLaunchKernelGGL((k_basis_project<NTP, F16, M, false>), dim3(nunits), dim3(64), 0, st, pl->d_params,    \
+            hipLaunchKernelGGL((k_basis_project<NTP, F16, M, false, TIN>), dim3(nunits), dim3(64), 0, st, pl->d_params,    \
                                pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean,  \
                                cpart, unit0, reverse, ai, ab, (const int64_t *)nullptr);                              \
     } while (0)
@@ -712,7 +755,7 @@ static int launch_bp_mode(const svdq_plan *pl, const float *const *pp, const int
     return SVDQ_OK;
 }
 
-template <int NTP>
+template <int NTP, typename TIN>
 static int launch_bp_t(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, const float *W,
                        const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart,
                        int unit0, int nunits, int reverse, const void *idx, const void *base, const int64_t *ustart,
@@ -720,9 +763,9 @@ static int launch_bp_t(const svdq_plan *pl, const void *ptrs, const int64_t *row
     auto pp = reinterpret_cast<const float *const *>(ptrs);
     int rc;
     if (pl->cfg.fp16)
-        rc = launch_bp_mode<NTP, true>(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st);
+        rc = launch_bp_mode<NTP, true, TIN>(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st);
     else
-        rc = launch_bp_mode<NTP, false>(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st);
+        rc = launch_bp_mode<NTP, false, TIN>(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st);
     if (rc != SVDQ_OK) return rc;
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
@@ -732,11 +775,11 @@ int svdq_launch_basis_project(const svdq_plan *pl, const void *ptrs, const int64
                               double *cpart, int unit0, int nunits, int reverse, const void *idx, const void *base,
                               hipStream_t st, const int64_t *ustart) {
 #define SVDQ_BP_CASE(n) \
-    case n: return launch_bp_t<n>(pl, ptrs, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st)
-    switch (pl->ntp) {
+    case n: return launch_bp_t<n, TIN>(pl, ptrs, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st)
+    SVDQ_DISPATCH_INPUT(pl, TIN, switch (pl->ntp) {
         SVDQ_BP_CASE(4); SVDQ_BP_CASE(8); SVDQ_BP_CASE(12); SVDQ_BP_CASE(16);
         SVDQ_BP_CASE(20); SVDQ_BP_CASE(24); SVDQ_BP_CASE(28); SVDQ_BP_CASE(32);
-    }
+    });
 #undef SVDQ_BP_CASE
     svdq_set_error("unsupported padded task count %d", pl->ntp);
     return SVDQ_EUNSUPPORTED;

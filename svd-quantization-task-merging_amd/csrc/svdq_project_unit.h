@@ -49,7 +49,8 @@ __device__ __forceinline__ bf16x8 pack_bf16(const f32x4 &lo, const f32x4 &hi) {
 // One work unit of pass 2 by ONE wavefront.  X: NTP*XS floats, OUT: SVDQ_BLK_ROWS*NTP + 16 elements of
 // wave-private LDS.
 // FULL: the plan has exactly NTP tasks -- every "task t is real" test folds away (see k_basis_project_q)
-template <int NTP, bool OUT16, int MODE = 0, bool FULL = false>
+// TIN: element type of the task / base tensors (svdq_input.h), widened to fp32 by the loaders; float for the walk.
+template <int NTP, bool OUT16, int MODE = 0, bool FULL = false, typename TIN = float>
 __device__ __forceinline__ void bp_unit(
     float *X, typename OutT<OUT16>::type *OUT, int uidx, const SvdqParam *__restrict__ params,
     const SvdqUnit *__restrict__ units, const float *const *__restrict__ ptrs,
@@ -60,6 +61,7 @@ __device__ __forceinline__ void bp_unit(
     constexpr bool GATHER = (MODE & 1) != 0, SUB = (MODE & 2) != 0, WALK = (MODE & 4) != 0;
     static_assert(!(GATHER && WALK), "index lists and the mask walk are alternatives");
     static_assert(!(MODE != 0 && SVDQ_PREFETCH2), "gather / minus-base support the one-block-ahead pipeline only");
+    static_assert(!WALK || sizeof(TIN) == 4, "the mask walk reads fp32 tensors only");
     const int NT = FULL ? NTP : NT_arg;
     constexpr int PACK = (NTP <= 8) ? 2 : 1;
     constexpr int NB = (NTP + 15) / 16;
@@ -82,9 +84,9 @@ __device__ __forceinline__ void bp_unit(
     const int r = r_dev[p];
     const int nl = r - k;
 
-    gfloat *bp[NTP];
+    gin<TIN> *bp[NTP];
 #pragma unroll
-    for (int t = 0; t < NTP; ++t) bp[t] = (gfloat *)ptrs[(size_t)p * NT + (t < NT ? t : NT - 1)];
+    for (int t = 0; t < NTP; ++t) bp[t] = (gin<TIN> *)ptrs[(size_t)p * NT + (t < NT ? t : NT - 1)];
 
     const int c = lane & 15, g = lane >> 4;
 
@@ -143,28 +145,28 @@ __device__ __forceinline__ void bp_unit(
     f32x4 v0[NTP];
     gint *gidx = nullptr;
     i32x4 ixn = {-1, -1, -1, -1};  // indices of the block after the one whose data is in flight
-    gfloat *gbase = nullptr;
+    gin<TIN> *gbase = nullptr;
     f32x4 vb = zero4();  // base rows of the block whose fine-tuned rows sit in v
-    if constexpr (SUB) gbase = (gfloat *)aux2[p];
+    if constexpr (SUB) gbase = (gin<TIN> *)aux2[p];
     if constexpr (WALK) {
         // loads are issued by the walk loop below
     } else if constexpr (GATHER) {
         gidx = (gint *)aux[p];
         if (r_begin < r_end) {
             const i32x4 ix0 = load_idx(gidx, r_begin, D, lane);
-            load_block_gather<NTP>(v0, bp, ix0, r_begin + SVDQ_BLK_ROWS <= D);
-            if constexpr (SUB) vb = load_base_gather(gbase, ix0, r_begin + SVDQ_BLK_ROWS <= D);
+            load_block_gather<NTP, TIN>(v0, bp, ix0, r_begin + SVDQ_BLK_ROWS <= D);
+            if constexpr (SUB) vb = load_base_gather<TIN>(gbase, ix0, r_begin + SVDQ_BLK_ROWS <= D);
             if (r_begin + SVDQ_BLK_ROWS < r_end) ixn = load_idx(gidx, r_begin + SVDQ_BLK_ROWS, D, lane);
         }
     } else {
-        if (r_begin < r_end) load_block<NTP>(v0, bp, r_begin, D, lane);
+        if (r_begin < r_end) load_block<NTP, TIN>(v0, bp, r_begin, D, lane);
         if constexpr (SUB) {
-            if (r_begin < r_end) vb = load_base(gbase, r_begin, D, lane);
+            if (r_begin < r_end) vb = load_base<TIN>(gbase, r_begin, D, lane);
         }
     }
 #if SVDQ_PREFETCH2
     f32x4 v1[NTP];
-    if (r_begin + SVDQ_BLK_ROWS < r_end) load_block<NTP>(v1, bp, r_begin + SVDQ_BLK_ROWS, D, lane);
+    if (r_begin + SVDQ_BLK_ROWS < r_end) load_block<NTP, TIN>(v1, bp, r_begin + SVDQ_BLK_ROWS, D, lane);
 #endif
 
     // one block out of the strip: U tiles, fp16 staging, rounding-correction MFMAs, the two row-major stores
@@ -368,12 +370,12 @@ UNROLL_N(SVDQ_UNROLL_BP)
             wave_sync();
             if (rb + AHEAD * SVDQ_BLK_ROWS < r_end) {
                 if constexpr (GATHER) {
-                    load_block_gather<NTP>(v, bp, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
-                    if constexpr (SUB) vb = load_base_gather(gbase, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
+                    load_block_gather<NTP, TIN>(v, bp, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
+                    if constexpr (SUB) vb = load_base_gather<TIN>(gbase, ixn, rb + 2 * SVDQ_BLK_ROWS <= D);
                     if (rb + 2 * SVDQ_BLK_ROWS < r_end) ixn = load_idx(gidx, rb + 2 * SVDQ_BLK_ROWS, D, lane);
                 } else {
-                    load_block<NTP>(v, bp, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
-                    if constexpr (SUB) vb = load_base(gbase, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
+                    load_block<NTP, TIN>(v, bp, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
+                    if constexpr (SUB) vb = load_base<TIN>(gbase, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
                 }
             }
             compute(rb);
@@ -412,7 +414,7 @@ UNROLL_N(SVDQ_UNROLL_BP)
 }
 
 SVDQ_STAMP_DECL(svdq_stamps_project)
-template <int NTP, bool OUT16, int MODE, bool FULL>
+template <int NTP, bool OUT16, int MODE, bool FULL, typename TIN = float>
 __global__ __launch_bounds__(64) void k_basis_project(
     const SvdqParam *__restrict__ params, const SvdqUnit *__restrict__ units,
     const float *const *__restrict__ ptrs, const int64_t *__restrict__ rows_dev, int NT, int center,
@@ -424,7 +426,7 @@ __global__ __launch_bounds__(64) void k_basis_project(
     __shared__ __attribute__((aligned(16))) out_t OUT[SVDQ_BLK_ROWS * NTP + 16];  // +16: dump slot for idle lanes
     SVDQ_STAMP_BEGIN();
     const int uidx = unit0 + unit_of_block((int)blockIdx.x, (int)gridDim.x, reverse);
-    bp_unit<NTP, OUT16, MODE, FULL>(X, OUT, uidx, params, units, ptrs, rows_dev, NT, center, Wtab, k_dev, r_dev, basis,
+    bp_unit<NTP, OUT16, MODE, FULL, TIN>(X, OUT, uidx, params, units, ptrs, rows_dev, NT, center, Wtab, k_dev, r_dev, basis,
                                     meanbuf, cpart, aux, aux2, ustart);
     SVDQ_STAMP_END(svdq_stamps_project, uidx);
 }

@@ -125,7 +125,7 @@ int svdq_launch_gram_total(const svdq_plan *pl, const double *part2, double *out
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
 
-template <int THREADS, int NMAX>
+template <int THREADS, int NMAX, typename TIN>
 __global__ __launch_bounds__(THREADS) void k_eig(const SvdqParam *__restrict__ params,
                                                  const float *const *__restrict__ ptrs,
                                                  const int64_t *__restrict__ rows_dev, int NT, int center, float thr,
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(THREADS) void k_eig(const SvdqParam *__restrict__ p
         if (idx_ptrs) row0 = idx_ptrs[p][0];
         else if (ustart) row0 = ustart[params[p].unit_begin] & ((1ll << 62) - 1);
     }
-    eig_param<THREADS, NMAX>(lds, p, threadIdx.x, D, ptrs, NT, center, thr, max_rank, gram_part2, Wtab, c0_out, sigma_out,
+    eig_param<THREADS, NMAX, TIN>(lds, p, threadIdx.x, D, ptrs, NT, center, thr, max_rank, gram_part2, Wtab, c0_out, sigma_out,
                              k_out, r_out, energy_out, rows_out, row0, base_ptrs, refine_out, (double)resolve);
 }
 
@@ -253,14 +253,16 @@ int svdq_launch_eig(const svdq_plan *pl, const void *ptrs, const int64_t *rows_d
     int32_t *kk = reinterpret_cast<int32_t *>(small + L.k_off), *rr = reinterpret_cast<int32_t *>(small + L.r_off);
     float *en = reinterpret_cast<float *>(small + L.energy_off);
     int64_t *ro = reinterpret_cast<int64_t *>(small + L.rows_off);
-    if (pl->n_tasks <= 8)
-        hipLaunchKernelGGL((k_eig<64, 8>), dim3(nparams), dim3(64), 0, st, pl->d_params, pp, rows_dev, pl->n_tasks,
-                           pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank, gram_part2, W, c0, param0, sg,
-                           kk, rr, en, ro, ip, bpp, only, refine_out, resolve, ustart);
-    else
-        hipLaunchKernelGGL((k_eig<256, 32>), dim3(nparams), dim3(256), 0, st, pl->d_params, pp, rows_dev, pl->n_tasks,
-                           pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank, gram_part2, W, c0, param0, sg,
-                           kk, rr, en, ro, ip, bpp, only, refine_out, resolve, ustart);
+    // the input type only changes how k_eig reads row 0 of every task (the completion column)
+    SVDQ_DISPATCH_INPUT(pl, TIN,
+        if (pl->n_tasks <= 8)
+            hipLaunchKernelGGL((k_eig<64, 8, TIN>), dim3(nparams), dim3(64), 0, st, pl->d_params, pp, rows_dev, pl->n_tasks,
+                               pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank, gram_part2, W, c0, param0, sg,
+                               kk, rr, en, ro, ip, bpp, only, refine_out, resolve, ustart);
+        else
+            hipLaunchKernelGGL((k_eig<256, 32, TIN>), dim3(nparams), dim3(256), 0, st, pl->d_params, pp, rows_dev,
+                               pl->n_tasks, pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank, gram_part2, W, c0,
+                               param0, sg, kk, rr, en, ro, ip, bpp, only, refine_out, resolve, ustart));
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
 

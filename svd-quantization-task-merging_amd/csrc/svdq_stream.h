@@ -50,6 +50,7 @@
 #endif
 
 #include "svdq_common.h"
+#include "svdq_input.h"
 #include <hip/hip_fp16.h>
 
 #define XS SVDQ_XS
@@ -132,30 +133,25 @@ __device__ __forceinline__ f32x4 zero4() {
 typedef const __attribute__((address_space(1))) float gfloat;
 typedef const __attribute__((address_space(1))) f32x4 gf32x4;
 
-// Issue the 16-B loads of one 256-row block: lane l takes rows rb+4l..rb+4l+3 of every task.
+// Issue the loads of one 256-row block: lane l takes rows rb+4l..rb+4l+3 of every task (16 B per lane and task for
+// fp32 inputs, 8 B for half inputs -- the same lanes hold the same rows for every input type).
 // Full blocks take the unconditional path (no per-load branch, all loads in flight together);
 // only the last block of a parameter takes the guarded one.
-template <int NTP>
-__device__ __forceinline__ void load_block(f32x4 (&v)[NTP], gfloat *(&bp)[NTP], int64_t rb,
+template <int NTP, typename TIN = float>
+__device__ __forceinline__ void load_block(f32x4 (&v)[NTP], gin<TIN> *(&bp)[NTP], int64_t rb,
                                            int64_t D, int lane) {
     const int64_t r = rb + 4 * lane;
     if (rb + SVDQ_BLK_ROWS <= D) {
 #pragma unroll
-        for (int t = 0; t < NTP; ++t) {
-#if SVDQ_NT_LOADS
-            v[t] = __builtin_nontemporal_load(reinterpret_cast<gf32x4 *>(bp[t] + r));
-#else
-            v[t] = *reinterpret_cast<gf32x4 *>(bp[t] + r);
-#endif
-        }
+        for (int t = 0; t < NTP; ++t) v[t] = in_load4<TIN, SVDQ_NT_LOADS != 0>(bp[t] + r);
     } else {
 #pragma unroll
         for (int t = 0; t < NTP; ++t) {
             f32x4 o = zero4();
-            if (r < D) o.x = bp[t][r];
-            if (r + 1 < D) o.y = bp[t][r + 1];
-            if (r + 2 < D) o.z = bp[t][r + 2];
-            if (r + 3 < D) o.w = bp[t][r + 3];
+            if (r < D) o.x = in_load1<TIN>(bp[t] + r);
+            if (r + 1 < D) o.y = in_load1<TIN>(bp[t] + (r + 1));
+            if (r + 2 < D) o.z = in_load1<TIN>(bp[t] + (r + 2));
+            if (r + 3 < D) o.w = in_load1<TIN>(bp[t] + (r + 3));
             v[t] = o;
         }
     }
@@ -191,54 +187,56 @@ __device__ __forceinline__ i32x4 load_idx(gint *idx, int64_t rb, int64_t D, int 
 
 // "Minus base" mode (svdq_compress_from_base): the task tensors are FINE-TUNED weights and the delta
 // finetuned - base is formed in registers, so the task vectors are never written to or read back from HBM.
-__device__ __forceinline__ f32x4 load_base(gfloat *b, int64_t rb, int64_t D, int lane) {
+template <typename TIN = float>
+__device__ __forceinline__ f32x4 load_base(gin<TIN> *b, int64_t rb, int64_t D, int lane) {
     const int64_t r = rb + 4 * lane;
-    if (rb + SVDQ_BLK_ROWS <= D) return *reinterpret_cast<gf32x4 *>(b + r);
+    if (rb + SVDQ_BLK_ROWS <= D) return in_load4<TIN>(b + r);
     f32x4 o = zero4();
-    if (r < D) o.x = b[r];
-    if (r + 1 < D) o.y = b[r + 1];
-    if (r + 2 < D) o.z = b[r + 2];
-    if (r + 3 < D) o.w = b[r + 3];
+    if (r < D) o.x = in_load1<TIN>(b + r);
+    if (r + 1 < D) o.y = in_load1<TIN>(b + (r + 1));
+    if (r + 2 < D) o.z = in_load1<TIN>(b + (r + 2));
+    if (r + 3 < D) o.w = in_load1<TIN>(b + (r + 3));
     return o;
 }
 
 // base rows of a gathered block (minus-base mode combined with gather mode): same indices as the task rows
-__device__ __forceinline__ f32x4 load_base_gather(gfloat *b, const i32x4 &ix, bool full) {
+template <typename TIN = float>
+__device__ __forceinline__ f32x4 load_base_gather(gin<TIN> *b, const i32x4 &ix, bool full) {
     f32x4 o = zero4();
     if (full) {
-        o.x = b[ix.x];
-        o.y = b[ix.y];
-        o.z = b[ix.z];
-        o.w = b[ix.w];
+        o.x = in_load1<TIN>(b + ix.x);
+        o.y = in_load1<TIN>(b + ix.y);
+        o.z = in_load1<TIN>(b + ix.z);
+        o.w = in_load1<TIN>(b + ix.w);
     } else {
-        if (ix.x >= 0) o.x = b[ix.x];
-        if (ix.y >= 0) o.y = b[ix.y];
-        if (ix.z >= 0) o.z = b[ix.z];
-        if (ix.w >= 0) o.w = b[ix.w];
+        if (ix.x >= 0) o.x = in_load1<TIN>(b + ix.x);
+        if (ix.y >= 0) o.y = in_load1<TIN>(b + ix.y);
+        if (ix.z >= 0) o.z = in_load1<TIN>(b + ix.z);
+        if (ix.w >= 0) o.w = in_load1<TIN>(b + ix.w);
     }
     return o;
 }
 
-template <int NTP>
-__device__ __forceinline__ void load_block_gather(f32x4 (&v)[NTP], gfloat *(&bp)[NTP], const i32x4 &ix, bool full) {
+template <int NTP, typename TIN = float>
+__device__ __forceinline__ void load_block_gather(f32x4 (&v)[NTP], gin<TIN> *(&bp)[NTP], const i32x4 &ix, bool full) {
     if (full) {
 #pragma unroll
         for (int t = 0; t < NTP; ++t) {
             f32x4 o;
-            o.x = bp[t][ix.x];
-            o.y = bp[t][ix.y];
-            o.z = bp[t][ix.z];
-            o.w = bp[t][ix.w];
+            o.x = in_load1<TIN>(bp[t] + ix.x);
+            o.y = in_load1<TIN>(bp[t] + ix.y);
+            o.z = in_load1<TIN>(bp[t] + ix.z);
+            o.w = in_load1<TIN>(bp[t] + ix.w);
             v[t] = o;
         }
     } else {
 #pragma unroll
         for (int t = 0; t < NTP; ++t) {
             f32x4 o = zero4();
-            if (ix.x >= 0) o.x = bp[t][ix.x];
-            if (ix.y >= 0) o.y = bp[t][ix.y];
-            if (ix.z >= 0) o.z = bp[t][ix.z];
-            if (ix.w >= 0) o.w = bp[t][ix.w];
+            if (ix.x >= 0) o.x = in_load1<TIN>(bp[t] + ix.x);
+            if (ix.y >= 0) o.y = in_load1<TIN>(bp[t] + ix.y);
+            if (ix.z >= 0) o.z = in_load1<TIN>(bp[t] + ix.z);
+            if (ix.w >= 0) o.w = in_load1<TIN>(bp[t] + ix.w);
             v[t] = o;
         }
     }

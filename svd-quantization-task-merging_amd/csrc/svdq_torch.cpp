@@ -28,6 +28,9 @@
 //   ingest(Tensor base, Tensor[] finetuned) -> Tensor[]
 //   task_gram(Tensor[] deltas, int n_tasks) -> Tensor
 //   plan_cache_size() -> int                                  plans kept by compress (for tests)
+// compress, compress_gather, compress_from_base, diagnostics (unmasked) and task_gram read fp16 / bf16 task tensors as
+// they are when every task tensor (and every base tensor) has that one dtype (svdq_plan_set_input_type: the outputs are
+// byte-identical to those of the same call on the tensors converted to fp32); any other mix is converted to fp32 first.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -56,13 +59,35 @@ void *stream_of(const c10::Device &dev) { return (void *)c10::hip::getCurrentHIP
 
 void sync(const c10::Device &dev) { c10::hip::getCurrentHIPStream(dev.index()).synchronize(); }
 
-// fp32, flat, contiguous, 16-byte aligned: the only input contract of the ABI
+// fp32, flat, contiguous, 16-byte aligned: the input contract of an fp32-input plan (SVDQ_INPUT_F32, the default)
 at::Tensor prep(const at::Tensor &t) {
     TORCH_CHECK(t.is_cuda(), "svdq operators take device tensors");
     at::Tensor v = t.detach();
     if (v.scalar_type() != at::kFloat) v = v.to(at::kFloat);
     v = v.contiguous().view({-1});
     if (reinterpret_cast<uintptr_t>(v.data_ptr()) & 15) v = v.clone();
+    return v;
+}
+
+// The ABI input type (svdq_plan_set_input_type) of a set of task tensors (and base tensors): fp16 or bf16 when every one
+// of them has that dtype -- the kernels then read them as they are -- otherwise fp32 (every tensor goes through prep).
+int32_t input_type_of(at::TensorList a, at::TensorList b = {}) {
+    if (a.empty()) return SVDQ_INPUT_F32;
+    const at::ScalarType s = a[0].scalar_type();
+    if (s != at::kHalf && s != at::kBFloat16) return SVDQ_INPUT_F32;
+    for (const at::Tensor &t : a)
+        if (t.scalar_type() != s) return SVDQ_INPUT_F32;
+    for (const at::Tensor &t : b)
+        if (t.scalar_type() != s) return SVDQ_INPUT_F32;
+    return s == at::kHalf ? SVDQ_INPUT_F16 : SVDQ_INPUT_BF16;
+}
+
+// the input contract of a half-input plan: the tensor's own dtype, flat, contiguous, 8-byte aligned (no fp32 copy)
+at::Tensor prep_in(const at::Tensor &t, int32_t in_type) {
+    if (in_type == SVDQ_INPUT_F32) return prep(t);
+    TORCH_CHECK(t.is_cuda(), "svdq operators take device tensors");
+    at::Tensor v = t.detach().contiguous().view({-1});
+    if (reinterpret_cast<uintptr_t>(v.data_ptr()) & 7) v = v.clone();
     return v;
 }
 
@@ -220,14 +245,15 @@ std::vector<int64_t> rows_of(const std::vector<at::Tensor> &vecs, int64_t n_task
     return rows;
 }
 
-std::vector<at::Tensor> prep_list(at::TensorList ts, int64_t n_tasks, const char *what) {
+std::vector<at::Tensor> prep_list(at::TensorList ts, int64_t n_tasks, const char *what,
+                                  int32_t in_type = SVDQ_INPUT_F32) {
     TORCH_CHECK_VALUE(n_tasks >= 1 && !ts.empty() && (int64_t)ts.size() % n_tasks == 0, what,
                       ": deltas must hold n_tasks tensors per parameter (parameter-major)");
     std::vector<at::Tensor> v;
     v.reserve(ts.size());
     for (const at::Tensor &t : ts) {
         TORCH_CHECK_VALUE(t.device() == ts[0].device(), what, ": all tensors must live on one device");
-        v.push_back(prep(t));
+        v.push_back(prep_in(t, in_type));
     }
     return v;
 }
@@ -242,9 +268,11 @@ struct PlanKey {
     bool center, fp16;
     int dev;
     void *stream;
+    int32_t in_type = SVDQ_INPUT_F32;
     bool operator==(const PlanKey &o) const {
         return rows == o.rows && n_tasks == o.n_tasks && max_rank == o.max_rank && bits == o.bits && stages == o.stages &&
-               energy == o.energy && center == o.center && fp16 == o.fp16 && dev == o.dev && stream == o.stream;
+               energy == o.energy && center == o.center && fp16 == o.fp16 && dev == o.dev && stream == o.stream &&
+               in_type == o.in_type;
     }
 };
 constexpr size_t kPlanCacheMax = 8;
@@ -271,6 +299,7 @@ std::unique_ptr<Plan> acquire_plan(const PlanKey &key, const c10::Device &dev) {
         cfg.low_bits = (int32_t)key.bits;
         cfg.rtvq_stages = (int32_t)key.stages;
         plan = make_plan(key.rows, key.n_tasks, cfg, dev);
+        check(svdq_plan_set_input_type(plan->h, key.in_type), "svdq_plan_set_input_type");
         while (g_cache.size() >= kPlanCacheMax) {
             sync(g_cache.front().second->dev);                        // its tables may still be in use
             g_cache.pop_front();
@@ -300,11 +329,13 @@ Outputs alloc_outputs(const Plan &plan, bool center, const c10::Device &dev) {
 std::tuple<at::Tensor, at::Tensor, at::Tensor> compress(at::TensorList deltas, int64_t n_tasks, double energy,
                                                         int64_t max_rank, bool center, bool fp16, int64_t bits,
                                                         int64_t stages) {
-    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "compress");
+    const int32_t in_type = input_type_of(deltas);
+    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "compress", in_type);
     const c10::Device dev = vecs[0].device();
     c10::DeviceGuard guard(dev);
     void *stream = stream_of(dev);
-    PlanKey key{rows_of(vecs, n_tasks), n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream};
+    PlanKey key{rows_of(vecs, n_tasks), n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream,
+                in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
     std::unique_ptr<Plan> plan = acquire_plan(key, dev);
     Outputs o = alloc_outputs(*plan, center, dev);
@@ -320,7 +351,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> compress(at::TensorList deltas, i
 std::tuple<at::Tensor, at::Tensor, at::Tensor> compress_from_base(at::TensorList finetuned, at::TensorList base,
                                                                   int64_t n_tasks, double energy, int64_t max_rank,
                                                                   bool center, bool fp16, int64_t bits, int64_t stages) {
-    std::vector<at::Tensor> vecs = prep_list(finetuned, n_tasks, "compress_from_base");
+    const int32_t in_type = input_type_of(finetuned, base);
+    std::vector<at::Tensor> vecs = prep_list(finetuned, n_tasks, "compress_from_base", in_type);
     const c10::Device dev = vecs[0].device();
     c10::DeviceGuard guard(dev);
     void *stream = stream_of(dev);
@@ -330,9 +362,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> compress_from_base(at::TensorList
     for (size_t p = 0; p < rows.size(); ++p) {
         TORCH_CHECK_VALUE(base[p].device() == dev, "compress_from_base: all tensors must live on one device");
         TORCH_CHECK_VALUE(base[p].numel() == rows[p], "parameter ", p, ": base and fine-tuned tensors differ in size");
-        bs.push_back(prep(base[p]));
+        bs.push_back(prep_in(base[p], in_type));
     }
-    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream};
+    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
     std::unique_ptr<Plan> plan = acquire_plan(key, dev);
     Outputs o = alloc_outputs(*plan, center, dev);
@@ -353,7 +385,9 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_with_masks(a
                                                                                int64_t max_rank, bool center, bool fp16,
                                                                                int64_t bits, int64_t stages, bool walk,
                                                                                const char *what) {
-    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, what);
+    // half inputs are read as they are through the index lists; the walk reads fp32 only
+    const int32_t in_type = walk ? SVDQ_INPUT_F32 : input_type_of(deltas);
+    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, what, in_type);
     const c10::Device dev = vecs[0].device();
     c10::DeviceGuard guard(dev);
     void *stream = stream_of(dev);
@@ -379,7 +413,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_with_masks(a
     at::Tensor work = bytes_on(dev, svdq_maskset_work_bytes(ms));
     at::Tensor ct = at::zeros({P}, at::TensorOptions().dtype(at::kLong).device(dev));
     at::Tensor mtab = table_of(mb, dev);
-    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream};
+    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
     std::unique_ptr<Plan> plan = acquire_plan(key, dev);
     Outputs o = alloc_outputs(*plan, center, dev);
@@ -581,7 +615,9 @@ std::vector<at::Tensor> merge_masked(const at::Tensor &small, const at::Tensor &
 at::Tensor diagnostics(at::TensorList deltas, at::TensorList masks, const at::Tensor &small, const at::Tensor &basis,
                        const at::Tensor &mean, int64_t n_tasks, double energy, int64_t max_rank, bool center, bool fp16,
                        int64_t bits, int64_t stages, bool add_mean) {
-    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "diagnostics");
+    // half inputs are read as they are by the plain form; the masked (walk) form reads fp32 only
+    const int32_t in_type = masks.empty() ? input_type_of(deltas) : SVDQ_INPUT_F32;
+    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "diagnostics", in_type);
     const c10::Device dev = vecs[0].device();
     c10::DeviceGuard guard(dev);
     void *stream = stream_of(dev);
@@ -600,7 +636,7 @@ at::Tensor diagnostics(at::TensorList deltas, at::TensorList masks, const at::Te
             }
         }
     } ms_guard{ms, dev};
-    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream};
+    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
     std::unique_ptr<Plan> plan = acquire_plan(key, dev);
     check_artifacts("diagnostics", small, basis, mean, plan->sizes, center, dev);
@@ -664,7 +700,8 @@ std::vector<at::Tensor> ingest(const at::Tensor &base, at::TensorList finetuned)
 }
 
 at::Tensor task_gram(at::TensorList deltas, int64_t n_tasks) {
-    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "task_gram");
+    const int32_t in_type = input_type_of(deltas);
+    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "task_gram", in_type);
     const c10::Device dev = vecs[0].device();
     c10::DeviceGuard guard(dev);
     svdq_config cfg{};
@@ -673,6 +710,7 @@ at::Tensor task_gram(at::TensorList deltas, int64_t n_tasks) {
     cfg.rtvq_stages = 2;
     cfg.fp16 = 1;
     auto plan = make_plan(rows_of(vecs, n_tasks), n_tasks, cfg, dev);
+    check(svdq_plan_set_input_type(plan->h, in_type), "svdq_plan_set_input_type");
     at::Tensor table = table_of(vecs, dev);
     at::Tensor G = at::empty({n_tasks, n_tasks}, at::TensorOptions().dtype(at::kDouble).device(dev));
     check(svdq_task_gram(plan->h, table.data_ptr(), nullptr, plan->workspace.data_ptr(), G.data_ptr<double>(),

@@ -136,6 +136,8 @@ def _batched_errors(task_vectors, compressed_all, bases, masks) -> Dict[str, Dic
         if mode == "plain":
             if mask is not None:
                 continue
+        elif getattr(batch.plan, "input_dtype", torch.float32) is not torch.float32:
+            continue      # svdq_diagnostics_masked reads fp32 task tensors only: half masked batches go per parameter
         elif (mask is None or batch.unit_start is None
               or getattr(batch, "mask_ident", {}).get(name) != _mask_identity(mask)
               or any(t in task_vectors and name in task_vectors[t] and mask.shape != task_vectors[t][name].shape

@@ -10,7 +10,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .pipeline import (BatchResult, CompressPlan, basis_dict, prepare_vector, resolve_device, task_artifact)
+from .pipeline import (BatchResult, CompressPlan, basis_dict, native_input_dtype, prepare_input, prepare_vector,
+                       resolve_device, task_artifact)
 from . import mask_loader as ml
 
 
@@ -50,8 +51,10 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
     # name -> bits on the config; the reference itself has one width per run (compress.py:180-183)
     bits_by_param = getattr(config, "svd_low_bits_by_param", None)
 
-    # group regions by the number of tasks that have the parameter (one plan per N)
-    groups: Dict[Tuple[int, str], List[dict]] = {}   # (tasks present, "plain" | "gather" | "walk") -> regions of one plan
+    # group regions by the number of tasks that have the parameter, the way to the rows and the input dtype (one plan
+    # each).  A parameter whose task tensors (and base tensor) all have one half dtype is read as it is (no fp32 copy;
+    # byte-identical outputs); any mix of dtypes, and every "walk" region, gets fp32 copies (prepare_vector).
+    groups: Dict[Tuple[int, str, torch.dtype], List[dict]] = {}   # (tasks present, "plain" | "gather" | "walk", dtype)
     keep = []
     with torch.cuda.device(dev):
         masked_by_n: Dict[int, List[tuple]] = {}
@@ -65,14 +68,18 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
             if mask is not None and mask.shape == deltas[0].shape and mask.numel() > 0:
                 masked_by_n.setdefault(len(present), []).append((name, present, deltas, mask))
             else:
-                vs = [d if d.dim() == 1 else prepare_vector(d, dev) for d in deltas] if _resident(deltas, dev) \
-                    else [prepare_vector(d, dev) for d in deltas]
+                idt = native_input_dtype(deltas + ([base_state[name]] if base_state is not None else []))
+                if idt is not torch.float32:
+                    vs = [prepare_input(d, dev, idt) for d in deltas]
+                else:
+                    vs = [d if d.dim() == 1 else prepare_vector(d, dev) for d in deltas] if _resident(deltas, dev) \
+                        else [prepare_vector(d, dev) for d in deltas]
                 if vs[0].numel() == 0:
                     continue
-                groups.setdefault((len(present), "plain"), []).append(
+                groups.setdefault((len(present), "plain", idt), []).append(
                     {"name": name, "region": "masked", "tasks": present, "vectors": vs, "count": None,
                      "upper": vs[0].numel(), "min": 0,
-                     "base": prepare_vector(base_state[name], dev) if base_state is not None else None})
+                     "base": prepare_input(base_state[name], dev, idt) if base_state is not None else None})
         # Masked parameters never get compacted copies of their deltas.  One count + scan per group (mask.sum() stays
         # on the device and becomes rows_dev); then, per region, one of two ways to reach the selected rows:
         #   walk   (N <= 16 and the region holds at least half of the elements): both passes walk the source rows with
@@ -92,28 +99,40 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                 it_, if_, _, _ = ms.indices(mask_list, want_false=include_noise and not walk_noise)
             keep.append((ms, it_, if_))
             for q, (name, present, deltas, mask_q) in enumerate(items):
-                vs = [prepare_vector(d, dev) for d in deltas]
                 ident = (mask_q.data_ptr(), mask_q.numel(), str(mask_q.device), mask_q.dtype)
-                bvec = prepare_vector(base_state[name], dev) if base_state is not None else None
+                base_t = base_state[name] if base_state is not None else None
+                native = native_input_dtype(deltas + ([base_t] if base_t is not None else []))
+                prepared = {}
+
+                def inputs(walk, deltas=deltas, base_t=base_t, native=native, prepared=prepared):
+                    # the walk reads fp32 only; the index lists read fp16 / bf16 as they are
+                    idt = torch.float32 if walk else native
+                    if idt not in prepared:
+                        prepared[idt] = ([prepare_input(d, dev, idt) for d in deltas],
+                                         prepare_input(base_t, dev, idt) if base_t is not None else None)
+                    return (idt,) + prepared[idt]
+
+                idt, vs, bvec = inputs(walk_sig)
                 e = {"name": name, "region": "masked", "tasks": present, "vectors": vs, "count": ct[q:q + 1],
                      "upper": vs[0].numel(), "min": min_size, "base": bvec}
                 e.update(ms=ms, q=q, inv=False, mask_ident=ident)
                 if not walk_sig:
                     e["index"] = it_[q]
-                groups.setdefault((n_present, "walk" if walk_sig else "gather"), []).append(e)
+                groups.setdefault((n_present, "walk" if walk_sig else "gather", idt), []).append(e)
                 if include_noise:
+                    idt, vs, bvec = inputs(walk_noise)
                     e = {"name": name, "region": "noise", "tasks": present, "vectors": vs, "count": cf[q:q + 1],
                          "upper": vs[0].numel(), "min": 1, "gate": ct[q:q + 1], "base": bvec}
                     e.update(ms=ms, q=q, inv=True, mask_ident=ident)
                     if not walk_noise:
                         e["index"] = if_[q]
-                    groups.setdefault((n_present, "walk" if walk_noise else "gather"), []).append(e)
+                    groups.setdefault((n_present, "walk" if walk_noise else "gather", idt), []).append(e)
         order = {n: i for i, n in enumerate(names)}
         for lst in groups.values():
             lst.sort(key=lambda e: (order[e["name"]], e["region"] != "masked"))
 
         bases: Dict[str, Dict] = {}
-        for (n_tasks, mode), entries in groups.items():
+        for (n_tasks, mode, idt), entries in groups.items():
             entries = [e for e in entries if e["upper"] > 0]
             if not entries:
                 continue
@@ -122,7 +141,7 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                                 center=config.svd_center, fp16=config.svd_fp16,
                                 low_bits=([int(bits_by_param(e["name"])) for e in entries] if bits_by_param
                                           else config.svd_low_bits),
-                                rtvq_stages=config.svd_rtvq_stages, device=dev)
+                                rtvq_stages=config.svd_rtvq_stages, device=dev, input_dtype=idt)
             rows_dev = None
             if any(e["count"] is not None for e in entries):
                 # rows actually processed = mask.sum() (device), or 0 when below svd_min_mask_size

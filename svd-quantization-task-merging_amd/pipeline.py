@@ -41,8 +41,9 @@ def wants_cpu(device) -> bool:
 
 
 def prepare_vector(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
-    """fp32, contiguous, flat, on ``dev``, 16-byte aligned (the only input contract of the ABI).  A tensor that
-    already is all of that comes back as it is (a model's worth of task tensors makes this the hot host call)."""
+    """fp32, contiguous, flat, on ``dev``, 16-byte aligned (the input contract of an fp32-input plan, the default).  A
+    tensor that already is all of that comes back as it is (a model's worth of task tensors makes this the hot host
+    call)."""
     if (t.dtype is torch.float32 and t.dim() == 1 and t.device == dev and t.is_contiguous()
             and not t.requires_grad and t.data_ptr() % 16 == 0):
         return t
@@ -51,6 +52,42 @@ def prepare_vector(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
         v = v.to(device=dev, dtype=torch.float32)
     v = v.contiguous().view(-1)
     if v.data_ptr() % 16 != 0:
+        v = v.clone()
+    return v
+
+
+# task-tensor dtypes the streaming kernels read as they are (svdq_plan_set_input_type)
+INPUT_TYPES = {torch.float32: nat.SVDQ_INPUT_F32, torch.float16: nat.SVDQ_INPUT_F16,
+               torch.bfloat16: nat.SVDQ_INPUT_BF16}
+
+
+def native_input_dtype(tensors) -> torch.dtype:
+    """The input dtype of a plan over ``tensors`` (the task tensors of a plan group, base tensors included): fp16 or
+    bf16 when every one of them has that dtype -- the kernels then read them without an fp32 copy, with outputs
+    byte-identical to those of the fp32 copies -- otherwise float32 (every tensor goes through ``prepare_vector``)."""
+    dt = None
+    for t in tensors:
+        if t is None:
+            continue
+        if dt is None:
+            dt = t.dtype
+        elif t.dtype != dt:
+            return torch.float32
+    return dt if dt in (torch.float16, torch.bfloat16) else torch.float32
+
+
+def prepare_input(t: torch.Tensor, dev: torch.device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """A task / base tensor for a plan whose input dtype is ``dtype``.  float32: ``prepare_vector``.  fp16 / bf16: the
+    tensor in its own dtype, flat, contiguous, on ``dev``, 8-byte aligned -- cloned only when its storage is not."""
+    if dtype is torch.float32:
+        return prepare_vector(t, dev)
+    if t.dtype is not dtype:
+        raise ValueError(f"expected a {dtype} tensor, got {t.dtype}")
+    v = t.detach()
+    if v.device != dev:
+        v = v.to(dev)
+    v = v.contiguous().view(-1)
+    if v.data_ptr() % 8 != 0:
         v = v.clone()
     return v
 
@@ -85,7 +122,9 @@ class CompressPlan:
     def __init__(self, rows: Sequence[int], n_tasks: int, *, energy_threshold: float = 0.90,
                  max_rank: Optional[int] = None, center: bool = True, fp16: bool = True,
                  low_bits: int = 4, rtvq_stages: int = 2, device="cuda", unit_rows: int = 0, flags: int = 0,
-                 gram_only: bool = False):
+                 gram_only: bool = False, input_dtype: torch.dtype = torch.float32):
+        if input_dtype not in INPUT_TYPES:
+            raise ValueError(f"input_dtype must be one of {list(INPUT_TYPES)}, got {input_dtype}")
         self.lib = nat.lib()
         self.device = resolve_device(device)
         self.rows = [int(x) for x in rows]
@@ -112,6 +151,10 @@ class CompressPlan:
             arr = (c_int32 * self.P)(*self.bits_list)
             with torch.cuda.device(self.device):
                 nat.check(self.lib.svdq_plan_set_low_bits(self._h, arr), "svdq_plan_set_low_bits")
+        # task / fine-tuned / base tensors in this dtype are read as they are (fp16 / bf16: no fp32 copy)
+        self.input_dtype = input_dtype
+        if input_dtype is not torch.float32:
+            nat.check(self.lib.svdq_plan_set_input_type(self._h, INPUT_TYPES[input_dtype]), "svdq_plan_set_input_type")
         self.sizes = nat.SvdqSizes()
         nat.check(self.lib.svdq_plan_sizes(self._h, byref(self.sizes)), "svdq_plan_sizes")
         self.layout = nat.SvdqSmallLayout()
@@ -169,7 +212,8 @@ class CompressPlan:
         """vectors[p][t] -> device int64 tensor [P*N] of data pointers (parameter-major)."""
         assert len(vectors) == self.P
         ptrs = []
-        f32, dev, N, rows = torch.float32, self.device, self.N, self.rows
+        f32, dev, N, rows = self.input_dtype, self.device, self.N, self.rows
+        align = 15 if f32 is torch.float32 else 7
         for p, vs in enumerate(vectors):
             if len(vs) != N:
                 raise ValueError(f"parameter {p}: expected {N} task vectors, got {len(vs)}")
@@ -177,9 +221,9 @@ class CompressPlan:
             for v in vs:
                 a = v.data_ptr()
                 if v.dtype is not f32 or v.device != dev or not v.is_contiguous():
-                    raise ValueError("task vectors must be contiguous fp32 tensors on the plan's device")
-                if a & 15:
-                    raise ValueError("task vector base address must be 16-byte aligned")
+                    raise ValueError(f"task vectors must be contiguous {f32} tensors on the plan's device")
+                if a & align:
+                    raise ValueError(f"task vector base address must be {align + 1}-byte aligned")
                 if v.numel() < need:
                     raise ValueError(f"parameter {p}: vector has {v.numel()} elements, plan says {need}")
                 ptrs.append(a)
@@ -615,11 +659,13 @@ def compress_batch(vectors: List[List[torch.Tensor]], *, energy_threshold: float
                    center: bool, fp16: bool, low_bits: int, rtvq_stages: int, device,
                    rows_dev: Optional[torch.Tensor] = None, rows_upper: Optional[List[int]] = None,
                    unit_rows: int = 0) -> Tuple[CompressPlan, SmallArtifacts]:
-    """Run the four stages on vectors[p][t] (flat fp32 device tensors). Returns (plan, small)."""
+    """Run the four stages on vectors[p][t] (flat device tensors: fp32, or all fp16 / all bf16 -- read as they are,
+    see ``native_input_dtype``). Returns (plan, small)."""
     dev = resolve_device(device)
     rows = rows_upper if rows_upper is not None else [int(vs[0].numel()) for vs in vectors]
     plan = CompressPlan(rows, len(vectors[0]), energy_threshold=energy_threshold, max_rank=max_rank, center=center,
-                        fp16=fp16, low_bits=low_bits, rtvq_stages=rtvq_stages, device=dev, unit_rows=unit_rows)
+                        fp16=fp16, low_bits=low_bits, rtvq_stages=rtvq_stages, device=dev, unit_rows=unit_rows,
+                        input_dtype=native_input_dtype(v for vs in vectors for v in vs))
     with torch.cuda.device(dev):
         table = plan.pointer_table(vectors)
         plan.run(table, rows_dev)
