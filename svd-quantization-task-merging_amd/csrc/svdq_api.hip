@@ -266,10 +266,48 @@ static void unit_range(const svdq_plan *pl, int32_t param0, int32_t nparams, int
     *nu = b.unit_begin + b.unit_count - a.unit_begin;
 }
 
-static int gram_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace, int32_t param0,
-                      int32_t nparams, const void *idx, void *stream, const void *base = nullptr,
-                      const int64_t *ustart = nullptr) {
-    if (!pl || !ptrs || !workspace) {
+int svdq_launch_status(bool launched, const char *kernel) {
+    if (!launched) {
+        svdq_set_error("%s: no kernel variant for this plan and input", kernel);
+        return SVDQ_EUNSUPPORTED;
+    }
+    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
+}
+
+// The rules for what the streaming passes can read, in one place.  Every entry point that takes task tensors calls
+// this once, before it enqueues anything; the launchers below rely on it.  mode: the MODE (SvdqInput::mode) that entry
+// point `who` is for -- a required table left NULL shows as another mode.
+static int svdq_check_input(const svdq_plan *pl, const SvdqInput &in, int mode, const char *who) {
+    if (!pl || !in.ptrs || in.mode() != mode || ((mode & 4) && !in.mask) || ((mode & 5) && !in.rows_dev)) {
+        svdq_set_error("%s: null argument (the plan, the tensor table and, as the entry point takes them, base_ptrs, "
+                       "index_ptrs or mask_ptrs and unit_start with rows_dev are required)", who);
+        return SVDQ_EINVAL;
+    }
+    if (mode & 4) {   // the walk is instantiated for fp32 tensors, and straight from checkpoints for N <= 16
+        if (int rc = svdq_require_f32_input(pl, who)) return rc;
+        if ((mode & 2) && pl->ntp > 16) {
+            svdq_set_error("%s: the mask walk straight from checkpoints covers N <= 16 tasks (got %d): use the index "
+                           "lists (svdq_compress_gather_from_base)", who, pl->n_tasks);
+            return SVDQ_EUNSUPPORTED;
+        }
+    }
+    if (pl->ntp < 4 || pl->ntp > 32 || pl->ntp % 4 != 0) {
+        svdq_set_error("%s: unsupported padded task count %d", who, pl->ntp);
+        return SVDQ_EUNSUPPORTED;
+    }
+    return SVDQ_OK;
+}
+
+static SvdqInput plain_input(const void *ptrs, const int64_t *rows_dev) {
+    SvdqInput in = {};
+    in.ptrs = ptrs;
+    in.rows_dev = rows_dev;
+    return in;
+}
+
+static int gram_range(const svdq_plan *pl, const SvdqInput &in, void *workspace, int32_t param0, int32_t nparams,
+                      void *stream) {
+    if (!workspace) {
         svdq_set_error("null argument");
         return SVDQ_EINVAL;
     }
@@ -277,37 +315,38 @@ static int gram_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows
     int u0, nu;
     unit_range(pl, param0, nparams, &u0, &nu);
     // N <= 16: exact products on the fp64 MFMA (pass 1 stays HBM-bound); N > 16: fp32 products first, the fp64 pass only
-    // for the parameters the eigen-stage flags (eig_range).  cfg.reserved bit 1 keeps fp32 products throughout (A/B).
-    const int f64 = (pl->ntp <= 16 && !(pl->cfg.reserved & 2)) ? 1 : 0;
-    return svdq_launch_gram(pl, ptrs, rows_dev, reinterpret_cast<double *>(ws(workspace, pl->ws_gram_off)), u0, nu,
-                            pl->cfg.center, idx, base, f64, nullptr, (hipStream_t)stream, ustart);
+    // for the parameters the eigen-stage flags (eig_range).  SVDQ_SW_GRAM_F32 keeps fp32 products throughout (A/B).
+    const int f64 = (pl->ntp <= 16 && !(pl->cfg.reserved & SVDQ_SW_GRAM_F32)) ? 1 : 0;
+    return svdq_launch_gram(pl, in, reinterpret_cast<double *>(ws(workspace, pl->ws_gram_off)), u0, nu, pl->cfg.center,
+                            f64, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int svdq_gram_center_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace,
                                       int32_t param0, int32_t nparams, void *stream) {
-    return gram_range(pl, ptrs, rows_dev, workspace, param0, nparams, nullptr, stream);
+    const SvdqInput in = plain_input(ptrs, rows_dev);
+    if (int rc = svdq_check_input(pl, in, 0, "svdq_gram_center_range")) return rc;
+    return gram_range(pl, in, workspace, param0, nparams, stream);
 }
 
 extern "C" int svdq_task_gram(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace,
                               double *out_gram, void *stream) {
-    if (!pl || !ptrs || !workspace || !out_gram) {
+    const SvdqInput in = plain_input(ptrs, rows_dev);
+    if (int rc = svdq_check_input(pl, in, 0, "svdq_task_gram")) return rc;
+    if (!workspace || !out_gram) {
         svdq_set_error("null argument");
         return SVDQ_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
     double *part = reinterpret_cast<double *>(ws(workspace, pl->ws_gram_off));
     double *part2 = reinterpret_cast<double *>(ws(workspace, pl->ws_gram2_off));
-    if (int rc = svdq_launch_gram(pl, ptrs, rows_dev, part, 0, pl->n_units, /*center=*/0, nullptr, nullptr,
-                                  pl->ntp <= 16, nullptr, st))
-        return rc;
+    if (int rc = svdq_launch_gram(pl, in, part, 0, pl->n_units, /*center=*/0, pl->ntp <= 16, nullptr, st)) return rc;
     if (int rc = svdq_launch_reduce(pl, part, part2, 0, pl->n_params, nullptr, st)) return rc;
     return svdq_launch_gram_total(pl, part2, out_gram, st);
 }
 
-static int eig_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace, void *small,
-                     int32_t param0, int32_t nparams, const void *idx, void *stream, const void *base = nullptr,
-                     const int64_t *ustart = nullptr) {
-    if (!pl || !ptrs || !workspace || !small) {
+static int eig_range(const svdq_plan *pl, const SvdqInput &in, void *workspace, void *small, int32_t param0,
+                     int32_t nparams, void *stream) {
+    if (!workspace || !small) {
         svdq_set_error("null argument");
         return SVDQ_EINVAL;
     }
@@ -318,34 +357,32 @@ static int eig_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_
     float *W = reinterpret_cast<float *>(ws(workspace, pl->ws_w_off));
     double *c0 = reinterpret_cast<double *>(ws(workspace, pl->ws_c0_off));
     uint8_t *sm = reinterpret_cast<uint8_t *>(small);
-    const bool refine = pl->ntp > 16 && !(pl->cfg.reserved & 2);
+    const bool refine = pl->ntp > 16 && !(pl->cfg.reserved & SVDQ_SW_GRAM_F32);
     int32_t *flags = refine ? reinterpret_cast<int32_t *>(ws(workspace, pl->ws_flag_off)) : nullptr;
     if (int rc = svdq_launch_reduce(pl, part, part2, param0, nparams, nullptr, st)) return rc;
-    if (int rc = svdq_launch_eig(pl, ptrs, rows_dev, part2, W, c0, sm, param0, nparams, idx, base, nullptr, flags, st,
-                                 ustart))
-        return rc;
+    if (int rc = svdq_launch_eig(pl, in, part2, W, c0, sm, param0, nparams, nullptr, flags, st)) return rc;
     if (!refine) return SVDQ_OK;
     // N > 16: the parameters whose spectrum reaches into the band fp32-product sums do not resolve are accumulated
     // again with exact products (v_mfma_f64_16x16x4_f64) and solved again; units of all other parameters return at
     // once, so a batch without such a parameter pays three near-empty launches
     int u0, nu;
     unit_range(pl, param0, nparams, &u0, &nu);
-    if (int rc = svdq_launch_gram(pl, ptrs, rows_dev, part, u0, nu, pl->cfg.center, idx, base, 1, flags, st, ustart))
-        return rc;
+    if (int rc = svdq_launch_gram(pl, in, part, u0, nu, pl->cfg.center, 1, flags, st)) return rc;
     if (int rc = svdq_launch_reduce(pl, part, part2, param0, nparams, flags, st)) return rc;
-    return svdq_launch_eig(pl, ptrs, rows_dev, part2, W, c0, sm, param0, nparams, idx, base, flags, nullptr, st, ustart);
+    return svdq_launch_eig(pl, in, part2, W, c0, sm, param0, nparams, flags, nullptr, st);
 }
 
 extern "C" int svdq_eig_rank_select_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev,
                                           void *workspace, void *small, int32_t param0, int32_t nparams,
                                           void *stream) {
-    return eig_range(pl, ptrs, rows_dev, workspace, small, param0, nparams, nullptr, stream);
+    const SvdqInput in = plain_input(ptrs, rows_dev);
+    if (int rc = svdq_check_input(pl, in, 0, "svdq_eig_rank_select_range")) return rc;
+    return eig_range(pl, in, workspace, small, param0, nparams, stream);
 }
 
-static int bp_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace, const void *small,
-                    void *basis, float *mean, int32_t param0, int32_t nparams, const void *idx, void *stream,
-                    const void *base = nullptr, const int64_t *ustart = nullptr) {
-    if (!pl || !ptrs || !workspace || !small || !basis) {
+static int bp_range(const svdq_plan *pl, const SvdqInput &in, void *workspace, const void *small, void *basis,
+                    float *mean, int32_t param0, int32_t nparams, void *stream) {
+    if (!workspace || !small || !basis) {
         svdq_set_error("null argument");
         return SVDQ_EINVAL;
     }
@@ -357,18 +394,20 @@ static int bp_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_d
     int u0, nu;
     unit_range(pl, param0, nparams, &u0, &nu);
     const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    return svdq_launch_basis_project(pl, ptrs, rows_dev, reinterpret_cast<const float *>(ws(workspace, pl->ws_w_off)),
+    return svdq_launch_basis_project(pl, in, reinterpret_cast<const float *>(ws(workspace, pl->ws_w_off)),
                                      reinterpret_cast<const int32_t *>(sm + pl->small.k_off),
                                      reinterpret_cast<const int32_t *>(sm + pl->small.r_off),
                                      reinterpret_cast<uint8_t *>(basis), mean,
                                      reinterpret_cast<double *>(ws(workspace, pl->ws_cpart_off)), u0, nu,
-                                     pl->cfg.reserved & 5, idx, base, (hipStream_t)stream, ustart);
+                                     pl->cfg.reserved & (SVDQ_SW_REVERSE | SVDQ_SW_XCD_CHUNKED), (hipStream_t)stream);
 }
 
 extern "C" int svdq_basis_project_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev,
                                         void *workspace, const void *small, void *basis, float *mean, int32_t param0,
                                         int32_t nparams, void *stream) {
-    return bp_range(pl, ptrs, rows_dev, workspace, small, basis, mean, param0, nparams, nullptr, stream);
+    const SvdqInput in = plain_input(ptrs, rows_dev);
+    if (int rc = svdq_check_input(pl, in, 0, "svdq_basis_project_range")) return rc;
+    return bp_range(pl, in, workspace, small, basis, mean, param0, nparams, stream);
 }
 
 extern "C" int svdq_coeff_quantize_range(const svdq_plan *pl, void *workspace, void *small, int32_t param0,
@@ -410,16 +449,28 @@ extern "C" int svdq_coeff_quantize(const svdq_plan *pl, void *workspace, void *s
     return svdq_coeff_quantize_range(pl, workspace, small, 0, pl->n_params, stream);
 }
 
-extern "C" int svdq_compress(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace,
-                             void *small, void *basis, float *mean, void *stream) {
-    if (pl && small)
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
-                               (hipStream_t)stream));
-    int rc = svdq_gram_center(pl, ptrs, rows_dev, workspace, stream);
-    if (rc == SVDQ_OK) rc = svdq_eig_rank_select(pl, ptrs, rows_dev, workspace, small, stream);
-    if (rc == SVDQ_OK) rc = svdq_basis_project(pl, ptrs, rows_dev, workspace, small, basis, mean, stream);
+// One compress step over the whole plan: status word cleared, then gram -> eig / rank -> basis + projection ->
+// coefficient quantization.  `in` has passed svdq_check_input.
+static int compress_step(const svdq_plan *pl, const SvdqInput &in, void *workspace, void *small, void *basis,
+                         float *mean, void *stream) {
+    if (!workspace || !small || !basis) {
+        svdq_set_error("null argument");
+        return SVDQ_EINVAL;
+    }
+    HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
+                           (hipStream_t)stream));
+    int rc = gram_range(pl, in, workspace, 0, pl->n_params, stream);
+    if (rc == SVDQ_OK) rc = eig_range(pl, in, workspace, small, 0, pl->n_params, stream);
+    if (rc == SVDQ_OK) rc = bp_range(pl, in, workspace, small, basis, mean, 0, pl->n_params, stream);
     if (rc == SVDQ_OK) rc = svdq_coeff_quantize(pl, workspace, small, stream);
     return rc;
+}
+
+extern "C" int svdq_compress(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace,
+                             void *small, void *basis, float *mean, void *stream) {
+    const SvdqInput in = plain_input(ptrs, rows_dev);
+    if (int rc = svdq_check_input(pl, in, 0, "svdq_compress")) return rc;
+    return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
 // Masked parameters without a compaction pass: delta_ptrs name the ORIGINAL (full-size) tensors,
@@ -429,19 +480,10 @@ extern "C" int svdq_compress(const svdq_plan *pl, const void *ptrs, const int64_
 extern "C" int svdq_compress_gather(const svdq_plan *pl, const void *ptrs, const void *index_ptrs,
                                     const int64_t *rows_dev, void *workspace, void *small, void *basis, float *mean,
                                     void *stream) {
-    if (!pl || !index_ptrs || !rows_dev) {
-        svdq_set_error("svdq_compress_gather: plan, index_ptrs and rows_dev are required");
-        return SVDQ_EINVAL;
-    }
-    if (small)
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
-                               (hipStream_t)stream));
-    int rc = gram_range(pl, ptrs, rows_dev, workspace, 0, pl->n_params, index_ptrs, stream);
-    if (rc == SVDQ_OK) rc = eig_range(pl, ptrs, rows_dev, workspace, small, 0, pl->n_params, index_ptrs, stream);
-    if (rc == SVDQ_OK)
-        rc = bp_range(pl, ptrs, rows_dev, workspace, small, basis, mean, 0, pl->n_params, index_ptrs, stream);
-    if (rc == SVDQ_OK) rc = svdq_coeff_quantize(pl, workspace, small, stream);
-    return rc;
+    SvdqInput in = plain_input(ptrs, rows_dev);
+    in.index = index_ptrs;
+    if (int rc = svdq_check_input(pl, in, 1, "svdq_compress_gather")) return rc;
+    return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
 // Step 0 folded into the path: delta_ptrs of svdq_compress are replaced by the FINE-TUNED tensors and one base
@@ -451,21 +493,10 @@ extern "C" int svdq_compress_gather(const svdq_plan *pl, const void *ptrs, const
 extern "C" int svdq_compress_from_base(const svdq_plan *pl, const void *finetuned_ptrs, const void *base_ptrs,
                                        const int64_t *rows_dev, void *workspace, void *small, void *basis, float *mean,
                                        void *stream) {
-    if (!pl || !base_ptrs) {
-        svdq_set_error("svdq_compress_from_base: plan and base_ptrs are required");
-        return SVDQ_EINVAL;
-    }
-    if (small)
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
-                               (hipStream_t)stream));
-    int rc = gram_range(pl, finetuned_ptrs, rows_dev, workspace, 0, pl->n_params, nullptr, stream, base_ptrs);
-    if (rc == SVDQ_OK)
-        rc = eig_range(pl, finetuned_ptrs, rows_dev, workspace, small, 0, pl->n_params, nullptr, stream, base_ptrs);
-    if (rc == SVDQ_OK)
-        rc = bp_range(pl, finetuned_ptrs, rows_dev, workspace, small, basis, mean, 0, pl->n_params, nullptr, stream,
-                      base_ptrs);
-    if (rc == SVDQ_OK) rc = svdq_coeff_quantize(pl, workspace, small, stream);
-    return rc;
+    SvdqInput in = plain_input(finetuned_ptrs, rows_dev);
+    in.base = base_ptrs;
+    if (int rc = svdq_check_input(pl, in, 2, "svdq_compress_from_base")) return rc;
+    return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
 // Both at once: masked parameters straight from checkpoints.  finetuned_ptrs name the ORIGINAL (full-size) fine-tuned
@@ -474,21 +505,11 @@ extern "C" int svdq_compress_from_base(const svdq_plan *pl, const void *finetune
 extern "C" int svdq_compress_gather_from_base(const svdq_plan *pl, const void *finetuned_ptrs, const void *base_ptrs,
                                               const void *index_ptrs, const int64_t *rows_dev, void *workspace,
                                               void *small, void *basis, float *mean, void *stream) {
-    if (!pl || !base_ptrs || !index_ptrs || !rows_dev) {
-        svdq_set_error("svdq_compress_gather_from_base: plan, base_ptrs, index_ptrs and rows_dev are required");
-        return SVDQ_EINVAL;
-    }
-    if (small)
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
-                               (hipStream_t)stream));
-    int rc = gram_range(pl, finetuned_ptrs, rows_dev, workspace, 0, pl->n_params, index_ptrs, stream, base_ptrs);
-    if (rc == SVDQ_OK)
-        rc = eig_range(pl, finetuned_ptrs, rows_dev, workspace, small, 0, pl->n_params, index_ptrs, stream, base_ptrs);
-    if (rc == SVDQ_OK)
-        rc = bp_range(pl, finetuned_ptrs, rows_dev, workspace, small, basis, mean, 0, pl->n_params, index_ptrs, stream,
-                      base_ptrs);
-    if (rc == SVDQ_OK) rc = svdq_coeff_quantize(pl, workspace, small, stream);
-    return rc;
+    SvdqInput in = plain_input(finetuned_ptrs, rows_dev);
+    in.index = index_ptrs;
+    in.base = base_ptrs;
+    if (int rc = svdq_check_input(pl, in, 3, "svdq_compress_gather_from_base")) return rc;
+    return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
 // Masked parameters WITHOUT index lists (the default for dense masks; reference cli.py:324-341 +
@@ -497,27 +518,16 @@ extern "C" int svdq_compress_gather_from_base(const svdq_plan *pl, const void *f
 // (svdq_maskset_unit_starts / _combine_starts; its bit 62 selects the cleared elements -- the noise region) and
 // rows_dev[p] how many rows parameter p has.  The passes walk the source rows, read the mask beside them and compact
 // the selected rows into the LDS strip on the fly: 4 N + 1 bytes per source row and pass, no index lists, no compacted
-// copies.  Outputs are those of svdq_compress on the compacted tensors, bit for bit.  Above 16 tasks both passes take
-// their one-wave kernels (svdq_project_walk.hip): slower per byte than the two-wave kernels the index-list route runs.
+// copies.  Which task counts the walk covers, and what its outputs are bit-identical to: include/svdq.h,
+// svdq_compress_masked.
 extern "C" int svdq_compress_masked(const svdq_plan *pl, const void *ptrs, const void *mask_ptrs,
                                     const int64_t *unit_start, const int64_t *rows_dev, void *workspace, void *small,
                                     void *basis, float *mean, void *stream) {
-    if (!pl || !mask_ptrs || !unit_start || !rows_dev) {
-        svdq_set_error("svdq_compress_masked: plan, mask_ptrs, unit_start and rows_dev are required");
-        return SVDQ_EINVAL;
-    }
-    if (int rc = svdq_require_f32_input(pl, "svdq_compress_masked")) return rc;
-    if (small)
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
-                               (hipStream_t)stream));
-    int rc = gram_range(pl, ptrs, rows_dev, workspace, 0, pl->n_params, mask_ptrs, stream, nullptr, unit_start);
-    if (rc == SVDQ_OK)
-        rc = eig_range(pl, ptrs, rows_dev, workspace, small, 0, pl->n_params, mask_ptrs, stream, nullptr, unit_start);
-    if (rc == SVDQ_OK)
-        rc = bp_range(pl, ptrs, rows_dev, workspace, small, basis, mean, 0, pl->n_params, mask_ptrs, stream, nullptr,
-                      unit_start);
-    if (rc == SVDQ_OK) rc = svdq_coeff_quantize(pl, workspace, small, stream);
-    return rc;
+    SvdqInput in = plain_input(ptrs, rows_dev);
+    in.mask = mask_ptrs;
+    in.ustart = unit_start;
+    if (int rc = svdq_check_input(pl, in, 4, "svdq_compress_masked")) return rc;
+    return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
 // The same straight from checkpoints: finetuned[row] - base[row] is formed in registers in both passes.
@@ -525,26 +535,10 @@ extern "C" int svdq_compress_masked(const svdq_plan *pl, const void *ptrs, const
 extern "C" int svdq_compress_masked_from_base(const svdq_plan *pl, const void *finetuned_ptrs, const void *base_ptrs,
                                               const void *mask_ptrs, const int64_t *unit_start, const int64_t *rows_dev,
                                               void *workspace, void *small, void *basis, float *mean, void *stream) {
-    if (!pl || !base_ptrs || !mask_ptrs || !unit_start || !rows_dev) {
-        svdq_set_error("svdq_compress_masked_from_base: plan, base_ptrs, mask_ptrs, unit_start and rows_dev are required");
-        return SVDQ_EINVAL;
-    }
-    if (int rc = svdq_require_f32_input(pl, "svdq_compress_masked_from_base")) return rc;
-    if (pl->ntp > 16) {
-        svdq_set_error("the mask-walk mode covers N <= 16 tasks (got %d): use the index lists "
-                       "(svdq_compress_gather_from_base)", pl->n_tasks);
-        return SVDQ_EUNSUPPORTED;
-    }
-    if (small)
-        HIP_TRY(hipMemsetAsync(reinterpret_cast<uint8_t *>(small) + pl->small.status_off, 0, sizeof(int32_t),
-                               (hipStream_t)stream));
-    int rc = gram_range(pl, finetuned_ptrs, rows_dev, workspace, 0, pl->n_params, mask_ptrs, stream, base_ptrs, unit_start);
-    if (rc == SVDQ_OK)
-        rc = eig_range(pl, finetuned_ptrs, rows_dev, workspace, small, 0, pl->n_params, mask_ptrs, stream, base_ptrs,
-                       unit_start);
-    if (rc == SVDQ_OK)
-        rc = bp_range(pl, finetuned_ptrs, rows_dev, workspace, small, basis, mean, 0, pl->n_params, mask_ptrs, stream,
-                      base_ptrs, unit_start);
-    if (rc == SVDQ_OK) rc = svdq_coeff_quantize(pl, workspace, small, stream);
-    return rc;
+    SvdqInput in = plain_input(finetuned_ptrs, rows_dev);
+    in.mask = mask_ptrs;
+    in.ustart = unit_start;
+    in.base = base_ptrs;
+    if (int rc = svdq_check_input(pl, in, 6, "svdq_compress_masked_from_base")) return rc;
+    return compress_step(pl, in, workspace, small, basis, mean, stream);
 }

@@ -58,35 +58,57 @@ __host__ __device__ static inline int64_t svdq_align_up(int64_t x, int64_t a) { 
 // padded task count the streaming kernels are instantiated for (multiple of 4, <= 32)
 static inline int svdq_ntp(int n) { return (n + 3) / 4 * 4; }
 
+// svdq_config.reserved: the measurement switches (bit meanings: include/svdq.h)
+enum {
+    SVDQ_SW_REVERSE = 1,         // pass 2 walks the units in reverse order
+    SVDQ_SW_GRAM_F32 = 2,        // fp32-product Gram for every N
+    SVDQ_SW_XCD_CHUNKED = 4,     // XCD-chunked unit order in both passes
+    SVDQ_SW_PASS2_TWO_WAVE = 8,  // N = 17..20: the two-wave pass 2
+};
+
+// What the streaming passes of one compress step read.  Which pointers are set selects the kernels' MODE.
+struct SvdqInput {
+    const void *ptrs;         // device table [n_params * n_tasks] of task (with base: fine-tuned) tensors
+    const int64_t *rows_dev;  // NULL, or per-parameter row counts [n_params]
+    const void *index;        // NULL, or device table [n_params] of int32 index lists (gather, svdq_compress_gather)
+    const void *mask;         // NULL, or device table [n_params] of combined-mask byte tensors (walk, svdq_compress_masked)
+    const int64_t *ustart;    // NULL, or the walk's per-unit source start positions [n_units] (svdq_maskset_*_starts)
+    const void *base;         // NULL, or device table [n_params] of base tensors (minus-base, svdq_compress_from_base)
+
+    // the kernels' MODE template value: 0 plain, 1 gather, 2 base, 3 gather + base, 4 walk, 6 walk + base
+    int mode() const { return (ustart ? 4 : (index ? 1 : 0)) | (base ? 2 : 0); }
+    // the streaming kernels' two `aux` tables: the walk reads its masks where the gather reads its index lists
+    const void *const *aux() const { return static_cast<const void *const *>(mask ? mask : index); }
+    const void *const *aux2() const { return static_cast<const void *const *>(base); }
+    const float *const *tensors() const { return static_cast<const float *const *>(ptrs); }
+};
+
 void svdq_set_error(const char *fmt, ...);
 // SVDQ_OK for an fp32-input plan; otherwise SVDQ_EUNSUPPORTED with the error text naming `who` (entry points whose
 // kernels read task tensors as fp32 only)
 int svdq_require_f32_input(const svdq_plan *pl, const char *who);
+// what a launcher returns: `launched` is its dispatch's result (svdq_dispatch.h).  Which (mode, input type, task
+// count) combinations have a kernel is svdq_check_input's business (svdq_api.hip), so false here is a library bug.
+int svdq_launch_status(bool launched, const char *kernel);
 
 // launchers (defined in the .hip files)
-// idx: NULL, or a device table [n_params] of int32 index lists (gather mode, see svdq_compress_gather);
-// base: NULL, or a device table [n_params] of base tensors (minus-base mode, see svdq_compress_from_base);
 // only: NULL, or a device table [n_params] of int32 -- parameters whose entry is 0 are skipped (refinement pass)
-// ustart: NULL, or the walk mode's per-unit source start positions [n_units] (svdq_maskset_*_starts); idx then names
-// the combined MASK byte tensors instead of index lists (svdq_compress_masked)
-int svdq_launch_gram(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, double *gram_part,
-                     int unit0, int nunits, int center, const void *idx, const void *base, int f64,
-                     const int32_t *only, hipStream_t st, const int64_t *ustart = nullptr);
+// f64: accumulate the products with v_mfma_f64_16x16x4_f64 (exact) instead of fp32 MFMA
+int svdq_launch_gram(const svdq_plan *pl, const SvdqInput &in, double *gram_part, int unit0, int nunits, int center,
+                     int f64, const int32_t *only, hipStream_t st);
 int svdq_launch_gram_total(const svdq_plan *pl, const double *part2, double *out, hipStream_t st);
-int svdq_launch_basis_project(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, const float *W,
-                              const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean,
-                              double *cpart, int unit0, int nunits, int reverse, const void *idx, const void *base,
-                              hipStream_t st, const int64_t *ustart = nullptr);
+// reverse: the unit order switches (SVDQ_SW_REVERSE | SVDQ_SW_XCD_CHUNKED) of cfg.reserved
+int svdq_launch_basis_project(const svdq_plan *pl, const SvdqInput &in, const float *W, const int32_t *k_dev,
+                              const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart, int unit0, int nunits,
+                              int reverse, hipStream_t st);
 // pass 2 of the mask-walk mode for 16 < N <= 32 (svdq_project_walk.hip)
-int svdq_launch_basis_project_walk32(const svdq_plan *pl, const float *const *pp, const int64_t *rows_dev, const float *W,
-                                     const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart,
-                                     int unit0, int nunits, int reverse, const void *const *masks, const int64_t *ustart,
-                                     hipStream_t st);
+int svdq_launch_basis_project_walk32(const svdq_plan *pl, const SvdqInput &in, const float *W, const int32_t *k_dev,
+                                     const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart, int unit0,
+                                     int nunits, int reverse, hipStream_t st);
 // refine_out: NULL, or a device table [n_params] that receives 1 where a singular value lies in the band the fp32-product
 // Gram does not resolve (then the caller re-accumulates those parameters in fp64 and calls again with only = that table)
-int svdq_launch_eig(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, const double *gram_part, float *W,
-                    double *c0, uint8_t *small, int param0, int nparams, const void *idx, const void *base,
-                    const int32_t *only, int32_t *refine_out, hipStream_t st, const int64_t *ustart = nullptr);
+int svdq_launch_eig(const svdq_plan *pl, const SvdqInput &in, const double *gram_part, float *W, double *c0,
+                    uint8_t *small, int param0, int nparams, const int32_t *only, int32_t *refine_out, hipStream_t st);
 int svdq_launch_reduce(const svdq_plan *pl, const double *part, double *part2, int param0, int nparams,
                        const int32_t *only, hipStream_t st);
 int svdq_launch_coeff(const svdq_plan *pl, const double *cpart, const double *c0, uint8_t *small, int param0,

@@ -1,5 +1,6 @@
 // svdq_gram.hip -- pass 1 of the SVD-Hybrid compressor: G = Tc^T Tc (k_gram).  Helpers and the layout notes: svdq_stream.h.
 #include "svdq_stream.h"
+#include "svdq_dispatch.h"
 
 // ------------------------------------------------------------------------------------ pass 1
 // One work unit of pass 1 (a run of 256-row blocks of one parameter) by ONE wavefront.
@@ -474,91 +475,38 @@ __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) 
     SVDQ_STAMP_END(svdq_stamps_gram, uidx);
 }
 
-// ------------------------------------------------------------------------------------ launchers
-// idx: NULL or the device table of index lists (gather mode); base: NULL or the device table of base tensors
-// (minus-base mode); both may be given (masked parameters straight from checkpoints).  ustart: NULL, or the per-unit
-// source start positions of the walk mode -- idx is then the device table of combined MASK byte tensors.
-template <int NTP, typename TIN>
-static int launch_gram_t(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, double *gram_part,
-                         int unit0, int nunits, int center, const void *idx, const void *base, int f64,
-                         const int32_t *only, const int64_t *ustart, hipStream_t st) {
-    auto pp = reinterpret_cast<const float *const *>(ptrs);
-    auto ai = (const void *const *)idx, ab = (const void *const *)base;
-#define SVDQ_LAUNCH_GRAM_(M, F, FULL_)                                                                                     \
-    hipLaunchKernelGGL((k_gram<NTP, M, F, FULL_, TIN>), dim3(nunits), dim3(64), 0, st, pl->d_params, pl->d_units, pp, rows_dev, \
-                       pl->n_tasks, center, gram_part, unit0, ai, only, ab, pl->cfg.reserved & 4, ustart)
-    // the plain and the mask-walk mode have a variant for plans with exactly NTP tasks
-#define SVDQ_LAUNCH_GRAM(M, F)                                                                                       \
-    do {                                                                                                             \
-        if constexpr ((M) == 0 || (M) == 4) {                                                                        \
-            if (pl->n_tasks == NTP) {                                                                                \
-                SVDQ_LAUNCH_GRAM_(M, F, true);                                                                       \
-                break;                                                                                               \
-            }                                                                                                        \
-        }                                                                                                            \
-        SVDQ_LAUNCH_GRAM_(M, F, false);                                                                              \
-    } while (0)
-    const int mode = ustart ? (4 | (base ? 2 : 0)) : ((idx ? 1 : 0) | (base ? 2 : 0));
-    if constexpr (sizeof(TIN) != 4) {   // half inputs: modes 0..3 only (the walk is instantiated for fp32)
-        if (mode & 4) {
-            svdq_set_error("the mask walk reads fp32 task tensors only");
-            return SVDQ_EUNSUPPORTED;
-        }
-    } else if constexpr (NTP <= 16) {
-        if (mode & 4) {      // walk mode exists for the one-wave kernels (N <= 16), always with the default Gram
-            if (f64) {
-                if (mode == 4) SVDQ_LAUNCH_GRAM(4, true); else SVDQ_LAUNCH_GRAM(6, true);
-            } else {
-                if (mode == 4) SVDQ_LAUNCH_GRAM(4, false); else SVDQ_LAUNCH_GRAM(6, false);
-            }
-            return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
-        }
-    }
-    if (mode & 4) {      // 16 < N <= 32: the same one-wave kernel walks (pass 2: svdq_project_walk.hip); not from checkpoints
-        if (mode != 4) {
-            svdq_set_error("the mask walk straight from checkpoints covers N <= 16 tasks (got %d): use the index lists "
-                           "(svdq_compress_gather_from_base)", pl->n_tasks);
-            return SVDQ_EUNSUPPORTED;
-        }
-        if constexpr (sizeof(TIN) == 4) {
-            if (f64) SVDQ_LAUNCH_GRAM_(4, true, false); else SVDQ_LAUNCH_GRAM_(4, false, false);
-        }
-        return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
-    }
-    if (f64) {
-        switch (mode) {
-            case 0: SVDQ_LAUNCH_GRAM(0, true); break;
-            case 1: SVDQ_LAUNCH_GRAM(1, true); break;
-            case 2: SVDQ_LAUNCH_GRAM(2, true); break;
-            default: SVDQ_LAUNCH_GRAM(3, true); break;
-        }
-    } else {
-        switch (mode) {
-            case 0: SVDQ_LAUNCH_GRAM(0, false); break;
-            case 1: SVDQ_LAUNCH_GRAM(1, false); break;
-            case 2: SVDQ_LAUNCH_GRAM(2, false); break;
-            default: SVDQ_LAUNCH_GRAM(3, false); break;
-        }
-    }
-#undef SVDQ_LAUNCH_GRAM
-#undef SVDQ_LAUNCH_GRAM_
-    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
-}
-
-// f64: accumulate the products with v_mfma_f64_16x16x4_f64 (exact) instead of fp32 MFMA; only: NULL, or a device
-// table [n_params] -- units of parameters whose entry is 0 return at once (the refinement pass of N > 16)
-int svdq_launch_gram(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, double *gram_part,
-                     int unit0, int nunits, int center, const void *idx, const void *base, int f64,
-                     const int32_t *only, hipStream_t st, const int64_t *ustart) {
-#define SVDQ_GRAM_CASE(n) \
-    case n: return launch_gram_t<n, TIN>(pl, ptrs, rows_dev, gram_part, unit0, nunits, center, idx, base, f64, only, ustart, st)
-    SVDQ_DISPATCH_INPUT(pl, TIN, switch (pl->ntp) {
-        SVDQ_GRAM_CASE(4); SVDQ_GRAM_CASE(8); SVDQ_GRAM_CASE(12); SVDQ_GRAM_CASE(16);
-        SVDQ_GRAM_CASE(20); SVDQ_GRAM_CASE(24); SVDQ_GRAM_CASE(28); SVDQ_GRAM_CASE(32);
+// ------------------------------------------------------------------------------------ launcher
+// Variants: the walk (MODE 4, 6) reads fp32 tensors only, and above 16 tasks plain deltas only (MODE 4); the plain and
+// the walk mode have a FULL variant for plans with exactly NTP tasks, the walk up to 16 tasks only.
+int svdq_launch_gram(const svdq_plan *pl, const SvdqInput &in, double *gram_part, int unit0, int nunits, int center,
+                     int f64, const int32_t *only, hipStream_t st) {
+    const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
+        using TIN = typename decltype(tin_c)::type;
+        return svdq_dispatch_int<4, 8, 12, 16, 20, 24, 28, 32>(pl->ntp, [&](auto ntp_c) {
+            constexpr int NTP = ntp_c;
+            return svdq_dispatch_int<0, 1, 2, 3, 4, 6>(in.mode(), [&](auto mode_c) {
+                constexpr int MODE = mode_c;
+                constexpr bool WALK = (MODE & 4) != 0;
+                constexpr bool HAS_FULL = MODE == 0 || (MODE == 4 && NTP <= 16);
+                if constexpr (WALK && (!std::is_same_v<TIN, float> || (NTP > 16 && MODE != 4))) return false;
+                else return svdq_dispatch_bool(f64 != 0, [&](auto f64_c) {
+                    constexpr bool F64 = f64_c;
+                    return svdq_dispatch_bool(HAS_FULL && pl->n_tasks == NTP, [&](auto full_c) {
+                        constexpr bool FULL = full_c;
+                        if constexpr (FULL && !HAS_FULL) return false;
+                        else {
+                            hipLaunchKernelGGL((k_gram<NTP, MODE, F64, FULL, TIN>), dim3(nunits), dim3(64), 0, st,
+                                               pl->d_params, pl->d_units, in.tensors(), in.rows_dev, pl->n_tasks, center,
+                                               gram_part, unit0, in.aux(), only, in.aux2(),
+                                               pl->cfg.reserved & SVDQ_SW_XCD_CHUNKED, in.ustart);
+                            return true;
+                        }
+                    });
+                });
+            });
+        });
     });
-#undef SVDQ_GRAM_CASE
-    svdq_set_error("unsupported padded task count %d", pl->ntp);
-    return SVDQ_EUNSUPPORTED;
+    return svdq_launch_status(ok, "k_gram");
 }
 
 

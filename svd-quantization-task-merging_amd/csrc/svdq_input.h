@@ -74,18 +74,3 @@ __device__ __forceinline__ svdq_f32x2 in_load2(gin<TIN> *p) {
         return in_widen2<TIN>(*reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(p));
     }
 }
-
-// the plan's input type as a template argument (SVDQ_INPUT_F32 / F16 / BF16)
-#define SVDQ_DISPATCH_INPUT(pl, TIN_, ...)                          \
-    do {                                                            \
-        if ((pl)->in_type == SVDQ_INPUT_F16) {                      \
-            using TIN_ = __half;                                    \
-            __VA_ARGS__;                                            \
-        } else if ((pl)->in_type == SVDQ_INPUT_BF16) {              \
-            using TIN_ = __hip_bfloat16;                            \
-            __VA_ARGS__;                                            \
-        } else {                                                    \
-            using TIN_ = float;                                     \
-            __VA_ARGS__;                                            \
-        }                                                           \
-    } while (0)

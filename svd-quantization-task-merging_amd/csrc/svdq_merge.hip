@@ -24,6 +24,7 @@
 // (the diagnostics' sums run in another order: equal to the last digits of the fp64 accumulators).
 
 #include "svdq_common.h"
+#include "svdq_dispatch.h"
 #include "svdq_input.h"
 #include <hip/hip_fp16.h>
 
@@ -1008,42 +1009,25 @@ static int launch_reconstruct(const char *who, const svdq_plan *pl, const int64_
                        (mp ? (size_t)64 * rpl * 4 : 0) + (size_t)(ns * pl->n_tasks + ns) * 4;
     const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
     const float *mn = pl->cfg.center ? mean : nullptr;
-#define SVDQ_MRG_LAUNCH(F16, NS_)                                                                                      \
-    do {                                                                                                               \
-        if (mp && rpl == 4)                                                                                            \
-            hipLaunchKernelGGL((k_merge_expand<F16, NS_, 4>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,       \
-                               pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn, cbar, set_share,  \
-                               scale, mp, unit_start, fill, bp, op);                                                   \
-        else if (mp)                                                                                                   \
-            hipLaunchKernelGGL((k_merge_expand<F16, NS_, 2>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,       \
-                               pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn, cbar, set_share,  \
-                               scale, mp, unit_start, fill, bp, op);                                                   \
-        else if (rpl == 4)                                                                                             \
-            hipLaunchKernelGGL((k_merge_reconstruct<F16, NS_, 4>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,  \
-                               pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn, cbar, set_share,  \
-                               scale, bp, op);                                                                         \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_merge_reconstruct<F16, NS_, 2>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,  \
-                               pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn, cbar, set_share,  \
-                               scale, bp, op);                                                                         \
-    } while (0)
-    if (pl->cfg.fp16) {
-        switch (ns) {
-            case 1: SVDQ_MRG_LAUNCH(true, 1); break;
-            case 2: SVDQ_MRG_LAUNCH(true, 2); break;
-            case 4: SVDQ_MRG_LAUNCH(true, 4); break;
-            default: SVDQ_MRG_LAUNCH(true, 8); break;
-        }
-    } else {
-        switch (ns) {
-            case 1: SVDQ_MRG_LAUNCH(false, 1); break;
-            case 2: SVDQ_MRG_LAUNCH(false, 2); break;
-            case 4: SVDQ_MRG_LAUNCH(false, 4); break;
-            default: SVDQ_MRG_LAUNCH(false, 8); break;
-        }
-    }
-#undef SVDQ_MRG_LAUNCH
-    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
+    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
+        constexpr bool F16 = f16_c;
+        return svdq_dispatch_int<1, 2, 4, 8>(ns, [&](auto ns_c) {
+            constexpr int NS = ns_c;
+            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
+                constexpr int RPL = rpl_c;
+                if (mp)
+                    hipLaunchKernelGGL((k_merge_expand<F16, NS, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
+                                       pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn, cbar,
+                                       set_share, scale, mp, unit_start, fill, bp, op);
+                else
+                    hipLaunchKernelGGL((k_merge_reconstruct<F16, NS, RPL>), dim3(pl->n_units), dim3(64), lds, st,
+                                       pl->d_params, pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn,
+                                       cbar, set_share, scale, bp, op);
+                return true;
+            });
+        });
+    });
+    return svdq_launch_status(ok, who);
 }
 
 extern "C" int svdq_merge_reconstruct(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
@@ -1099,30 +1083,6 @@ __global__ void k_one_hot(int n, float *w) {
 #ifndef SVDQ_DIAG_RPL_MID
 #define SVDQ_DIAG_RPL_MID 2      // rows per lane and block of the 9..24-task variants (A/B builds)
 #endif
-template <int NTP, int RPL, int SETS, bool FULL, typename TIN>
-static void launch_diag(const svdq_plan *pl, const void *ptrs, const void *mask_ptrs, const int64_t *unit_start,
-                        const int64_t *rows_dev, const int32_t *kk, const int32_t *rr, const uint8_t *basis,
-                        const float *mean, int add_mean, const float *ctask, DiagPart *part, hipStream_t st) {
-    auto pp = reinterpret_cast<const float *const *>(ptrs);
-    auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
-    using G = DiagGeom<NTP, RPL, SETS>;
-    const int n = pl->n_tasks, es = pl->cfg.fp16 ? 2 : 4;
-    const size_t lds = (size_t)svdq_align_up((int64_t)G::RB * n * es + 48, 16) +
-                       (size_t)(NTP + 1) * diag_xs(G::RB, mp != nullptr) * 4;
-#define SVDQ_DIAG_LAUNCH(F16, WALK_)                                                                                   \
-    hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK_, TIN>), dim3(pl->n_units), dim3(64), lds, st,           \
-                       pl->d_params, pl->d_units, pp, mp, unit_start, rows_dev, n, kk, rr, basis, mean, add_mean, ctask,  \
-                       part)
-    if constexpr (sizeof(TIN) != 4) {   // half inputs: the plain form only (svdq_diagnostics_masked rejects them)
-        if (pl->cfg.fp16) SVDQ_DIAG_LAUNCH(true, false); else SVDQ_DIAG_LAUNCH(false, false);
-    } else if (pl->cfg.fp16) {
-        if (mp) SVDQ_DIAG_LAUNCH(true, true); else SVDQ_DIAG_LAUNCH(true, false);
-    } else {
-        if (mp) SVDQ_DIAG_LAUNCH(false, true); else SVDQ_DIAG_LAUNCH(false, false);
-    }
-#undef SVDQ_DIAG_LAUNCH
-}
-
 static int run_diagnostics(const char *who, const svdq_plan *pl, const void *delta_ptrs, const void *mask_ptrs,
                            const int64_t *unit_start, const int64_t *rows_dev, const void *small, const void *basis,
                            const float *mean, int32_t add_mean, double *out, void *work, void *stream) {
@@ -1144,27 +1104,40 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
     const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
     auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
     auto bs = reinterpret_cast<const uint8_t *>(basis);
+    auto pp = reinterpret_cast<const float *const *>(delta_ptrs);
+    auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
     // variants by padded task count (the prefetch registers and the X strips are sized by it), each also for plans with
-    // exactly that many tasks
-#define SVDQ_DIAG_ARGS pl, delta_ptrs, mask_ptrs, unit_start, rows_dev, kk, rr, bs, mean, add_mean, ctask, part, st
-#define SVDQ_DIAG_PICK(NTP_, RPL_, PACK_)                                                                              \
-    SVDQ_DISPATCH_INPUT(pl, TIN,                                                                                       \
-        if (n == NTP_) launch_diag<NTP_, RPL_, PACK_, true, TIN>(SVDQ_DIAG_ARGS);                                       \
-        else launch_diag<NTP_, RPL_, PACK_, false, TIN>(SVDQ_DIAG_ARGS))
-    if (n <= 4) SVDQ_DIAG_PICK(4, 4, 4);
-    else if (n <= 8) SVDQ_DIAG_PICK(8, 4, 2);
-    else if (n <= 12) SVDQ_DIAG_PICK(12, SVDQ_DIAG_RPL_MID, 1);
-    else if (n <= 16) SVDQ_DIAG_PICK(16, SVDQ_DIAG_RPL_MID, 1);
-    else if (n <= 20) SVDQ_DIAG_PICK(20, SVDQ_DIAG_RPL_MID, 1);
-    else if (n <= 24) SVDQ_DIAG_PICK(24, SVDQ_DIAG_RPL_MID, 1);
-    else if (n <= 28) SVDQ_DIAG_PICK(28, 1, 1);
-    else if (n <= 32) SVDQ_DIAG_PICK(32, 1, 1);
-    else {
-        svdq_set_error("%s: unsupported task count %d", who, (int)n);
-        return SVDQ_EUNSUPPORTED;
-    }
-#undef SVDQ_DIAG_PICK
-#undef SVDQ_DIAG_ARGS
+    // exactly that many tasks (FULL); the walk over the masks (WALK) reads fp32 tensors only, which
+    // svdq_diagnostics_masked has checked
+    const bool ok = svdq_dispatch_int<4, 8, 12, 16, 20, 24, 28, 32>(pl->ntp, [&](auto ntp_c) {
+        constexpr int NTP = ntp_c;
+        constexpr int RPL = NTP <= 8 ? 4 : (NTP <= 24 ? SVDQ_DIAG_RPL_MID : 1);   // rows per lane and block
+        constexpr int SETS = NTP == 4 ? 4 : (NTP == 8 ? 2 : 1);                   // row sets packed into one tile
+        using G = DiagGeom<NTP, RPL, SETS>;
+        const size_t lds = (size_t)svdq_align_up((int64_t)G::RB * n * (pl->cfg.fp16 ? 2 : 4) + 48, 16) +
+                           (size_t)(NTP + 1) * diag_xs(G::RB, mp != nullptr) * 4;
+        return svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
+            using TIN = typename decltype(tin_c)::type;
+            constexpr bool CAN_WALK = std::is_same_v<TIN, float>;
+            return svdq_dispatch_bool(n == NTP, [&](auto full_c) {
+                constexpr bool FULL = full_c;
+                return svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
+                    constexpr bool F16 = f16_c;
+                    return svdq_dispatch_bool(CAN_WALK && mp != nullptr, [&](auto walk_c) {
+                        constexpr bool WALK = walk_c;
+                        if constexpr (WALK && !CAN_WALK) return false;
+                        else {
+                            hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK, TIN>), dim3(pl->n_units), dim3(64),
+                                               lds, st, pl->d_params, pl->d_units, pp, mp, unit_start, rows_dev, (int)n, kk,
+                                               rr, bs, mean, add_mean, ctask, part);
+                            return true;
+                        }
+                    });
+                });
+            });
+        });
+    });
+    if (!ok) return svdq_launch_status(false, who);
     hipLaunchKernelGGL(k_diag_finish, dim3(pl->n_params, (int)n), dim3(64), 0, st, pl->d_params, rows_dev, (int)n, part, out);
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }

@@ -1,6 +1,7 @@
 // svdq_project.hip -- pass 2 of the SVD-Hybrid compressor: U = Tc W -> fp16, mean, c = fp16(U)^T Tc (k_basis_project and its
 // N > 16 forms).  Helpers and the layout notes: svdq_stream.h.
 #include "svdq_project_unit.h"
+#include "svdq_dispatch.h"
 
 // ------------------------------------------------------------------------------------ N > 16: two waves
 // For 16 < N <= 32 the single-wave pass 2 needs 300+ registers (one wave per SIMD, nothing to overlap the
@@ -683,106 +684,54 @@ __global__ __launch_bounds__(64, SVDQ_Q_WAVES) void k_basis_project_q(
             }
 }
 
-// ------------------------------------------------------------------------------------ launchers
-template <int NTP, bool F16, typename TIN>
-static int launch_bp_mode(const svdq_plan *pl, const float *const *pp, const int64_t *rows_dev, const float *W,
-                          const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart,
-                          int unit0, int nunits, int reverse, const void *idx, const void *base,
-                          const int64_t *ustart, hipStream_t st) {
-    auto ai = (const void *const *)idx, ab = (const void *const *)base;
-    if constexpr (sizeof(TIN) != 4) {   // half inputs: modes 0..3 only (the walk is instantiated for fp32)
-        if (ustart) {
-            svdq_set_error("the mask walk reads fp32 task tensors only");
-            return SVDQ_EUNSUPPORTED;
-        }
-    } else if (ustart) {
-        if constexpr (NTP <= 16) {
-#define SVDQ_LAUNCH_BPW(M, FULL_)                                                                                     \
-    hipLaunchKernelGGL((k_basis_project<NTP, F16, M, FULL_, float>), dim3(nunits), dim3(64), 0, st, pl->d_params, pl->d_units, \
-                       pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean, cpart, unit0, reverse, \
-                       ai, ab, ustart)
-            if (pl->n_tasks == NTP) {
-                if (base) SVDQ_LAUNCH_BPW(6, true); else SVDQ_LAUNCH_BPW(4, true);
-            } else {
-                if (base) SVDQ_LAUNCH_BPW(6, false); else SVDQ_LAUNCH_BPW(4, false);
-            }
-#undef SVDQ_LAUNCH_BPW
-            return SVDQ_OK;
-        }
-        if (base) {
-            svdq_set_error("the mask walk straight from checkpoints covers N <= 16 tasks (got %d): use the index lists "
-                           "(svdq_compress_gather_from_base)", pl->n_tasks);
-            return SVDQ_EUNSUPPORTED;
-        }
-        return svdq_launch_basis_project_walk32(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse,
-                                                ai, ustart, st);   // the one-wave kernel: svdq_project_walk.hip
-    }
-#define SVDQ_LAUNCH_BP(M)                                                                                             \
-    do {                                                                                                              \
-        if constexpr (NTP == 20) {   /* N = 21..24: measured slower than the two-wave kernel (11.9 against 10.0 ms) */ \
-            if (!(pl->cfg.reserved & 8)) {   /* bit 3: the two-wave kernel instead (A/B) */                           \
-                if (pl->n_tasks == NTP)                                                                               \
-                    hipLaunchKernelGGL((k_basis_project_q<NTP, F16, M, true, TIN>), dim3(nunits), dim3(64), 0, st,         \
-                                       pl->d_params, pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, \
-                                       r_dev, basis, mean, cpart, unit0, reverse, ai, ab);                            \
-                else                                                                                                  \
-                    hipLaunchKernelGGL((k_basis_project_q<NTP, F16, M, false, TIN>), dim3(nunits), dim3(64), 0, st,        \
-                                       pl->d_params, pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, \
-                                       r_dev, basis, mean, cpart, unit0, reverse, ai, ab);                            \
-                break;                                                                                                \
-            }                                                                                                         \
-        }                                                                                                             \
-        if constexpr (NTP > 16)                                                                                       \
-            hipLaunchKernelGGL((k_basis_project2<NTP, F16, M, TIN>), dim3(nunits), dim3(128), 0, st, pl->d_params,         \
-                               pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean,  \
-                               cpart, unit0, reverse, ai, ab);                                                        \
-        else if (pl->n_tasks == NTP)                                                                                  \
-            hipLaunchKernelGGL((k_basis_project<NTP, F16, M, true, TIN>), dim3(nunits), dim3(64), 0, st, pl->d_params,     \
-                               pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean,  \
-                               cpart, unit0, reverse, ai, ab, (const int64_t *)nullptr);                              \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_basis_project<NTP, F16, M, false, TIN>), dim3(nunits), dim3(64), 0, st, pl->d_params,    \
-                               pl->d_units, pp, rows_dev, pl->n_tasks, pl->cfg.center, W, k_dev, r_dev, basis, mean,  \
-                               cpart, unit0, reverse, ai, ab, (const int64_t *)nullptr);                              \
-    } while (0)
-    switch ((idx ? 1 : 0) | (base ? 2 : 0)) {
-        case 0: SVDQ_LAUNCH_BP(0); break;
-        case 1: SVDQ_LAUNCH_BP(1); break;
-        case 2: SVDQ_LAUNCH_BP(2); break;
-        default: SVDQ_LAUNCH_BP(3); break;
-    }
-#undef SVDQ_LAUNCH_BP
-    return SVDQ_OK;
-}
-
-template <int NTP, typename TIN>
-static int launch_bp_t(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, const float *W,
-                       const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart,
-                       int unit0, int nunits, int reverse, const void *idx, const void *base, const int64_t *ustart,
-                       hipStream_t st) {
-    auto pp = reinterpret_cast<const float *const *>(ptrs);
-    int rc;
-    if (pl->cfg.fp16)
-        rc = launch_bp_mode<NTP, true, TIN>(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st);
-    else
-        rc = launch_bp_mode<NTP, false, TIN>(pl, pp, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st);
-    if (rc != SVDQ_OK) return rc;
-    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
-}
-
-int svdq_launch_basis_project(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, const float *W,
-                              const int32_t *k_dev, const int32_t *r_dev, uint8_t *basis, float *mean,
-                              double *cpart, int unit0, int nunits, int reverse, const void *idx, const void *base,
-                              hipStream_t st, const int64_t *ustart) {
-#define SVDQ_BP_CASE(n) \
-    case n: return launch_bp_t<n, TIN>(pl, ptrs, rows_dev, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, idx, base, ustart, st)
-    SVDQ_DISPATCH_INPUT(pl, TIN, switch (pl->ntp) {
-        SVDQ_BP_CASE(4); SVDQ_BP_CASE(8); SVDQ_BP_CASE(12); SVDQ_BP_CASE(16);
-        SVDQ_BP_CASE(20); SVDQ_BP_CASE(24); SVDQ_BP_CASE(28); SVDQ_BP_CASE(32);
+// ------------------------------------------------------------------------------------ launcher
+// Variants: up to 16 tasks the one-wave k_basis_project (svdq_project_unit.h), also for plans with exactly NTP tasks
+// (FULL) and for the walk over fp32 tensors (MODE 4, 6); above 16 tasks the two-wave k_basis_project2, except
+// N = 17..20, which take the one-wave 4x4-block k_basis_project_q (N = 21..24 measured slower with it than with the
+// two-wave kernel, 11.9 against 10.0 ms) unless SVDQ_SW_PASS2_TWO_WAVE asks for the two-wave kernel (A/B).  The walk
+// above 16 tasks is svdq_project_walk.hip's.
+int svdq_launch_basis_project(const svdq_plan *pl, const SvdqInput &in, const float *W, const int32_t *k_dev,
+                              const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart, int unit0, int nunits,
+                              int reverse, hipStream_t st) {
+    if (in.ustart && pl->ntp > 16)
+        return svdq_launch_basis_project_walk32(pl, in, W, k_dev, r_dev, basis, mean, cpart, unit0, nunits, reverse, st);
+    const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
+        using TIN = typename decltype(tin_c)::type;
+        return svdq_dispatch_int<4, 8, 12, 16, 20, 24, 28, 32>(pl->ntp, [&](auto ntp_c) {
+            constexpr int NTP = ntp_c;
+            return svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
+                constexpr bool F16 = f16_c;
+                return svdq_dispatch_int<0, 1, 2, 3, 4, 6>(in.mode(), [&](auto mode_c) {
+                    constexpr int MODE = mode_c;
+                    if constexpr ((MODE & 4) != 0 && (!std::is_same_v<TIN, float> || NTP > 16)) return false;
+                    else return svdq_dispatch_bool(pl->n_tasks == NTP, [&](auto full_c) {
+                        constexpr bool FULL = full_c;
+                        if constexpr (NTP == 20) {
+                            if (!(pl->cfg.reserved & SVDQ_SW_PASS2_TWO_WAVE)) {
+                                hipLaunchKernelGGL((k_basis_project_q<NTP, F16, MODE, FULL, TIN>), dim3(nunits), dim3(64), 0,
+                                                   st, pl->d_params, pl->d_units, in.tensors(), in.rows_dev, pl->n_tasks,
+                                                   pl->cfg.center, W, k_dev, r_dev, basis, mean, cpart, unit0, reverse,
+                                                   in.aux(), in.aux2());
+                                return true;
+                            }
+                        }
+                        if constexpr (NTP > 16)
+                            hipLaunchKernelGGL((k_basis_project2<NTP, F16, MODE, TIN>), dim3(nunits), dim3(128), 0, st,
+                                               pl->d_params, pl->d_units, in.tensors(), in.rows_dev, pl->n_tasks,
+                                               pl->cfg.center, W, k_dev, r_dev, basis, mean, cpart, unit0, reverse,
+                                               in.aux(), in.aux2());
+                        else
+                            hipLaunchKernelGGL((k_basis_project<NTP, F16, MODE, FULL, TIN>), dim3(nunits), dim3(64), 0, st,
+                                               pl->d_params, pl->d_units, in.tensors(), in.rows_dev, pl->n_tasks,
+                                               pl->cfg.center, W, k_dev, r_dev, basis, mean, cpart, unit0, reverse,
+                                               in.aux(), in.aux2(), in.ustart);
+                        return true;
+                    });
+                });
+            });
+        });
     });
-#undef SVDQ_BP_CASE
-    svdq_set_error("unsupported padded task count %d", pl->ntp);
-    return SVDQ_EUNSUPPORTED;
+    return svdq_launch_status(ok, "k_basis_project");
 }
 
 

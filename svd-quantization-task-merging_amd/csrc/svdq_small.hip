@@ -9,6 +9,7 @@
 //            (rtvq.py:4-82) -- one lane per task, n = r-k <= 31 scalars each.
 
 #include "svdq_common.h"
+#include "svdq_dispatch.h"
 #include "svdq_eig.h"
 #include <hip/hip_fp16.h>
 
@@ -237,33 +238,31 @@ __global__ __launch_bounds__(EIG_THREADS) void k_coeff(const SvdqParam *__restri
 }
 
 // ------------------------------------------------------------------------------------ launchers
-int svdq_launch_eig(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, const double *gram_part2, float *W,
-                    double *c0, uint8_t *small, int param0, int nparams, const void *idx, const void *base,
-                    const int32_t *only, int32_t *refine_out, hipStream_t st, const int64_t *ustart) {
-    if (ustart) idx = nullptr;   // walk mode: idx names mask bytes, not index lists
+int svdq_launch_eig(const svdq_plan *pl, const SvdqInput &in, const double *gram_part2, float *W, double *c0,
+                    uint8_t *small, int param0, int nparams, const int32_t *only, int32_t *refine_out, hipStream_t st) {
     // smallest sigma / sigma_0 the Gram behind gram_part2 resolves: exact-product (fp64 MFMA) sums reach the fp32
-    // resolution of the data; fp32-product sums (cfg.reserved bit 1, and N > 16 before its refinement) do not
-    const bool exact = (pl->ntp <= 16 && !(pl->cfg.reserved & 2)) || only != nullptr;
+    // resolution of the data; fp32-product sums (SVDQ_SW_GRAM_F32, and N > 16 before its refinement) do not
+    const bool exact = (pl->ntp <= 16 && !(pl->cfg.reserved & SVDQ_SW_GRAM_F32)) || only != nullptr;
     const float resolve = exact ? 1e-6f : 3e-4f;
-    auto ip = reinterpret_cast<const int32_t *const *>(idx);
-    auto bpp = reinterpret_cast<const float *const *>(base);
     const svdq_small_layout &L = pl->small;
-    auto pp = reinterpret_cast<const float *const *>(ptrs);
     float *sg = reinterpret_cast<float *>(small + L.sigma_off);
     int32_t *kk = reinterpret_cast<int32_t *>(small + L.k_off), *rr = reinterpret_cast<int32_t *>(small + L.r_off);
     float *en = reinterpret_cast<float *>(small + L.energy_off);
     int64_t *ro = reinterpret_cast<int64_t *>(small + L.rows_off);
     // the input type only changes how k_eig reads row 0 of every task (the completion column)
-    SVDQ_DISPATCH_INPUT(pl, TIN,
-        if (pl->n_tasks <= 8)
-            hipLaunchKernelGGL((k_eig<64, 8, TIN>), dim3(nparams), dim3(64), 0, st, pl->d_params, pp, rows_dev, pl->n_tasks,
-                               pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank, gram_part2, W, c0, param0, sg,
-                               kk, rr, en, ro, ip, bpp, only, refine_out, resolve, ustart);
-        else
-            hipLaunchKernelGGL((k_eig<256, 32, TIN>), dim3(nparams), dim3(256), 0, st, pl->d_params, pp, rows_dev,
-                               pl->n_tasks, pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank, gram_part2, W, c0,
-                               param0, sg, kk, rr, en, ro, ip, bpp, only, refine_out, resolve, ustart));
-    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
+    const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
+        using TIN = typename decltype(tin_c)::type;
+        return svdq_dispatch_bool(pl->n_tasks <= 8, [&](auto small_c) {
+            constexpr int THREADS = small_c ? 64 : 256, NMAX = small_c ? 8 : 32;
+            hipLaunchKernelGGL((k_eig<THREADS, NMAX, TIN>), dim3(nparams), dim3(THREADS), 0, st, pl->d_params, in.tensors(),
+                               in.rows_dev, pl->n_tasks, pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank,
+                               gram_part2, W, c0, param0, sg, kk, rr, en, ro,
+                               static_cast<const int32_t *const *>(in.index), static_cast<const float *const *>(in.base), only,
+                               refine_out, resolve, in.ustart);
+            return true;
+        });
+    });
+    return svdq_launch_status(ok, "k_eig");
 }
 
 int svdq_launch_coeff(const svdq_plan *pl, const double *cpart, const double *c0, uint8_t *small, int param0,

@@ -378,7 +378,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> compress_from_base(at::TensorList
 }
 
 // masked parameters: masks[p] = the combined mask of parameter p (bool / uint8, the parameter's shape).
-// walk = true: svdq_maskset_count_scan + _unit_starts + svdq_compress_masked (no index lists; above 16 tasks on the one-wave kernels);
+// walk = true: svdq_maskset_count_scan + _unit_starts + svdq_compress_masked (no index lists; N <= 32, the _from_base form
+// N <= 16: the walk's range is stated in include/svdq.h, svdq_compress_masked);
 // walk = false: svdq_maskset_indices + svdq_compress_gather.  rows (int64 [P], device) = mask.sum() per parameter.
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_with_masks(at::TensorList deltas, at::TensorList masks,
                                                                                int64_t n_tasks, double energy,
