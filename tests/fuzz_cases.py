@@ -3,8 +3,8 @@
 oracle_case : random (D, N, thresholds, centre, fp16, bits, stages) against the CPU oracle (the restated reference op
               sequence): singular values, rank, retained energy, reconstructions; and, free of the basis freedom,
               the span of U_high (principal angles against the reference's, where a gap makes it unique), the
-              projections on the device's own basis (fp64 on the host) and the reference quantizer on the device's
-              own c_low, bit for bit.
+              projections on the device's own basis (fp64 on the host), the reference quantizer on the device's
+              own c_low, bit for bit, and the basis and the mean row by row against the inputs (helpers.basis_rows_check).
 modes_case  : gather mode (against compacted copies), minus-base mode (against ingest + compress), both combined
               (against ingest + gather) and the mask walk must reproduce the plain path bit for bit; the masked
               consumers (svdq_merge_masked, svdq_diagnostics_masked) must reproduce merge / diagnostics of the
@@ -177,6 +177,15 @@ def oracle_case(sq, orc, dev, seed: int, c: int):
         if coarse and eo2 > limit + 1e-12:
             msgs.append(f"rms recon error vs original {eo2 ** 0.5:.3e} vs reference {er2 ** 0.5:.3e} "
                         f"(limit {limit ** 0.5:.3e})")
+    # the basis and the mean themselves, row by row against the fp32 inputs (tests/test_hip_basis_rows.py)
+    if r > 0:
+        from helpers import basis_rows_check
+        Uh, Ul, mu = plan.basis_tensors(0, k, r, D)
+        try:
+            basis_rows_check(deltas, Uh.cpu(), Ul.cpu(), mu.cpu() if mu is not None else None, sm.coef[0, :N, :r],
+                             sm.sigma[0, :r], fp16, center, what="basis rows")
+        except AssertionError as e:
+            msgs.append(str(e)[:300])
     plan.close()
     return desc, msgs
 

@@ -147,3 +147,203 @@ def diag_check_chunked(got, x, U_high, U_low, c_high, c_low, what="", chunk=1 <<
            "reconstructed_norm": math.sqrt(a2) * g}
     for key, w in want.items():
         assert abs(float(got[key]) - w) <= 2e-6 * abs(w) + tol[key] + 1e-30, (what, key, float(got[key]), w, tol[key])
+
+
+# ------------------------------------------------------------------------------------------------ basis rows
+# The constants of basis_rows_ratios that cannot be derived to the last factor.  Fitted on the REFERENCE chain on the CPU
+# (oracle.svd_basis + oracle.project: LAPACK fp32 SVD, .half(), fp32 GEMVs) over every (N, D, centre, storage, unit
+# size) of tests/test_hip_basis_rows.py -- 3 200 chains up to D = 70 001 and the four of D = 4 194 307 -- as TWICE the
+# largest value any chain needs; tools/fit_basis_rows.py regenerates the figures, DESIGN.md section 2 has the table.
+# Never tuned on the kernels.
+#   g: coefficient term of identity (a).  What the reference needs grows with D as the error of a D-term fp32 product
+#      does -- fp32 basis: 88 at D = 256, 305 at 8 193, 523 at 70 001, 7 470 at 4 194 307, i.e. 2 ... 5.51 sqrt(D), the
+#      largest at D = 256, N = 2 -- so g = BASIS_ROWS_G sqrt(D) from BASIS_ROWS_SMALL rows on.  Below, sqrt(D) means
+#      nothing (D = 4, N = 3, centred needs 24.32 = 12.16 sqrt(D)) and g is the flat BASIS_ROWS_G0.  fp16 basis: 0 up to
+#      D = 70 001 (the two u terms cover it), 3.26 sqrt(D) at D = 4 194 307 (N = 32, uncentred).
+#   c: fp32 term of identity (c).  Needed: 17.0 up to D = 70 001, 140.5 at D = 4 194 307 (N = 16: LAPACK's
+#      |U^T U - I| reaches 1.0e-5 there).  The rounding to fp16 happens to a column formed in fp32, so the term applies
+#      under both storage types; the fp16 reference alone needs none (its |U^T U - I| <= 6.3e-4 is inside the rounding part).
+#   The figures of the 4 M-row shapes move with LAPACK's blocking, i.e. with the thread count (measured with 4 threads;
+#   smaller needs have been seen with 16); those up to D = 70 001 do not.
+BASIS_ROWS_SMALL = 64
+BASIS_ROWS_G0 = {True: 0.0, False: 2 * 24.32}
+BASIS_ROWS_G = {True: 2 * 3.26, False: 2 * 5.51}
+BASIS_ROWS_C = {True: 2 * 140.5, False: 2 * 140.5}
+NULL_SIGMA = 1e-6        # sigma_j <= NULL_SIGMA sigma_0: a null direction ("Null directions")
+
+
+def basis_rows_ratios(deltas, U_high, U_low, mean, coef, sigma, fp16, center, g0=None, g=None, c=None, chunk=1 << 18):
+    """The three row-local identities of the compressor's streaming outputs, in fp64 on the host, from the original
+    fp32 inputs: ``deltas`` (N tensors of >= D elements), ``U_high [D, k]`` / ``U_low [D, r-k]`` / ``mean [D, 1] | None``
+    as stored, ``coef [N, r]`` the fp32 coefficients before rounding and ``sigma [r]`` the reported singular values.
+    Evaluated in row chunks, so host memory stays flat.  Returns error / bound ratios and what a fit needs:
+
+    (a) |T[i,t] - mean[i] - sum_j U[i,j] coef[t,j]| per ELEMENT against
+          u A_it + [fp16: 2^-25 sum_j |c_tj|]                      storage rounding of U (u = 2^-11 fp16, 2^-24 fp32)
+        + (r + N) 2^-24 (A_it + sum_t |T_it| + |mean_i|)           fp32 arithmetic of the row; A = |U| |c|^T
+        + sum_j |U_ij| (u + g 2^-24) (|U_j|^T |Tc_t|)              a coefficient on the stored column: projection of the
+                                                                   storage error + the fp32 error of a D-term product
+                                                                   (g = G0 for D < 64, G sqrt(D) from there on)
+        + sum over zero columns j of sigma64_j                     a null direction is left out by design
+        + 1e-30
+    (b) |mean[i] - mean64[i]| <= (N + 1) 2^-24 sum_t |T_it| / N
+    (c) |U^T U - I| per entry over the nonzero columns against
+          [fp16: (2u + u^2) (|U|^T |U|)_ij + 2^-25 (1 + u) (|U_i|_1 + |U_j|_1) + D 2^-50]     rounding of both factors
+        + c 2^-24 sigma_0 / min(sigma_i, sigma_j)                  a column formed in fp32
+        with sigma = the fp64 singular values of the (centred) INPUT, a null direction's nonzero column (the completion,
+        or whatever LAPACK returns there) taking the smallest real sigma.  A column is exactly zero or subject to this;
+        zero only where sigma64_j <= 2e-6 sigma64_0 and the reported sigma_j <= 1e-6 sigma_0.
+    """
+    N = len(deltas)
+    D = int(U_high.shape[0])
+    r = int(U_high.shape[1] + U_low.shape[1])
+    assert (mean is None) == (not center), "mean must be None exactly when centring is off"
+    assert U_low.shape[0] == D and all(d.numel() >= D for d in deltas)
+    C = torch.as_tensor(np.ascontiguousarray(np.asarray(coef)[:N, :r], dtype=np.float64)).reshape(N, r)
+    Ca = C.abs()
+    e32 = 2.0 ** -24
+    u = 2.0 ** -11 if fp16 else e32
+    floor = 2.0 ** -25 if fp16 else 0.0
+    if D < BASIS_ROWS_SMALL:
+        gk = BASIS_ROWS_G0[bool(fp16)] if g0 is None else g0
+    else:
+        gk = (BASIS_ROWS_G[bool(fp16)] if g is None else g) * np.sqrt(D)
+    ck = BASIS_ROWS_C[bool(fp16)] if c is None else c
+    mflat = mean.reshape(-1) if mean is not None else None
+    inf = float("inf")      # a NaN anywhere in the outputs is an error of infinite size, not a comparison that is False
+
+    def rows(lo, hi):
+        T = torch.stack([d.reshape(-1)[lo:hi] for d in deltas], dim=1).double()
+        U = torch.cat([U_high[lo:hi].double(), U_low[lo:hi].double()], dim=1)
+        mu = mflat[lo:hi].double() if center else torch.zeros(hi - lo, dtype=torch.float64)
+        return T, U, mu
+
+    # pass 1: the mean, and the column sums that (a) and (c) need
+    M = torch.zeros(r, N, dtype=torch.float64)
+    G = torch.zeros(r, r, dtype=torch.float64)
+    Ga = torch.zeros(r, r, dtype=torch.float64)
+    GT = torch.zeros(N, N, dtype=torch.float64)
+    l1 = torch.zeros(r, dtype=torch.float64)
+    out = {"b": 0.0, "b_row": -1}
+    for lo in range(0, D, chunk):
+        hi = min(lo + chunk, D)
+        T, U, mu = rows(lo, hi)
+        m64 = T.mean(dim=1) if center else torch.zeros(hi - lo, dtype=torch.float64)
+        if center:
+            rb = ((mu - m64).abs() / ((N + 1) * e32 * T.abs().sum(dim=1) / N + 1e-30)).nan_to_num(nan=inf)
+            i = int(rb.argmax())
+            if float(rb[i]) > out["b"]:
+                out["b"], out["b_row"] = float(rb[i]), lo + i
+        Ua = U.abs()
+        M += Ua.T @ (T - mu[:, None]).abs()
+        G += U.T @ U
+        Ga += Ua.T @ Ua
+        l1 += Ua.sum(dim=0)
+        Tc = T - m64[:, None]
+        GT += Tc.T @ Tc
+    if D <= chunk:
+        T = rows(0, D)[0]
+        S64 = torch.linalg.svdvals(T - T.mean(dim=1, keepdim=True) if center else T)
+    else:      # sigma >= 1e-6 sigma_0 from an fp64 Gram: 1e-16 sigma_0^2 / sigma^2 <= 1e-4 relative
+        S64 = torch.linalg.eigvalsh(GT).flip(0).clamp_min(0.0).sqrt()
+    S64 = S64[:r].numpy().copy()
+    out["S64"] = S64
+    s0 = float(S64[0]) if r else 0.0
+    zero = (l1 == 0).numpy()
+    sg = np.asarray(sigma, dtype=np.float64).reshape(-1)[:r]
+    for j in np.nonzero(zero)[0]:
+        assert S64[j] <= 2 * NULL_SIGMA * s0 and sg[j] <= NULL_SIGMA * sg[0], \
+            f"column {j} is zero but sigma64 = {S64[j]:.3e} (sigma64_0 = {s0:.3e}), reported {sg[j]:.3e}"
+    null = float(S64[zero].sum())
+
+    # (c); an all-zero input (sigma_0 = 0) has no direction to hold orthonormal: every column may be zero or the completion
+    out.update({"c": 0.0, "c_need": 0.0, "c_at": (-1, -1), "c_err": 0.0})
+    nz = np.nonzero(~zero)[0]
+    real = S64 > NULL_SIGMA * s0
+    if s0 > 0 and nz.size and real.any():
+        se = np.maximum(S64, S64[real].min())[nz]
+        idx = torch.as_tensor(nz)
+        err = (G[idx][:, idx] - torch.eye(nz.size, dtype=torch.float64)).abs().numpy()
+        b16 = np.zeros_like(err)
+        if fp16:
+            l = l1[idx].numpy()
+            b16 = (2 * u + u * u) * Ga[idx][:, idx].numpy() + floor * (1 + u) * (l[:, None] + l[None, :]) + D * floor ** 2
+        b32 = e32 * s0 / np.minimum.outer(se, se)
+        rc = np.nan_to_num(err / (b16 + ck * b32 + 1e-300), nan=inf)
+        a = np.unravel_index(int(rc.argmax()), rc.shape)
+        out.update({"c": float(rc[a]), "c_at": (int(nz[a[0]]), int(nz[a[1]])), "c_err": float(err.max()),
+                    "c_need": float(np.maximum((err - b16) / b32, 0.0).max())})
+
+    # pass 2: (a)
+    out.update({"a": 0.0, "a0": 0.0, "a_need": 0.0, "a_at": (-1, -1), "a_err": 0.0, "a_tol": 0.0})
+    for lo in range(0, D, chunk):
+        hi = min(lo + chunk, D)
+        T, U, mu = rows(lo, hi)
+        Ua = U.abs()
+        E = (T - mu[:, None] - U @ C.T).abs()
+        A = Ua @ Ca.T
+        L = (u * A + floor * Ca.sum(dim=1)[None, :]
+             + (r + N) * e32 * (A + T.abs().sum(dim=1, keepdim=True) + mu.abs()[:, None])
+             + u * (Ua @ M) + null + 1e-30)
+        Cg = e32 * (Ua @ M)
+        ra = (E / (L + gk * Cg)).nan_to_num(nan=inf)
+        i = int(ra.argmax())
+        if float(ra.reshape(-1)[i]) > out["a"]:
+            out.update({"a": float(ra.reshape(-1)[i]), "a_at": (lo + i // N, i % N), "a_err": float(E.reshape(-1)[i]),
+                        "a_tol": float((L + gk * Cg).reshape(-1)[i])})
+        out["a0"] = max(out["a0"], float((E / L).max()))      # without the g term
+        need = ((E - L).clamp_min(0.0) / (Cg + 1e-300)).max()
+        out["a_need"] = max(out["a_need"], float(need))
+    return out
+
+
+def basis_rows_assert(s, what=""):
+    """The verdict on what basis_rows_ratios returned: each identity's largest error / bound is at most 1."""
+    assert s["b"] <= 1.0, (what, "(b) mean", "row", s["b_row"], "error / bound", s["b"])
+    assert s["a"] <= 1.0, (what, "(a) row identity", "row, task", s["a_at"], "error", s["a_err"], "bound", s["a_tol"],
+                           "error / bound", s["a"])
+    assert s["c"] <= 1.0, (what, "(c) orthonormality", "columns", s["c_at"], "max error", s["c_err"], "error / bound", s["c"])
+
+
+def basis_rows_check(deltas, U_high, U_low, mean, coef, sigma, fp16, center, what="", chunk=1 << 18):
+    """Asserts the three identities of basis_rows_ratios with the committed constants; returns the ratios."""
+    s = basis_rows_ratios(deltas, U_high, U_low, mean, coef, sigma, fp16, center, chunk=chunk)
+    basis_rows_assert(s, what)
+    return s
+
+
+BASIS_ROWS_N = [1, 2, 3, 4, 5, 7, 8, 9, 12, 13, 16, 17, 19, 20, 21, 24, 27, 28, 31, 32]
+BASIS_ROWS_LARGE = [(4 * 2 ** 20 + 3, 8, True, True), (4 * 2 ** 20 + 3, 16, False, True), (4 * 2 ** 20 + 3, 20, True, True),
+                    (4 * 2 ** 20 + 3, 32, True, False)]      # (D, N, fp16, center)
+
+
+def basis_rows_sizes(N):
+    """The parameter sizes of one plan: around the task count, the 64-row wave tile, the 256-row block, the 1024- /
+    4096- / 8192-row units, several units with a partial last block, and one of many units with an odd tail."""
+    return [D for D in (1, 2, N - 1, N, N + 1, 63, 64, 65, 255, 256, 257, 1023, 1025, 4095, 4096, 4097, 8191, 8193,
+                        3 * 8192 + 255, 70001) if D > 0]
+
+
+def basis_rows_inputs(orc, D, N, unit_rows=0):
+    """``synthetic_deltas`` (seeded per (N, D)) plus a spike, different for every task and boundary, at the first and
+    last rows of the 64-row tile, the 256-row block and the unit, and at the tensor's last row: those rows differ from
+    their neighbours by several times the data (1e-2), so one written to the wrong place cannot pass for its neighbour."""
+    ds = [d.clone() for d in orc.synthetic_deltas(D, N, 7919 * N + D, rank=min(3, N))]
+    ur = unit_rows or (8192 if N > 16 else 4096)
+    for q, row in enumerate((0, 63, 64, 255, 256, ur - 1, ur, D - 1)):
+        if 0 <= row < D:
+            for t, d in enumerate(ds):
+                d[row] += (0.05 + 0.01 * t + 0.003 * q) * (-1.0 if (q + t) % 3 == 0 else 1.0)
+    return ds
+
+
+def reference_chain(orc, deltas, center, fp16):
+    """What the kernels replace, on the CPU: LAPACK fp32 SVD, the ``.half()`` cast, fp32 GEMVs against the cast basis.
+    Returns (U_high, U_low, mean, coef [N, r], sigma [r])."""
+    b = orc.svd_basis(deltas, 0.9, None, center, fp16)
+    mean = b["mean"]
+    coef = []
+    for d in deltas:
+        ch, cl = orc.project(d if mean is None else d - mean.squeeze(1), b["U_high"], b["U_low"])
+        coef.append(torch.cat([ch, cl]).numpy())
+    return b["U_high"], b["U_low"], mean, np.stack(coef), b["singular_values"].numpy()

@@ -457,22 +457,36 @@ def test_single_task_and_all_zero_inputs(sq, orc):
 
 
 # ------------------------------------------------------------------------------- oracle at larger sizes
-@pytest.mark.parametrize("D,N,seed,thr,bits,stages", [
-    (589824, 8, 31, 0.90, 4, 2),       # one ViT-B 768x768 matrix
-    (1000003, 8, 32, 0.95, 4, 4),      # odd length: tail block + unaligned tails
-    (262144, 20, 33, 0.90, 8, 2),      # N = 20: two 16-slot MFMA blocks
-    (300000, 2, 34, 0.90, 4, 2),       # N = 2 (padded to 4 task slots)
-    (70001, 13, 35, 0.99, 2, 2),       # N = 13 (padded to 16)
-    (40000, 32, 36, 0.90, 4, 2),       # N = 32 (max)
-    (90001, 18, 37, 0.90, 4, 2),       # N = 18: padded to 20, BB block on the vector ALU with two empty slots
-    (50000, 17, 38, 0.95, 4, 2),       # N = 17: a single task beyond the first 16-slot block
+def _seeded(D, N, seed, thr, bits, stages, center=True, fp16=True):
+    ident = f"{D}-{N}-{seed}-{thr}-{bits}-{stages}" + ("" if center and fp16 else f"-center{int(center)}-fp16{int(fp16)}")
+    return pytest.param(D, N, seed, thr, bits, stages, center, fp16, id=ident)
+
+
+@pytest.mark.parametrize("D,N,seed,thr,bits,stages,center,fp16", [
+    _seeded(589824, 8, 31, 0.90, 4, 2),       # one ViT-B 768x768 matrix
+    _seeded(1000003, 8, 32, 0.95, 4, 4),      # odd length: tail block + unaligned tails
+    _seeded(262144, 20, 33, 0.90, 8, 2),      # N = 20: two 16-slot MFMA blocks
+    _seeded(300000, 2, 34, 0.90, 4, 2),       # N = 2 (padded to 4 task slots)
+    _seeded(70001, 13, 35, 0.99, 2, 2),       # N = 13 (padded to 16)
+    _seeded(40000, 32, 36, 0.90, 4, 2),       # N = 32 (max)
+    _seeded(90001, 18, 37, 0.90, 4, 2),       # N = 18: padded to 20, BB block on the vector ALU with two empty slots
+    _seeded(50000, 17, 38, 0.95, 4, 2),       # N = 17: a single task beyond the first 16-slot block
+    _seeded(300001, 8, 39, 0.90, 4, 2, center=False),        # uncentred and
+    _seeded(300001, 8, 40, 0.90, 4, 2, fp16=False),          # fp32-basis store paths at a real size
+    _seeded(262147, 20, 41, 0.90, 4, 2, center=False),
+    _seeded(262147, 20, 42, 0.90, 4, 2, fp16=False),
+    _seeded(150001, 12, 43, 0.90, 4, 2),      # N == NTP ("FULL" kernel variants) that no other seeded case selects
+    _seeded(150001, 16, 44, 0.90, 4, 2),
+    _seeded(100003, 24, 45, 0.90, 4, 2),
+    _seeded(100003, 28, 46, 0.90, 4, 2),
 ])
-def test_against_oracle_seeded(sq, orc, D, N, seed, thr, bits, stages):
+def test_against_oracle_seeded(sq, orc, D, N, seed, thr, bits, stages, center, fp16):
+    from helpers import basis_rows_check
     deltas = orc.synthetic_deltas(D, N, seed, rank=min(3, N))
-    ref = orc.compress_parameter(deltas, thr, 64, True, True, bits, stages)
+    ref = orc.compress_parameter(deltas, thr, 64, center, fp16, bits, stages)
     dev = torch.device("cuda", 0)
-    plan, sm = sq.compress_batch([[d.to(dev) for d in deltas]], energy_threshold=thr, max_rank=64, center=True,
-                                 fp16=True, low_bits=bits, rtvq_stages=stages, device=dev)
+    plan, sm = sq.compress_batch([[d.to(dev) for d in deltas]], energy_threshold=thr, max_rank=64, center=center,
+                                 fp16=fp16, low_bits=bits, rtvq_stages=stages, device=dev)
     k, r = int(sm.k[0]), int(sm.r[0])
     S_ref = ref["basis"]["singular_values"].numpy()
     assert k == ref["basis"]["k"]
@@ -490,6 +504,10 @@ def test_against_oracle_seeded(sq, orc, D, N, seed, thr, bits, stages):
         assert np.all(rel <= 3.0 * rel_ref + 1e-3) and rel.mean() <= 1.3 * rel_ref.mean() + 1e-3
     elif r - k == 1:  # F4: the reference itself produces NaN for this input; so must we
         assert not np.isfinite(recon).any() and not np.isfinite(ref_recon).any()
+    # the basis and the mean themselves, row by row (tests/test_hip_basis_rows.py)
+    U_high, U_low, mean = plan.basis_tensors(0, k, r, D)
+    basis_rows_check(deltas, U_high.cpu(), U_low.cpu(), mean.cpu() if center else None, sm.coef[0, :N, :r],
+                     sm.sigma[0, :r], fp16, center, what=f"seeded D={D} N={N} center={center} fp16={fp16}")
 
 
 def test_batch_of_ragged_parameters_matches_single_runs(sq, orc):
