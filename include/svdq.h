@@ -182,6 +182,32 @@ int svdq_coeff_quantize_range(const svdq_plan *plan, void *workspace_dev, void *
 int svdq_task_gram(const svdq_plan *plan, const void *delta_ptrs, const int64_t *rows_dev, void *workspace,
                    double *out_gram, void *stream);
 
+/* The same Gram as a by-product of pass 1 (the one statement of the contract; the sources point here).  The
+ * reference's clustering (flatten_task_vectors clustering.py:55-120, cluster_tasks :198-245,
+ * compute_cluster_statistics :263-316) needs only the N x N inner products of the concatenated task vectors, and
+ * pass 1 of the compressor reads every task vector anyway.
+ *   svdq_plan_set_task_gram(plan, enable): call before svdq_plan_sizes.  It may enlarge workspace_bytes (N + 1 side
+ *     sums per work unit and their reduced form) and changes nothing else: sizes, small layout, basis layout and the
+ *     unit table stay, and every artifact of the plan (small buffer, basis, mean) is byte-identical to that of the
+ *     same plan without the by-product.  A plan that does not enable it runs exactly the kernels it ran before.
+ *   svdq_plan_task_gram(plan, workspace, out_gram, stream): valid once pass 1 and the eigen stage of ALL parameters
+ *     of the plan have been enqueued on `workspace` -- after svdq_compress, svdq_compress_from_base, or
+ *     svdq_gram_center[_range] + svdq_eig_rank_select[_range] covering every parameter; before or after pass 2.
+ *     Writes out_gram[N*N] (device, fp64, row-major, plan task order) = sum over the plan's parameters of T_p^T T_p
+ *     over the rows processed (rows_dev respected; from-base plans: T = finetuned - base), i.e. what svdq_task_gram
+ *     returns for the same tensors, without reading them again.  Asynchronous on `stream`, no host copy, capturable.
+ *     center == 0: the total of the Gram partials pass 1 left, the very sums of svdq_task_gram (bit-equal to it for
+ *     N <= 16 with the default switches).  center == 1: with m the row mean that was subtracted and Tc the centred rows,
+ *     T^T T = Tc^T Tc + a 1^T + 1 a^T + s 1 1^T, a = Tc^T m, s = m^T m; pass 1 sums a and s beside the Gram (fp32 over
+ *     four rows, fp64 beyond) and the correction is applied on the device in fp64 in a fixed order.  The result is
+ *     exactly symmetric and the same bits in every run.
+ *   Covered: plain deltas and from-base plans, fp32 / fp16 / bf16 inputs, N = 1..32.  Not covered: the masked routes --
+ *     on a plan with the by-product enabled svdq_compress_gather[_from_base] and svdq_compress_masked[_from_base]
+ *     return SVDQ_EUNSUPPORTED (their Gram would be over the selected rows only; the reference clusters on the
+ *     unmasked vectors).  svdq_plan_task_gram on a plan that did not enable it: SVDQ_EINVAL. */
+int svdq_plan_set_task_gram(svdq_plan *plan, int32_t enable);
+int svdq_plan_task_gram(const svdq_plan *plan, void *workspace_dev, double *out_gram_dev, void *stream);
+
 /* svdq_compress for MASKED parameters without a compaction pass (replaces the 2*N boolean-index gathers per
  * parameter of cli.py:333 / compress.py:144, i.e. apply_mask_to_tensor mask_loader.py:651-679 feeding
  * construct_masked_basis and compress_masked_regions): delta_ptrs name the original full-size tensors,

@@ -61,6 +61,8 @@ SIGNATURES = {
                                            c_int32, c_int32, c_void_p]),
     "svdq_coeff_quantize_range": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "svdq_task_gram": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "svdq_plan_set_task_gram": (c_int32, [c_void_p, c_int32]),
+    "svdq_plan_task_gram": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "svdq_ingest": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svdq_tvq_work_bytes": (c_int64, [c_void_p]),
     "svdq_tvq_quantize": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

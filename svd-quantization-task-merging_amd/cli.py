@@ -8,7 +8,8 @@ HIP entry points of this package:
   Step 1  load_task_vectors           one subtraction pass for all tasks (svdq_ingest)
   Step 2  load_task_masks + combine_masks   batched mask combine (svdq_maskset_combine)
   Step 4+5 run_basis_and_compress     the hot path: six kernel launches for the whole model (svdq_compress)
-  Step 6  compute_weights / cluster_tasks   N x N task Gram on the GPU (svdq_task_gram)
+  Step 6  compute_weights / cluster_tasks   N x N task Gram: a by-product of Step 4's first pass (svdq_plan_task_gram);
+                                      masked parameters add one pass over their unmasked deltas (svdq_task_gram)
   Step 7  merge_all_parameters / merge_with_clustering, apply_merged_deltas (svdq_reconstruct, svdq_mask_expand)
   Step 8  compute_all_diagnostics     fused reconstruction error (svdq_recon_error)
 
@@ -54,10 +55,12 @@ def run_svd_hybrid_pipeline(config: SVDHybridConfig) -> Dict:
     base_state_dict = load_checkpoint(config.base_model_path, device="cpu")
     paths = get_task_checkpoint_paths(config.checkpoint_dir, config.tasks)
     has_masks = bool(config.mask_dir) and os.path.exists(config.mask_dir)
-    # Nothing downstream needs the task vectors themselves when there is no clustering and no reconstruction
-    # diagnostics: then finetuned - base is formed inside the two streaming passes (svdq_compress_from_base; masked
-    # parameters through svdq_compress_gather_from_base) and the deltas are never materialised.
-    from_checkpoints = config.svd_weighting != "cluster" and not config.svd_eval_reconstruction
+    # Nothing downstream needs the task vectors themselves when there are no reconstruction diagnostics: then
+    # finetuned - base is formed inside the two streaming passes (svdq_compress_from_base; masked parameters through
+    # svdq_compress_gather_from_base) and the deltas are never materialised.  Clustering takes the task Gram the
+    # compressor's first pass leaves behind; only masked parameters are not in it (the reference clusters on their
+    # unmasked vectors), so a cluster-weighted run with masks still forms the task vectors.
+    from_checkpoints = not config.svd_eval_reconstruction and (config.svd_weighting != "cluster" or not has_masks)
     if from_checkpoints:
         float_base = {k: v for k, v in base_state_dict.items() if isinstance(v, torch.Tensor) and v.is_floating_point()}
         task_vectors = {}
@@ -104,7 +107,9 @@ def run_svd_hybrid_pipeline(config: SVDHybridConfig) -> Dict:
     print(f"[6/8] weights ({config.svd_weighting})")
     cluster_assignments = None
     if config.svd_weighting == "cluster":
-        cluster_assignments = cluster_tasks(task_vectors, config.svd_cluster_k, method="kmeans", device=device)
+        names_only = {t: {} for t in task_vectors} if from_checkpoints else task_vectors
+        cluster_assignments = cluster_tasks(names_only, config.svd_cluster_k, method="kmeans", device=device,
+                                            bases=bases)
         for cid, members in get_cluster_members(cluster_assignments).items():
             print(f"      cluster {cid}: {members}")
     weights = compute_weights(config.tasks, weighting_strategy=config.svd_weighting,

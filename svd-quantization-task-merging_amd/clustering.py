@@ -21,9 +21,46 @@ import torch
 from .pipeline import CompressPlan, native_input_dtype, prepare_input, resolve_device
 
 
+def scatter_task_gram(total: np.ndarray, gram: np.ndarray, present: List[str], tasks: List[str]) -> None:
+    """Add one plan's Gram (rows / columns = the tasks in ``present``, the plan's task order) into the run's N x N
+    matrix ``total`` (rows / columns = ``tasks``).  A task the plan's parameters lack counts as zeros for them
+    (flatten_task_vectors), i.e. its rows and columns get nothing."""
+    pos = {t: i for i, t in enumerate(tasks)}
+    idx = np.array([pos[t] for t in present], dtype=np.int64)
+    total[np.ix_(idx, idx)] += np.asarray(gram, dtype=np.float64).reshape(len(present), len(present))
+
+
+def recorded_task_gram(bases, tasks: List[str]):
+    """The task Gram that the plans behind ``bases`` (driver.build_bases with the by-product enabled) recorded as they
+    ran: (G [N, N] fp64 in the order of ``tasks``, the set of parameter names it covers), or None when nothing was
+    recorded or a recorded task is not in ``tasks``."""
+    seen, records = set(), []
+    for b in (bases or {}).values():
+        art = b.get("masked") if isinstance(b, dict) else None
+        batch = getattr(art, "_batch", None)
+        rec = getattr(batch[0], "task_gram", None) if batch is not None else None
+        if rec is not None and id(batch[0]) not in seen:
+            seen.add(id(batch[0]))
+            records.append(rec)
+    if not records or any(t not in tasks for r in records for t in r["tasks"]):
+        return None
+    G = np.zeros((len(tasks), len(tasks)), dtype=np.float64)
+    covered = set()
+    for r in records:
+        gram = r["gram"]
+        scatter_task_gram(G, gram.cpu().numpy() if isinstance(gram, torch.Tensor) else gram, r["tasks"], tasks)
+        covered.update(r["names"])
+    return G, covered
+
+
 def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *, process_group=None,
-              ) -> Tuple[np.ndarray, List[str]]:
+              bases=None) -> Tuple[np.ndarray, List[str]]:
     """N x N inner products (fp64, host) of the flattened task vectors, tasks in sorted order.
+
+    ``bases`` (from driver.build_bases / run_basis_and_compress[_from_checkpoints] with the task-Gram by-product, the
+    default of a cluster-weighted config): the Gram its plans recorded while compressing is taken as it is, and only the
+    parameters it does not cover (the masked ones, here in full, unmasked form) are read -- in the common case none,
+    and then ``task_vectors`` only has to name the tasks.
 
     Same row/column conventions as flatten_task_vectors (clustering.py:55-120): tasks sorted by name,
     parameters the union over tasks, a parameter a task lacks counts as zeros.  With ``process_group``
@@ -34,6 +71,9 @@ def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *
     names = sorted({n for tv in task_vectors.values() for n in tv.keys()})
     N = len(tasks)
     vectors, rows = [], []
+    recorded = recorded_task_gram(bases, tasks) if bases is not None else None
+    if recorded is not None:
+        names = [n for n in names if n not in recorded[1]]
     # one plan for the whole model: all fp16 / all bf16 task tensors are read as they are, any mix as fp32 copies
     idt = native_input_dtype(tv[n] for tv in task_vectors.values() for n in tv.keys())
     with torch.cuda.device(dev):
@@ -54,6 +94,8 @@ def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *
             G = plan.task_gram(plan.pointer_table(vectors))
         else:
             G = torch.zeros((N, N), dtype=torch.float64, device=dev)
+        if recorded is not None:
+            G = G + torch.from_numpy(recorded[0]).to(dev)
         if process_group is not None:
             from .shard import all_reduce_gram
             all_reduce_gram(G, None if process_group is True else process_group)
@@ -119,11 +161,11 @@ def cluster_from_gram(G: np.ndarray, task_names: List[str], k: int, method: str 
 
 
 def cluster_tasks(task_vectors: Dict[str, Dict[str, torch.Tensor]], k: int, method: str = "kmeans",
-                  device="cuda", process_group=None) -> Dict[str, int]:
+                  device="cuda", process_group=None, bases=None) -> Dict[str, int]:
     """clustering.py:198-245: unit-normalised task vectors -> k-means / Ward labels per task name."""
     if method not in ("kmeans", "hierarchical"):
         raise ValueError(f"Unknown clustering method: {method}")
-    G, tasks = task_gram(task_vectors, device, process_group=process_group)
+    G, tasks = task_gram(task_vectors, device, process_group=process_group, bases=bases)
     return cluster_from_gram(G, tasks, k, method)
 
 
@@ -153,9 +195,9 @@ def cluster_statistics_from_gram(G: np.ndarray, task_names: List[str], cluster_a
 
 
 def compute_cluster_statistics(task_vectors: Dict[str, Dict[str, torch.Tensor]], cluster_assignments: Dict[str, int],
-                               device="cuda", process_group=None) -> Dict[int, Dict]:
+                               device="cuda", process_group=None, bases=None) -> Dict[int, Dict]:
     """clustering.py:278-316 (distances of the UN-normalised task vectors to their cluster centroid)."""
-    G, tasks = task_gram(task_vectors, device, process_group=process_group)
+    G, tasks = task_gram(task_vectors, device, process_group=process_group, bases=bases)
     return cluster_statistics_from_gram(G, tasks, cluster_assignments)
 
 

@@ -147,6 +147,7 @@ extern "C" int svdq_plan_create(svdq_plan **out, int32_t n_tasks, int32_t n_para
     pl->ws_flag_off = off;
     off += svdq_align_up((int64_t)n_params * 4, 256);                 // N > 16: parameters that need the fp64 Gram pass
     pl->sizes.workspace_bytes = off;
+    pl->ws_base_bytes = off;
     pl->sizes.basis_bytes = basis_bytes;
     pl->sizes.mean_floats = mean_floats;
     pl->sizes.n_units = pl->n_units;
@@ -226,6 +227,25 @@ extern "C" int svdq_plan_set_input_type(svdq_plan *pl, int32_t type) {
         return SVDQ_EINVAL;
     }
     pl->in_type = type;
+    return SVDQ_OK;
+}
+
+// include/svdq.h, svdq_plan_task_gram: the side sums get a region of their own behind everything else
+extern "C" int svdq_plan_set_task_gram(svdq_plan *pl, int32_t enable) {
+    if (!pl) {
+        svdq_set_error("svdq_plan_set_task_gram: null argument");
+        return SVDQ_EINVAL;
+    }
+    pl->task_gram = enable ? 1 : 0;
+    int64_t off = pl->ws_base_bytes;
+    if (pl->task_gram) {
+        const int64_t ns = pl->n_tasks + 1;
+        pl->ws_side_off = off;
+        off += svdq_align_up((int64_t)pl->n_units * ns * 8, 256);
+        pl->ws_side2_off = off;
+        off += svdq_align_up((int64_t)pl->n_params * SVDQ_RC * ns * 8, 256);
+    }
+    pl->sizes.workspace_bytes = off;
     return SVDQ_OK;
 }
 
@@ -317,8 +337,13 @@ static int gram_range(const svdq_plan *pl, const SvdqInput &in, void *workspace,
     // N <= 16: exact products on the fp64 MFMA (pass 1 stays HBM-bound); N > 16: fp32 products first, the fp64 pass only
     // for the parameters the eigen-stage flags (eig_range).  SVDQ_SW_GRAM_F32 keeps fp32 products throughout (A/B).
     const int f64 = (pl->ntp <= 16 && !(pl->cfg.reserved & SVDQ_SW_GRAM_F32)) ? 1 : 0;
+    // task-Gram by-product: a centred plan sums a = Tc^T m and s = m^T m beside the Gram (k_gram_side); an uncentred
+    // plan's Gram partials are what svdq_plan_task_gram totals, so it runs k_gram as it is
+    double *side = (pl->task_gram && pl->cfg.center)
+                       ? reinterpret_cast<double *>(ws(workspace, pl->ws_side_off))
+                       : nullptr;
     return svdq_launch_gram(pl, in, reinterpret_cast<double *>(ws(workspace, pl->ws_gram_off)), u0, nu, pl->cfg.center,
-                            f64, nullptr, (hipStream_t)stream);
+                            f64, nullptr, (hipStream_t)stream, side);
 }
 
 extern "C" int svdq_gram_center_range(const svdq_plan *pl, const void *ptrs, const int64_t *rows_dev, void *workspace,
@@ -342,6 +367,33 @@ extern "C" int svdq_task_gram(const svdq_plan *pl, const void *ptrs, const int64
     if (int rc = svdq_launch_gram(pl, in, part, 0, pl->n_units, /*center=*/0, pl->ntp <= 16, nullptr, st)) return rc;
     if (int rc = svdq_launch_reduce(pl, part, part2, 0, pl->n_params, nullptr, st)) return rc;
     return svdq_launch_gram_total(pl, part2, out_gram, st);
+}
+
+extern "C" int svdq_plan_task_gram(const svdq_plan *pl, void *workspace, double *out_gram, void *stream) {
+    if (!pl || !workspace || !out_gram) {
+        svdq_set_error("svdq_plan_task_gram: null argument");
+        return SVDQ_EINVAL;
+    }
+    if (!pl->task_gram) {
+        svdq_set_error("svdq_plan_task_gram: the plan did not enable the by-product (svdq_plan_set_task_gram before "
+                       "svdq_plan_sizes)");
+        return SVDQ_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const double *part2 = reinterpret_cast<const double *>(ws(workspace, pl->ws_gram2_off));
+    if (!pl->cfg.center) return svdq_launch_gram_total(pl, part2, out_gram, st);
+    double *side = reinterpret_cast<double *>(ws(workspace, pl->ws_side_off));
+    double *side2 = reinterpret_cast<double *>(ws(workspace, pl->ws_side2_off));
+    if (int rc = svdq_launch_reduce_side(pl, side, side2, st)) return rc;
+    return svdq_launch_gram_total_side(pl, part2, side2, out_gram, st);
+}
+
+// the masked routes on a by-product plan (include/svdq.h, svdq_plan_task_gram)
+static int refuse_task_gram(const svdq_plan *pl, const char *who) {
+    if (!pl || !pl->task_gram) return SVDQ_OK;
+    svdq_set_error("%s: the plan has the task-Gram by-product enabled (svdq_plan_set_task_gram), which covers plain "
+                   "and from-base plans only", who);
+    return SVDQ_EUNSUPPORTED;
 }
 
 static int eig_range(const svdq_plan *pl, const SvdqInput &in, void *workspace, void *small, int32_t param0,
@@ -483,6 +535,7 @@ extern "C" int svdq_compress_gather(const svdq_plan *pl, const void *ptrs, const
     SvdqInput in = plain_input(ptrs, rows_dev);
     in.index = index_ptrs;
     if (int rc = svdq_check_input(pl, in, 1, "svdq_compress_gather")) return rc;
+    if (int rc = refuse_task_gram(pl, "svdq_compress_gather")) return rc;
     return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
@@ -509,6 +562,7 @@ extern "C" int svdq_compress_gather_from_base(const svdq_plan *pl, const void *f
     in.index = index_ptrs;
     in.base = base_ptrs;
     if (int rc = svdq_check_input(pl, in, 3, "svdq_compress_gather_from_base")) return rc;
+    if (int rc = refuse_task_gram(pl, "svdq_compress_gather_from_base")) return rc;
     return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
@@ -527,6 +581,7 @@ extern "C" int svdq_compress_masked(const svdq_plan *pl, const void *ptrs, const
     in.mask = mask_ptrs;
     in.ustart = unit_start;
     if (int rc = svdq_check_input(pl, in, 4, "svdq_compress_masked")) return rc;
+    if (int rc = refuse_task_gram(pl, "svdq_compress_masked")) return rc;
     return compress_step(pl, in, workspace, small, basis, mean, stream);
 }
 
@@ -540,5 +595,6 @@ extern "C" int svdq_compress_masked_from_base(const svdq_plan *pl, const void *f
     in.ustart = unit_start;
     in.base = base_ptrs;
     if (int rc = svdq_check_input(pl, in, 6, "svdq_compress_masked_from_base")) return rc;
+    if (int rc = refuse_task_gram(pl, "svdq_compress_masked_from_base")) return rc;
     return compress_step(pl, in, workspace, small, basis, mean, stream);
 }

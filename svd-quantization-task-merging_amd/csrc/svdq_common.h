@@ -51,6 +51,10 @@ struct svdq_plan {
     SvdqUnit *d_units;
     int32_t *d_bits;  // optional per-parameter low_bits (svdq_plan_set_low_bits), NULL = cfg.low_bits everywhere
     int32_t in_type;  // SVDQ_INPUT_*: element type of the task / fine-tuned / base tensors (svdq_plan_set_input_type)
+    // task-Gram by-product (svdq_plan_set_task_gram): pass 1 also leaves the side sums a = Tc^T m, s = m^T m
+    int32_t task_gram;
+    int64_t ws_base_bytes;              // workspace_bytes without the by-product's regions
+    int64_t ws_side_off, ws_side2_off;  // [n_units][N + 1] unit partials, [n_params * SVDQ_RC][N + 1] (k_reduce_side)
 };
 
 __host__ __device__ static inline int64_t svdq_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
@@ -95,8 +99,13 @@ int svdq_launch_status(bool launched, const char *kernel);
 // only: NULL, or a device table [n_params] of int32 -- parameters whose entry is 0 are skipped (refinement pass)
 // f64: accumulate the products with v_mfma_f64_16x16x4_f64 (exact) instead of fp32 MFMA
 int svdq_launch_gram(const svdq_plan *pl, const SvdqInput &in, double *gram_part, int unit0, int nunits, int center,
-                     int f64, const int32_t *only, hipStream_t st);
+                     int f64, const int32_t *only, hipStream_t st, double *side_part = nullptr);
 int svdq_launch_gram_total(const svdq_plan *pl, const double *part2, double *out, hipStream_t st);
+// task-Gram by-product: the unit side partials -> SVDQ_RC chunks per parameter (k_reduce's order), and
+// out = total(part2) + a 1^T + 1 a^T + s 1 1^T with a, s the totals of side2
+int svdq_launch_reduce_side(const svdq_plan *pl, const double *side, double *side2, hipStream_t st);
+int svdq_launch_gram_total_side(const svdq_plan *pl, const double *part2, const double *side2, double *out,
+                                hipStream_t st);
 // reverse: the unit order switches (SVDQ_SW_REVERSE | SVDQ_SW_XCD_CHUNKED) of cfg.reserved
 int svdq_launch_basis_project(const svdq_plan *pl, const SvdqInput &in, const float *W, const int32_t *k_dev,
                               const int32_t *r_dev, uint8_t *basis, float *mean, double *cpart, int unit0, int nunits,

@@ -12,7 +12,33 @@
 // (fp32 sums inside a 256-row block) only reaches ~1e-3..1e-4 sigma_0.  Pass 1 is HBM-bound for N <= 16, so the fp64
 // form is the default there; N > 16 would become MFMA-bound and keeps fp32 products.
 // TIN: element type of the task / base tensors (svdq_input.h), widened to fp32 by the loaders; float for the walk.
-template <int NTP, int MODE = 0, bool F64 = false, bool FULL = false, typename TIN = float>
+// SIDE (MODE 0 / 2 only; the task-Gram by-product, svdq_plan_task_gram): beside the Gram of the centred rows Tc the
+// unit sums a[t] = sum_rows Tc[row][t] m[row] and s = sum_rows m[row]^2 (m = the row mean that was subtracted), from
+// which T^T T = Tc^T Tc + a 1^T + 1 a^T + s 1 1^T.  fp32 inside a block: an explicit fma chain over the lane's four
+// rows (so every instantiation rounds alike), then the 64 lane values of one sum at a time meet in side_wave_sum
+// (fixed order) and lane i keeps sum i, which it carries in fp64 across the blocks of the unit -- a handful of
+// registers, where N + 1 fp64 lane accumulators, and a reduce-scatter of all N + 1 lane values at once, cost the
+// N <= 8 and N <= 16 kernels their launch bounds (spills) and N = 20 its second wave.
+// side_part[unit][NT + 1].  The strip in LDS, the MFMA phase and the Gram partials are those of the SIDE = false
+// kernel, bit for bit.
+// Sum of x over the 64 lanes, the same bits in every lane: inside a row of 16 lanes four DPP adds (lane ^ 1, lane ^ 2,
+// the mirror of the half row, the mirror of the row: both lanes of a pair add the same two numbers), across the four
+// rows two shuffles.  In place: one value at a time needs one register.
+template <int CTRL>
+__device__ __forceinline__ float side_dpp_add(float x) {
+    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float side_wave_sum(float x) {
+    x = side_dpp_add<0xB1>(x);    // quad_perm [1, 0, 3, 2]
+    x = side_dpp_add<0x4E>(x);    // quad_perm [2, 3, 0, 1]
+    x = side_dpp_add<0x141>(x);   // row_half_mirror
+    x = side_dpp_add<0x140>(x);   // row_mirror
+    x += __shfl_xor(x, 16);
+    x += __shfl_xor(x, 32);
+    return x;
+}
+
+template <int NTP, int MODE = 0, bool F64 = false, bool FULL = false, typename TIN = float, bool SIDE = false>
 __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *__restrict__ params,
                                           const SvdqUnit *__restrict__ units,
                                           const float *const *__restrict__ ptrs,
@@ -21,7 +47,9 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
                                           const void *const *__restrict__ aux = nullptr,
                                           const int32_t *__restrict__ only = nullptr,
                                           const void *const *__restrict__ aux2 = nullptr,
-                                          const int64_t *__restrict__ ustart = nullptr) {
+                                          const int64_t *__restrict__ ustart = nullptr,
+                                          double *__restrict__ side_part = nullptr) {
+    static_assert(!SIDE || (MODE & ~2) == 0, "the side sums exist for plain deltas and minus-base only");
     constexpr bool GATHER = (MODE & 1) != 0, SUB = (MODE & 2) != 0, WALK = (MODE & 4) != 0;
     static_assert(!(GATHER && WALK), "index lists and the mask walk are alternatives");
     static_assert(!(MODE != 0 && SVDQ_PREFETCH2), "gather / minus-base support the one-block-ahead pipeline only");
@@ -110,6 +138,7 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
 #pragma unroll
         for (int e = 0; e < 4; ++e) qd[i][e] = 0.0;
     const int b4 = lane >> 2, i4 = lane & 3, mg4 = b4 & 3, rg4 = b4 >> 2;
+    double side = 0.0;   // SIDE: lane t < NT: a[t], lane NTP: s, over the whole unit
 
     // The loads of the next block (or next two, SVDQ_PREFETCH2) are in flight while a block is computed.
     constexpr int AHEAD = SVDQ_PREFETCH2 ? 2 : 1;
@@ -334,7 +363,7 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
 #pragma unroll
                 for (int t = 0; t < NTP; ++t) v[t] = v[t] - vb;
             }
-            center_store<NTP, GATHER>(v, NT, center, X, lane);
+            const f32x4 mean = center_store<NTP, GATHER>(v, NT, center, X, lane);
             wave_sync();
             if (rb + AHEAD * SVDQ_BLK_ROWS < r_end) {
                 if constexpr (GATHER) {
@@ -345,6 +374,27 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
                     load_block<NTP, TIN>(v, bp, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
                     if constexpr (SUB) vb = load_base<TIN>(gbase, rb + AHEAD * SVDQ_BLK_ROWS, D, lane);
                 }
+            }
+            if constexpr (SIDE) {   // the lane's own four rows of every task, back from the strip (v is being refilled)
+                float s = mean.x * mean.x;
+                s = __builtin_fmaf(mean.y, mean.y, s);
+                s = __builtin_fmaf(mean.z, mean.z, s);
+                s = __builtin_fmaf(mean.w, mean.w, s);
+                s = side_wave_sum(s);
+                float mine = (lane == NTP) ? s : 0.f;
+#pragma unroll
+                for (int t = 0; t < NTP; ++t) {
+                    if (t < NT) {
+                        const f32x4 xc = *reinterpret_cast<const f32x4 *>(X + t * XS + 4 * lane);
+                        float a = xc.x * mean.x;
+                        a = __builtin_fmaf(xc.y, mean.y, a);
+                        a = __builtin_fmaf(xc.z, mean.z, a);
+                        a = __builtin_fmaf(xc.w, mean.w, a);
+                        a = side_wave_sum(a);
+                        mine = (lane == t) ? a : mine;
+                    }
+                }
+                side += (double)mine;
             }
             compute();
         };
@@ -365,6 +415,10 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
                 for (int q = 1; q < QC; ++q) t += accq[i * QC + q][e];
                 accd[i][e] = t;
             }
+    }
+
+    if constexpr (SIDE) {   // every unit writes its NT + 1 numbers, zeros included
+        if (lane < NT || lane == NTP) side_part[(size_t)uidx * (NT + 1) + (lane < NT ? lane : NT)] = side;
     }
 
     // One fp64 partial per slot, dense [NT][NT].  Lane (c,g) holds D[4g+e][c] (fp32 MFMA) or D[g+4e][c] (fp64 MFMA).
@@ -475,11 +529,58 @@ __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) 
     SVDQ_STAMP_END(svdq_stamps_gram, uidx);
 }
 
+// k_gram with the side sums of the task-Gram by-product (gram_unit, SIDE).  A kernel of its own, so that k_gram's
+// instantiations stay what they were; same launch bounds.
+template <int NTP, int MODE, bool F64, bool FULL, typename TIN>
+__global__ __launch_bounds__(64, (F64 && MODE == 0 && NTP <= 16) ? (NTP <= 8 ? SVDQ_GRAM64_WAVES8 : SVDQ_GRAM64_WAVES16) : 1) void k_gram_side(const SvdqParam *__restrict__ params,
+                                             const SvdqUnit *__restrict__ units,
+                                             const float *const *__restrict__ ptrs,
+                                             const int64_t *__restrict__ rows_dev, int NT, int center,
+                                             double *__restrict__ gram_part, int unit0,
+                                             const void *const *__restrict__ aux2, int order,
+                                             double *__restrict__ side_part) {
+    __shared__ __attribute__((aligned(16))) float X[NTP * XS];
+    const int uidx = unit0 + unit_of_block((int)blockIdx.x, (int)gridDim.x, order);
+    gram_unit<NTP, MODE, F64, FULL, TIN, true>(X, uidx, params, units, ptrs, rows_dev, NT, center, gram_part, nullptr,
+                                                nullptr, aux2, nullptr, side_part);
+}
+
 // ------------------------------------------------------------------------------------ launcher
+// The by-product launch: plain deltas and minus-base only (MODE 0, 2), never with `only` (the refinement launch of
+// N > 16 leaves the side partials of the first launch where they are).
+static int launch_gram_side(const svdq_plan *pl, const SvdqInput &in, double *gram_part, int unit0, int nunits,
+                            int center, int f64, hipStream_t st, double *side_part) {
+    const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
+        using TIN = typename decltype(tin_c)::type;
+        return svdq_dispatch_int<4, 8, 12, 16, 20, 24, 28, 32>(pl->ntp, [&](auto ntp_c) {
+            constexpr int NTP = ntp_c;
+            return svdq_dispatch_int<0, 2>(in.mode(), [&](auto mode_c) {
+                constexpr int MODE = mode_c;
+                return svdq_dispatch_bool(f64 != 0, [&](auto f64_c) {
+                    constexpr bool F64 = f64_c;
+                    return svdq_dispatch_bool(MODE == 0 && pl->n_tasks == NTP, [&](auto full_c) {
+                        constexpr bool FULL = full_c;
+                        if constexpr (FULL && MODE != 0) return false;
+                        else {
+                            hipLaunchKernelGGL((k_gram_side<NTP, MODE, F64, FULL, TIN>), dim3(nunits), dim3(64), 0, st,
+                                               pl->d_params, pl->d_units, in.tensors(), in.rows_dev, pl->n_tasks, center,
+                                               gram_part, unit0, in.aux2(), pl->cfg.reserved & SVDQ_SW_XCD_CHUNKED,
+                                               side_part);
+                            return true;
+                        }
+                    });
+                });
+            });
+        });
+    });
+    return svdq_launch_status(ok, "k_gram_side");
+}
+
 // Variants: the walk (MODE 4, 6) reads fp32 tensors only, and above 16 tasks plain deltas only (MODE 4); the plain and
 // the walk mode have a FULL variant for plans with exactly NTP tasks, the walk up to 16 tasks only.
 int svdq_launch_gram(const svdq_plan *pl, const SvdqInput &in, double *gram_part, int unit0, int nunits, int center,
-                     int f64, const int32_t *only, hipStream_t st) {
+                     int f64, const int32_t *only, hipStream_t st, double *side_part) {
+    if (side_part) return launch_gram_side(pl, in, gram_part, unit0, nunits, center, f64, st, side_part);
     const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
         using TIN = typename decltype(tin_c)::type;
         return svdq_dispatch_int<4, 8, 12, 16, 20, 24, 28, 32>(pl->ntp, [&](auto ntp_c) {

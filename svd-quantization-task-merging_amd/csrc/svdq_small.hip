@@ -126,6 +126,102 @@ int svdq_launch_gram_total(const svdq_plan *pl, const double *part2, double *out
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
 
+// ------------------------------------------------------------------------------------ task-Gram by-product
+// The side sums of k_gram_side (a[0..N-1] = Tc^T m and s = m^T m, N + 1 doubles per unit) take the same two steps as the
+// Gram partials.  k_reduce_side: chunk c of parameter p -> side2[(p * SVDQ_RC + c)][N + 1]; 256 threads = four groups
+// of 64, group g takes units a + g, a + g + 4, ... with eight loads in flight, the group sums meet in LDS in group
+// order.  Fixed order: the same bits in every run, and per parameter in every batch.
+__global__ __launch_bounds__(RED_THREADS) void k_reduce_side(const SvdqParam *__restrict__ params, int NT,
+                                                             const double *__restrict__ side,
+                                                             double *__restrict__ side2) {
+#pragma clang fp contract(off)
+    __shared__ double red[RED_THREADS];
+    const int p = blockIdx.x, c = blockIdx.y, ns = NT + 1;
+    const SvdqParam pd = params[p];
+    const int per = (pd.unit_count + SVDQ_RC - 1) / SVDQ_RC;  // units per chunk, as in k_reduce
+    int ua = c * per, ub = ua + per;
+    if (ub > pd.unit_count) ub = pd.unit_count;
+    if (ua > ub) ua = ub;
+    const int a = pd.unit_begin + ua, b = pd.unit_begin + ub;
+    const int g = threadIdx.x >> 6, l = threadIdx.x & 63;
+    double acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = 0.0;
+    if (l < ns) {
+        int s = a + g;
+        for (; s + 28 < b; s += 32) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc[u] += side[(size_t)(s + 4 * u) * ns + l];
+        }
+        for (; s < b; s += 4) acc[0] += side[(size_t)s * ns + l];
+    }
+    red[threadIdx.x] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    __syncthreads();
+    if (g == 0 && l < ns)
+        side2[((size_t)p * SVDQ_RC + c) * ns + l] = (red[l] + red[64 + l]) + (red[128 + l] + red[192 + l]);
+}
+
+int svdq_launch_reduce_side(const svdq_plan *pl, const double *side, double *side2, hipStream_t st) {
+    hipLaunchKernelGGL(k_reduce_side, dim3(pl->n_params, SVDQ_RC), dim3(RED_THREADS), 0, st, pl->d_params, pl->n_tasks,
+                       side, side2);
+    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
+}
+
+// k_gram_total plus the correction.  First the totals of a and s over all parameters and chunks: 256 threads =
+// G = 256 / (N + 1) groups, thread (group j, entry e) takes partials j, j + G, ... (eight in flight), entry e's group
+// sums are added in group order.  Then every Gram entry is totalled exactly as k_gram_total does and leaves as
+// G[i][j] + ((a[i] + a[j]) + s): symmetric partials in, an exactly symmetric matrix out.
+__global__ __launch_bounds__(256) void k_gram_total_side(int nparams, int NT, const double *__restrict__ part2,
+                                                         const double *__restrict__ side2, double *__restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    __shared__ double tot[SVDQ_MAX_TASKS + 1];
+    const int total = nparams * SVDQ_RC, nn = NT * NT, ns = NT + 1;
+    {
+        const int G = 256 / ns, j = threadIdx.x / ns, e = threadIdx.x % ns;
+        double acc[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] = 0.0;
+        if (j < G) {
+            int s = j;
+            for (; s + 7 * G < total; s += 8 * G) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc[u] += side2[(size_t)(s + u * G) * ns + e];
+            }
+            for (; s < total; s += G) acc[0] += side2[(size_t)s * ns + e];
+        }
+        red[threadIdx.x] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+        __syncthreads();
+        if (threadIdx.x < ns) {
+            double t = red[threadIdx.x];
+            for (int q = 1; q < G; ++q) t += red[q * ns + threadIdx.x];
+            tot[threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+    for (int e0 = 0; e0 < nn; e0 += 16) {   // k_gram_total's order
+        const int e = e0 + (threadIdx.x & 15), j = threadIdx.x >> 4;
+        const int per = (total + 15) / 16;
+        int a = j * per, b = a + per;
+        if (b > total) b = total;
+        if (a > b) a = b;
+        red[threadIdx.x] = e < nn ? chunk_sum(part2, a, b, nn, e) : 0.0;
+        __syncthreads();
+        for (int off = 128; off >= 16; off >>= 1) {
+            if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+            __syncthreads();
+        }
+        if (threadIdx.x < 16 && e < nn) out[e] = red[threadIdx.x] + ((tot[e / NT] + tot[e % NT]) + tot[NT]);
+        __syncthreads();
+    }
+}
+
+int svdq_launch_gram_total_side(const svdq_plan *pl, const double *part2, const double *side2, double *out,
+                                hipStream_t st) {
+    hipLaunchKernelGGL(k_gram_total_side, dim3(1), dim3(256), 0, st, pl->n_params, pl->n_tasks, part2, side2, out);
+    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
+}
+
 template <int THREADS, int NMAX, typename TIN>
 __global__ __launch_bounds__(THREADS) void k_eig(const SvdqParam *__restrict__ params,
                                                  const float *const *__restrict__ ptrs,

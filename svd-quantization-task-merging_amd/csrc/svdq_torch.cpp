@@ -12,6 +12,8 @@
 //   mask_select(Tensor x, Tensor mask, bool invert) -> Tensor
 //   compress(Tensor[] deltas, int n_tasks, float energy, int max_rank, bool center, bool fp16, int bits, int stages)
 //       -> (Tensor small, Tensor basis, Tensor mean)          packed buffers: svdq_plan_small_layout / _basis_layout
+//   compress_task_gram(Tensor[] deltas, int n_tasks, <settings>) -> (small, basis, mean, Tensor gram)
+//       compress + the fp64 [N, N] task Gram of the same deltas as a by-product of pass 1 (svdq_plan_task_gram)
 //   compress_masked(Tensor[] deltas, Tensor[] masks, int n_tasks, <settings>) -> (small, basis, mean, Tensor rows)
 //       masks[p] = the combined mask of parameter p; mask walk (svdq_compress_masked)
 //   compress_gather(...same...)                                the same through int32 index lists (svdq_compress_gather)
@@ -224,10 +226,11 @@ struct Plan {
 };
 
 std::unique_ptr<Plan> make_plan(const std::vector<int64_t> &rows, int64_t n_tasks, const svdq_config &cfg,
-                                const c10::Device &dev) {
+                                const c10::Device &dev, bool task_gram = false) {
     auto p = std::make_unique<Plan>();
     p->dev = dev;
     check(svdq_plan_create(&p->h, (int32_t)n_tasks, (int32_t)rows.size(), rows.data(), &cfg), "svdq_plan_create");
+    if (task_gram) check(svdq_plan_set_task_gram(p->h, 1), "svdq_plan_set_task_gram");   // before the sizes are read
     check(svdq_plan_sizes(p->h, &p->sizes), "svdq_plan_sizes");
     p->workspace = bytes_on(dev, p->sizes.workspace_bytes);
     return p;
@@ -269,10 +272,11 @@ struct PlanKey {
     int dev;
     void *stream;
     int32_t in_type = SVDQ_INPUT_F32;
+    bool task_gram = false;   // the plan leaves the task Gram as a by-product of pass 1 (compress_task_gram)
     bool operator==(const PlanKey &o) const {
         return rows == o.rows && n_tasks == o.n_tasks && max_rank == o.max_rank && bits == o.bits && stages == o.stages &&
                energy == o.energy && center == o.center && fp16 == o.fp16 && dev == o.dev && stream == o.stream &&
-               in_type == o.in_type;
+               in_type == o.in_type && task_gram == o.task_gram;
     }
 };
 constexpr size_t kPlanCacheMax = 8;
@@ -298,7 +302,7 @@ std::unique_ptr<Plan> acquire_plan(const PlanKey &key, const c10::Device &dev) {
         cfg.fp16 = key.fp16;
         cfg.low_bits = (int32_t)key.bits;
         cfg.rtvq_stages = (int32_t)key.stages;
-        plan = make_plan(key.rows, key.n_tasks, cfg, dev);
+        plan = make_plan(key.rows, key.n_tasks, cfg, dev, key.task_gram);
         check(svdq_plan_set_input_type(plan->h, key.in_type), "svdq_plan_set_input_type");
         while (g_cache.size() >= kPlanCacheMax) {
             sync(g_cache.front().second->dev);                        // its tables may still be in use
@@ -346,6 +350,36 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> compress(at::TensorList deltas, i
     check(rc, "svdq_compress");
     // inputs and the table are only read by the kernels just enqueued; temporaries are released stream-ordered
     return {o.small, o.basis, o.mean};
+}
+
+// compress + the uncentred N x N task Gram of the same tensors as a by-product of pass 1 (svdq_plan_task_gram):
+// compress's three outputs, bit for bit, and what task_gram returns for these deltas without reading them again
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_task_gram(at::TensorList deltas, int64_t n_tasks,
+                                                                              double energy, int64_t max_rank,
+                                                                              bool center, bool fp16, int64_t bits,
+                                                                              int64_t stages) {
+    const int32_t in_type = input_type_of(deltas);
+    std::vector<at::Tensor> vecs = prep_list(deltas, n_tasks, "compress_task_gram", in_type);
+    const c10::Device dev = vecs[0].device();
+    c10::DeviceGuard guard(dev);
+    void *stream = stream_of(dev);
+    PlanKey key{rows_of(vecs, n_tasks), n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream,
+                in_type, true};
+    std::lock_guard<std::mutex> lock(g_cache_mu);
+    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    Outputs o = alloc_outputs(*plan, center, dev);
+    at::Tensor table = table_of(vecs, dev);
+    at::Tensor gram = at::empty({n_tasks, n_tasks}, at::TensorOptions().dtype(at::kDouble).device(dev));
+    int rc = svdq_compress(plan->h, table.data_ptr(), nullptr, plan->workspace.data_ptr(), o.small.data_ptr(),
+                           o.basis.data_ptr(), center ? o.mean.data_ptr<float>() : nullptr, stream);
+    const char *what = "svdq_compress";
+    if (rc == SVDQ_OK) {
+        rc = svdq_plan_task_gram(plan->h, plan->workspace.data_ptr(), gram.data_ptr<double>(), stream);
+        what = "svdq_plan_task_gram";
+    }
+    release_plan(std::move(key), std::move(plan));
+    check(rc, what);
+    return {o.small, o.basis, o.mean, gram};
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> compress_from_base(at::TensorList finetuned, at::TensorList base,
@@ -836,6 +870,8 @@ TORCH_LIBRARY(svdq, m) {
     m.def("mask_select(Tensor x, Tensor mask, bool invert) -> Tensor");
     m.def("compress(Tensor[] deltas, int n_tasks, float energy, int max_rank, bool center, bool fp16, int bits, "
           "int stages) -> (Tensor, Tensor, Tensor)");
+    m.def("compress_task_gram(Tensor[] deltas, int n_tasks, float energy, int max_rank, bool center, bool fp16, int bits, "
+          "int stages) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("compress_masked(Tensor[] deltas, Tensor[] masks, int n_tasks, float energy, int max_rank, bool center, bool fp16, "
           "int bits, int stages) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("compress_gather(Tensor[] deltas, Tensor[] masks, int n_tasks, float energy, int max_rank, bool center, bool fp16, "
@@ -863,6 +899,7 @@ TORCH_LIBRARY_IMPL(svdq, CUDA, m) {
     m.impl("mask_combine", mask_combine);
     m.impl("mask_select", mask_select);
     m.impl("compress", compress);
+    m.impl("compress_task_gram", compress_task_gram);
     m.impl("compress_masked", compress_masked);
     m.impl("compress_gather", compress_gather);
     m.impl("compress_from_base", compress_from_base);

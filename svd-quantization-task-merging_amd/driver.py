@@ -35,10 +35,17 @@ def _resident(tensors, dev) -> bool:
 
 
 def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks: Optional[Dict[str, torch.Tensor]],
-                config, device="cuda", base_state: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Dict]:
+                config, device="cuda", base_state: Optional[Dict[str, torch.Tensor]] = None,
+                task_gram: Optional[bool] = None) -> Dict[str, Dict]:
     """Step 4 for all parameters.  Returns ``bases`` (reference layout: {param: {"masked": basis|None,
     "noise": basis|None}}), already cast to fp16 when ``config.svd_fp16`` (cli.py:354-361), with the
-    coefficients of Step 5 attached for ``compress_all_parameters``."""
+    coefficients of Step 5 attached for ``compress_all_parameters``.
+
+    ``task_gram`` (default: ``config.svd_weighting == "cluster"``): every plan of unmasked parameters also leaves the
+    uncentred task Gram of its tensors (svdq_plan_task_gram, a by-product of pass 1; the artifacts are byte-identical
+    either way), recorded on its BatchResult for ``clustering.task_gram(..., bases=bases)``."""
+    if task_gram is None:
+        task_gram = getattr(config, "svd_weighting", None) == "cluster"
     dev = resolve_device(device)
     combined_masks = combined_masks or {}
     names = sorted({n for tv in task_vectors.values() for n in tv.keys()})
@@ -76,7 +83,8 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                         else [prepare_vector(d, dev) for d in deltas]
                 if vs[0].numel() == 0:
                     continue
-                groups.setdefault((len(present), "plain", idt), []).append(
+                # with the by-product a plan's Gram columns must mean the same tasks for all its parameters
+                groups.setdefault((tuple(present) if task_gram else len(present), "plain", idt), []).append(
                     {"name": name, "region": "masked", "tasks": present, "vectors": vs, "count": None,
                      "upper": vs[0].numel(), "min": 0,
                      "base": prepare_input(base_state[name], dev, idt) if base_state is not None else None})
@@ -136,12 +144,16 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
             entries = [e for e in entries if e["upper"] > 0]
             if not entries:
                 continue
+            want_gram = bool(task_gram) and mode == "plain"
+            if isinstance(n_tasks, tuple):
+                n_tasks = len(n_tasks)
             plan = CompressPlan([e["upper"] for e in entries], n_tasks,
                                 energy_threshold=config.svd_energy_threshold, max_rank=config.svd_max_rank,
                                 center=config.svd_center, fp16=config.svd_fp16,
                                 low_bits=([int(bits_by_param(e["name"])) for e in entries] if bits_by_param
                                           else config.svd_low_bits),
-                                rtvq_stages=config.svd_rtvq_stages, device=dev, input_dtype=idt)
+                                rtvq_stages=config.svd_rtvq_stages, device=dev, input_dtype=idt,
+                                **({"task_gram": True} if want_gram else {}))
             rows_dev = None
             if any(e["count"] is not None for e in entries):
                 # rows actually processed = mask.sum() (device), or 0 when below svd_min_mask_size
@@ -184,6 +196,7 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                 plan.run_from_base(table, btab, rows_dev)
             else:
                 plan.run(table, rows_dev)
+            gram = plan.compress_task_gram() if want_gram else None
             small = plan.fetch_small()
             batch = BatchResult(plan, small, [(e["name"], e["region"]) for e in entries],
                                 [e["tasks"] for e in entries])
@@ -193,6 +206,9 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
             batch.mask_table, batch.unit_start = mtab, us
             batch.mask_ident = {e["name"]: e["mask_ident"] for e in entries if "mask_ident" in e}
             batch.from_base = base_state is not None
+            # the by-product: Gram of this plan's tensors, its task order, the parameters it covers
+            batch.task_gram = ({"gram": gram, "tasks": list(entries[0]["tasks"]), "names": [e["name"] for e in entries]}
+                               if want_gram else None)
             for i, e in enumerate(entries):
                 slot = bases.setdefault(e["name"], {"masked": None, "noise": None})
                 if int(small.rows[i]) <= 0:
@@ -298,21 +314,23 @@ def artifacts_from_batch(name: str, basis: Dict, task_vectors, config) -> Option
                                "noise": bn._batch if (bn is not None and getattr(bn, "_batch", None) is not None) else None})
 
 
-def run_basis_and_compress(task_vectors, combined_masks, config, device="cuda") -> Tuple[Dict, Dict]:
-    """cli.py Step 4 + Step 5 in one call: (bases, compressed_all)."""
+def run_basis_and_compress(task_vectors, combined_masks, config, device="cuda", task_gram: Optional[bool] = None
+                           ) -> Tuple[Dict, Dict]:
+    """cli.py Step 4 + Step 5 in one call: (bases, compressed_all).  ``task_gram``: see ``build_bases``."""
     from .compress import compress_all_parameters
-    bases = build_bases(task_vectors, combined_masks, config, device)
+    bases = build_bases(task_vectors, combined_masks, config, device, task_gram=task_gram)
     return bases, compress_all_parameters(task_vectors, combined_masks or {}, bases, config, device)
 
 
 def run_basis_and_compress_from_checkpoints(base_state: Dict[str, torch.Tensor],
                                             finetuned_states: Dict[str, Dict[str, torch.Tensor]], config,
-                                            device="cuda", combined_masks: Optional[Dict[str, torch.Tensor]] = None
-                                            ) -> Tuple[Dict, Dict]:
+                                            device="cuda", combined_masks: Optional[Dict[str, torch.Tensor]] = None,
+                                            task_gram: Optional[bool] = None) -> Tuple[Dict, Dict]:
     """cli.py Step 1 + Step 4 + Step 5 without materialising the task vectors: ``finetuned - base`` is formed
     inside the two streaming passes (svdq_compress_from_base; with ``combined_masks`` the masked parameters go
     through svdq_compress_gather_from_base).  Same (bases, compressed_all) as load_task_vectors +
-    run_basis_and_compress, bit for bit."""
+    run_basis_and_compress, bit for bit.  With ``task_gram`` (see ``build_bases``) the recorded Gram is that of the
+    deltas formed in registers, so a cluster-weighted run needs no task vectors either."""
     from .compress import compress_all_parameters
-    bases = build_bases(finetuned_states, combined_masks, config, device, base_state=base_state)
+    bases = build_bases(finetuned_states, combined_masks, config, device, base_state=base_state, task_gram=task_gram)
     return bases, compress_all_parameters(finetuned_states, combined_masks or {}, bases, config, device)

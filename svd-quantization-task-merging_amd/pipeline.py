@@ -122,9 +122,11 @@ class CompressPlan:
     def __init__(self, rows: Sequence[int], n_tasks: int, *, energy_threshold: float = 0.90,
                  max_rank: Optional[int] = None, center: bool = True, fp16: bool = True,
                  low_bits: int = 4, rtvq_stages: int = 2, device="cuda", unit_rows: int = 0, flags: int = 0,
-                 gram_only: bool = False, input_dtype: torch.dtype = torch.float32):
+                 gram_only: bool = False, input_dtype: torch.dtype = torch.float32, task_gram: bool = False):
         if input_dtype not in INPUT_TYPES:
             raise ValueError(f"input_dtype must be one of {list(INPUT_TYPES)}, got {input_dtype}")
+        if task_gram and gram_only:
+            raise ValueError("task_gram=True is the by-product of a compressing plan; a gram_only plan has task_gram()")
         self.lib = nat.lib()
         self.device = resolve_device(device)
         self.rows = [int(x) for x in rows]
@@ -155,6 +157,10 @@ class CompressPlan:
         self.input_dtype = input_dtype
         if input_dtype is not torch.float32:
             nat.check(self.lib.svdq_plan_set_input_type(self._h, INPUT_TYPES[input_dtype]), "svdq_plan_set_input_type")
+        # the uncentred task Gram as a by-product of pass 1 (compress_task_gram); set before the sizes are read
+        self.has_task_gram = bool(task_gram)
+        if self.has_task_gram:
+            nat.check(self.lib.svdq_plan_set_task_gram(self._h, 1), "svdq_plan_set_task_gram")
         self.sizes = nat.SvdqSizes()
         nat.check(self.lib.svdq_plan_sizes(self._h, byref(self.sizes)), "svdq_plan_sizes")
         self.layout = nat.SvdqSmallLayout()
@@ -272,6 +278,17 @@ class CompressPlan:
         out = torch.empty((self.N, self.N), dtype=torch.float64, device=self.device)
         nat.check(self.lib.svdq_task_gram(self._h, _ptr(table), _ptr(rows_dev), _ptr(self.workspace), _ptr(out),
                                           _stream_ptr()), "svdq_task_gram")
+        return out
+
+    def compress_task_gram(self) -> torch.Tensor:
+        """The same Gram (fp64 [N, N], device, plan task order) of the tensors the last run / the last pass 1 + eigen
+        stage over all parameters read, without reading them again (svdq_plan_task_gram); plans made with
+        ``task_gram=True`` only."""
+        if not self.has_task_gram:
+            raise ValueError("this plan was not created with task_gram=True")
+        out = torch.empty((self.N, self.N), dtype=torch.float64, device=self.device)
+        nat.check(self.lib.svdq_plan_task_gram(self._h, _ptr(self.workspace), _ptr(out), _stream_ptr()),
+                  "svdq_plan_task_gram")
         return out
 
     def run(self, table, rows_dev=None):
