@@ -142,7 +142,35 @@ int svdq_gram_center(const svdq_plan *plan, const void *delta_ptrs_dev, const in
  *      Cyclic Jacobi in fp64, sigma = sqrt(lambda) -> fp32, fp32 cumsum rule of the reference.
  *      Writes sigma / k / r / energy / rows into small_dev and W = V Sigma^-1 into the workspace.
  *      Reads row 0 of every task (delta_ptrs_dev) to build the orthonormal completion column of the
- *      null direction that centring creates (LAPACK returns an arbitrary orthonormal vector there). */
+ *      null direction that centring creates (LAPACK returns an arbitrary orthonormal vector there).
+ *
+ *      NON-FINITE INPUT (the one statement of the contract; the sources point here).  The reference stops on a task
+ *      delta that holds NaN or +-Inf: torch.linalg.svd raises "input matrix contained non-finite values" (compute_svd,
+ *      basis.py:216-249).  Errors of the data cannot be return codes of an asynchronous call, so they travel in the
+ *      small buffer:
+ *        what is flagged   a parameter with rows > 0 whose N x N Gram, right after the fixed-order sum of its partials,
+ *                          has an entry that is NaN or +-Inf.  Every compress route (plain, gather, from-base, gather +
+ *                          base, walk, walk + base) and the staged _range entry points end in this stage.  The Gram is
+ *                          accumulated in fp64 from exact products, so a non-finite entry means a non-finite delta among
+ *                          the rows processed (a centred Inf is a NaN; finetuned - base counts as formed in the passes).
+ *                          Rows that a mask does not select and parameters with rows_dev[p] == 0 are never read.
+ *        how it is seen    energy[p] is NaN.  energy[p] of every healthy parameter is finite, so isnan(energy[p]) IS the
+ *                          flag; it is written by every eigen stage, so a later clean run on the same buffers clears it.
+ *                          Also: sigma[p][0..N) = NaN; k[p] = min(1, r), r[p] and rows[p] as always (pass 2 and the
+ *                          coefficient epilogue index as for a healthy parameter); W and the closed-form coefficients
+ *                          are zero; the parameter's basis, mean and coefficient outputs are unspecified.  No Jacobi
+ *                          sweep runs on it, nothing reads out of bounds.
+ *        who raises        the calls here return SVDQ_OK and the torch operators stay asynchronous: a C or operator
+ *                          caller tests isnan(energy[p]) in its host copy of the small buffer (Python:
+ *                          pipeline.nonfinite_parameters).  CompressPlan.fetch_small raises NonFiniteInput, the
+ *                          dictionary API a RuntimeError that names the parameters and regions.
+ *        above 16 tasks    the first accumulation uses fp32 products, which overflow for finite deltas beyond ~1.8e19
+ *                          that the reference accepts: a non-finite fp32-product Gram asks for the fp64 refinement
+ *                          pass, and only a Gram that is still non-finite after it flags the parameter.
+ *        exception         cfg.reserved bit 1 (fp32-product Gram for every N, a measurement switch) has no refinement
+ *                          pass: there the fp32-product Gram flags directly, finite deltas beyond ~1.8e19 included.
+ *      Healthy parameters with sigma_0 beyond ~1.8e19 (where the reference's fp32 sum of squares overflows and its
+ *      energy reads inf / inf = NaN, k = 1): the same energy rule is evaluated in fp64, so their energy is finite. */
 int svdq_eig_rank_select(const svdq_plan *plan, const void *delta_ptrs_dev, const int64_t *rows_dev,
                          void *workspace_dev, void *small_dev, void *stream);
 

@@ -416,7 +416,9 @@ static int eig_range(const svdq_plan *pl, const SvdqInput &in, void *workspace, 
     if (!refine) return SVDQ_OK;
     // N > 16: the parameters whose spectrum reaches into the band fp32-product sums do not resolve are accumulated
     // again with exact products (v_mfma_f64_16x16x4_f64) and solved again; units of all other parameters return at
-    // once, so a batch without such a parameter pays three near-empty launches
+    // once, so a batch without such a parameter pays three near-empty launches.  A non-finite fp32-product Gram takes
+    // the same route (finite deltas beyond ~1.8e19 overflow the products only); what is still non-finite afterwards
+    // flags the parameter (include/svdq.h, svdq_eig_rank_select)
     int u0, nu;
     unit_range(pl, param0, nparams, &u0, &nu);
     if (int rc = svdq_launch_gram(pl, in, part, u0, nu, pl->cfg.center, 1, flags, st)) return rc;

@@ -80,6 +80,9 @@ __device__ __forceinline__ double chunk_sum(const double *__restrict__ part, int
 // the stand-alone kernel (k_eig) and the persistent fused kernel share it.  THREADS threads of ONE
 // workgroup must call it together (tid = thread index in [0, THREADS)).
 // TIN: element type of the task / base tensors (svdq_input.h); only row 0 is read here.
+// refine_out (N > 16, fp32-product Gram): receives 1 for a parameter that needs the fp64 Gram pass -- a spectrum in the
+// unresolved band, or a non-finite Gram (the products may have overflowed, not the data).  NULL: this Gram is final, a
+// non-finite one flags the parameter (include/svdq.h, svdq_eig_rank_select; SVDQ_SW_GRAM_F32 always passes NULL).
 template <int THREADS, int NMAX, typename TIN = float>
 __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
                           const float *const *__restrict__ ptrs, int NT, int center, float thr, int max_rank,
@@ -103,14 +106,45 @@ __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
     EIG_STAMP(0);
 
     // fixed-order sum of the SVDQ_RC level-2 partials
+    int bad = 0;  // an entry of this thread is NaN or +-Inf (all exponent bits set)
     for (int e = tid; e < nn; e += THREADS) {
         const double *src = gram_part2 + (size_t)p * SVDQ_RC * nn + e;
         double a = 0.0;
 #pragma unroll
         for (int c = 0; c < SVDQ_RC; ++c) a += src[(size_t)c * nn];
         Gd[e] = a;
+        bad |= (__double_as_longlong(a) & 0x7ff0000000000000ll) == 0x7ff0000000000000ll;
     }
+    // Non-finite input (include/svdq.h, svdq_eig_rank_select): a Gram with a NaN or Inf entry flags the parameter.
+    // The decision is uniform over the workgroup: one ballot (one wavefront) or one workgroup OR at the phase boundary.
+    if constexpr (THREADS == 64) bad = __builtin_amdgcn_ballot_w64(bad != 0) != 0;
+    else bad = __syncthreads_or(bad);
     phase_sync<THREADS>();
+    if (bad && D > 0) {
+        // Flagged: sigma and energy are NaN, k / r / rows as for a healthy parameter (pass 2 and k_coeff index as
+        // always), W and c0 zero.  No Jacobi sweep runs on NaN.  With fp32 products behind this Gram (refine_out set)
+        // the overflow may be that of the products, not of the data: the fp64 pass decides.
+        const int rf = (int)(D < (int64_t)n ? D : (int64_t)n);
+        if (tid == 0) {
+            const float qnan = __builtin_nanf("");
+            for (int i = 0; i < n; ++i) sigma_out[(size_t)p * n + i] = qnan;
+            k_out[p] = rf < 1 ? rf : 1;
+            r_out[p] = rf;
+            energy_out[p] = qnan;
+            rows_out[p] = D;
+            if (refine_out) refine_out[p] = 1;
+            float *aux = Wtab + (size_t)p * (nn + 4) + nn;
+            aux[0] = 0.f;
+            aux[1] = -1.f;
+            aux[2] = 0.f;
+            aux[3] = 0.f;
+        }
+        for (int e = tid; e < nn; e += THREADS) {
+            Wtab[(size_t)p * (nn + 4) + e] = 0.f;
+            c0_out[(size_t)p * nn + e] = 0.0;
+        }
+        return;
+    }
     EIG_STAMP(1);
 
     // Centred rows sum to zero, so 1/sqrt(N) is an exact null vector of Tc.  Deflate that direction explicitly in fp64
@@ -281,10 +315,28 @@ __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
         if (kk < 1) kk = 1;
         if (max_rank > 0 && kk > max_rank) kk = max_rank;
         if (kk > r) kk = r;
+        float en = (kk > 0 && r > 0) ? cum[kk - 1] : 0.f;
+        if (total > 3.4028234e38f) {
+            // sigma_0 beyond ~1.8e19: the fp32 sum of squares overflowed and the rule above read inf / inf = NaN
+            // (k = 1), as the reference's does.  NaN energy is the non-finite-input flag (include/svdq.h,
+            // svdq_eig_rank_select), so a healthy parameter never carries it: the same rule again, in fp64.
+            double tot64 = 0.0, run64 = 0.0;
+            for (int i = 0; i < r; ++i) tot64 += sig[i] * sig[i];
+            kk = 1;
+            for (int i = 0; i < r; ++i) {
+                run64 += sig[i] * sig[i];
+                if ((float)(run64 / tot64) < thr) ++kk;
+            }
+            if (max_rank > 0 && kk > max_rank) kk = max_rank;
+            if (kk > r) kk = r;
+            run64 = 0.0;
+            for (int i = 0; i < kk; ++i) run64 += sig[i] * sig[i];
+            en = (float)(run64 / tot64);
+        }
         for (int i = 0; i < n; ++i) sigma_out[(size_t)p * n + i] = (i < r) ? S[i] : 0.f;
         k_out[p] = kk;
         r_out[p] = r;
-        energy_out[p] = (kk > 0 && r > 0) ? cum[kk - 1] : 0.f;
+        energy_out[p] = en;
         rows_out[p] = D;
         // first direction below the resolution of this Gram (exact products: the fp32 resolution of the data), if any
         int i0 = -1;

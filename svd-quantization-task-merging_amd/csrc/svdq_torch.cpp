@@ -12,6 +12,9 @@
 //   mask_select(Tensor x, Tensor mask, bool invert) -> Tensor
 //   compress(Tensor[] deltas, int n_tasks, float energy, int max_rank, bool center, bool fp16, int bits, int stages)
 //       -> (Tensor small, Tensor basis, Tensor mean)          packed buffers: svdq_plan_small_layout / _basis_layout
+//       Non-finite deltas: compress and its variants stay asynchronous and do not raise; a parameter whose deltas hold
+//       NaN or Inf carries a NaN energy in `small` (include/svdq.h, svdq_eig_rank_select) and the caller tests for it
+//       when it reads the buffer: svdq_amd.pipeline.nonfinite_parameters(small, layout, n_params)
 //   compress_task_gram(Tensor[] deltas, int n_tasks, <settings>) -> (small, basis, mean, Tensor gram)
 //       compress + the fp64 [N, N] task Gram of the same deltas as a by-product of pass 1 (svdq_plan_task_gram)
 //   compress_masked(Tensor[] deltas, Tensor[] masks, int n_tasks, <settings>) -> (small, basis, mean, Tensor rows)

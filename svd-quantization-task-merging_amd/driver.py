@@ -10,8 +10,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .pipeline import (BatchResult, CompressPlan, basis_dict, native_input_dtype, prepare_input, prepare_vector,
-                       resolve_device, task_artifact)
+from .pipeline import (BatchResult, CompressPlan, NonFiniteInput, basis_dict, native_input_dtype, prepare_input,
+                       prepare_vector, resolve_device, task_artifact)
 from . import mask_loader as ml
 
 
@@ -43,7 +43,11 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
 
     ``task_gram`` (default: ``config.svd_weighting == "cluster"``): every plan of unmasked parameters also leaves the
     uncentred task Gram of its tensors (svdq_plan_task_gram, a by-product of pass 1; the artifacts are byte-identical
-    either way), recorded on its BatchResult for ``clustering.task_gram(..., bases=bases)``."""
+    either way), recorded on its BatchResult for ``clustering.task_gram(..., bases=bases)``.
+
+    Raises ``NonFiniteInput`` (a RuntimeError) naming each ``'parameter' [region]`` of a plan whose task deltas hold NaN
+    or Inf among the rows processed -- where the reference's torch.linalg.svd raises (include/svdq.h,
+    svdq_eig_rank_select)."""
     if task_gram is None:
         task_gram = getattr(config, "svd_weighting", None) == "cluster"
     dev = resolve_device(device)
@@ -197,7 +201,14 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
             else:
                 plan.run(table, rows_dev)
             gram = plan.compress_task_gram() if want_gram else None
-            small = plan.fetch_small()
+            try:
+                small = plan.fetch_small()
+            except NonFiniteInput as exc:
+                # where the reference's torch.linalg.svd stops (basis.py:216-249, reached from cli.py Step 4); regions
+                # the min-mask-size gate skips have rows_dev == 0, are never read and so never flagged
+                where = ", ".join(f"{entries[i]['name']!r} [{entries[i]['region']}]" for i in exc.indices)
+                raise NonFiniteInput(exc.indices, "input matrix contained non-finite values: the task deltas of "
+                                     f"{where} hold NaN or Inf (parameter [region])") from exc
             batch = BatchResult(plan, small, [(e["name"], e["region"]) for e in entries],
                                 [e["tasks"] for e in entries])
             batch.keep = keep

@@ -100,6 +100,32 @@ def _ptr(t: Optional[torch.Tensor]) -> c_void_p:
     return c_void_p(0 if t is None else t.data_ptr())
 
 
+class NonFiniteInput(RuntimeError):
+    """A task delta of the run held NaN or +-Inf (include/svdq.h, svdq_eig_rank_select: the eigen stage flags the
+    parameter with a NaN energy).  ``indices``: the flagged parameters, as indices into the plan."""
+
+    def __init__(self, indices: Sequence[int], message: Optional[str] = None):
+        self.indices = [int(i) for i in indices]
+        super().__init__(message or "input matrix contained non-finite values "
+                         f"(plan parameters {self.indices}: NaN or Inf among their task deltas)")
+
+
+def nonfinite_parameters(small, layout, n_params: int) -> List[int]:
+    """Plan indices of the parameters the eigen stage flagged -- those whose energy is NaN -- in one packed
+    small-artifact buffer.  ``small``: the buffer as a device tensor (its energies alone are copied to the host, which
+    synchronises), a host tensor, a numpy array or anything with the buffer protocol; ``layout``: the
+    ``svdq_small_layout`` of the plan that wrote it.  For callers of ``torch.ops.svdq.*`` and of the staged entry
+    points, and for the sharded run: after ``shard.gather_small`` every rank holds every rank's buffer, tests each
+    with that rank's layout and so raises (or not) like every other rank, after the collective."""
+    n = int(n_params)
+    off = int(layout.energy_off)
+    if isinstance(small, torch.Tensor):
+        raw = small.reshape(-1).view(torch.uint8)[off:off + 4 * n].cpu().numpy()
+    else:
+        raw = np.frombuffer(small, dtype=np.uint8)[off:off + 4 * n]
+    return np.flatnonzero(np.isnan(raw.view(np.float32))).tolist()
+
+
 @dataclass
 class SmallArtifacts:
     """Host copy of the packed small-artifact buffer, as typed numpy views."""
@@ -511,6 +537,9 @@ class CompressPlan:
         status = int(host[L.status_off:L.status_off + 4].view(np.int32)[0])
         if status != 0:
             raise RuntimeError(f"svdq_compress reported status {status}; results are invalid")
+        bad = nonfinite_parameters(host, L, P)    # on the host copy: no second copy, no second synchronisation
+        if bad:
+            raise NonFiniteInput(bad)
 
         def view(off, dtype, shape):
             n = int(np.prod(shape)) * np.dtype(dtype).itemsize
