@@ -531,6 +531,40 @@ int svdq_diagnostics_masked(const svdq_plan *plan, const void *delta_ptrs_dev, c
                             const void *basis_dev, const float *mean_dev, int32_t add_mean, double *out_dev,
                             void *work_dev, void *stream);
 
+/* ---- adopt STORED artifacts into a plan (the one statement of the contract; the sources point here).  The reference
+ *      writes its artifacts one file per parameter (save_basis / save_compressed_coefficients storage.py:52-174) and merges
+ *      them again later, with other weights or another base model (load_all_artifacts storage.py:341-389 ->
+ *      reconstruct_from_artifacts reload.py:142-238 -> merge_all_parameters merge.py:304-426).  svdq_plan_import puts such
+ *      artifacts -- wherever they came from -- into the packed buffers of a plan, after which every plan-level consumer that
+ *      needs only the artifacts works on them: svdq_merge, svdq_merge_coeffs, svdq_merge_reconstruct (and, given masks and
+ *      unit starts of the caller's, svdq_merge_masked).
+ *   the plan         svdq_plan_create with rows[p] = D of the stored basis, n_tasks = the tasks that hold the parameters,
+ *                    cfg.fp16 = the stored basis is fp16 (else fp32), cfg.center = means are stored, cfg.rtvq_stages as
+ *                    stored.  It needs no compress workspace.
+ *   small_dev        the plan's small-artifact buffer, ALREADY FILLED by the caller in the published layout
+ *                    (svdq_plan_small_layout; a host image + one hipMemcpyAsync): sigma[p][0..r), k, r, energy, rows (= D;
+ *                    0 = skip the parameter), c_high[p][t][0..k), codes[p][t][s][0..r-k), scale, zero_point, residual_norm,
+ *                    status = 0.  r <= min(rows, N), k <= r.  coef holds the fp32 coefficients before rounding; no stored
+ *                    artifact has them: they are ZERO on an adopted plan (no consumer above reads them).
+ *   u_high_ptrs_dev  device table [P] of U_high [rows, k]; u_low_ptrs_dev: [P] of U_low [rows, r - k]; mean_ptrs_dev: [P] of
+ *                    mean [rows] fp32, NULL exactly when cfg.center == 0 (mean_dev may then be NULL too).  Element type of
+ *                    U: fp16 / fp32 as cfg.fp16 says.  Every source is on the device, row-major and contiguous and starts
+ *                    on a 16-byte boundary (the caller's contract: the addresses live on the device, the host cannot see
+ *                    them; what it can see -- NULL tables or buffers, tables off 8 bytes, buffers off 16 -- is SVDQ_EINVAL).
+ *                    A table entry whose tensor is empty (k = 0, r = k, rows = 0) is never dereferenced.
+ *   what it does     ONE streaming launch over the plan's own work units: the unit (p, row0, nrows) copies rows
+ *                    [row0, min(row0 + nrows, rows)) of U_high to slab_off[p], of U_low to slab_off[p] +
+ *                    align256(rows * k * e), of mean to mean_off[p] (svdq_plan_basis_layout) -- each a contiguous byte
+ *                    range of a row-major tensor, 16-byte aligned at both ends except a parameter's last bytes.  k, r and
+ *                    rows are read from small_dev ON THE DEVICE (held to the slab: rows <= plan rows, r <= min(rows, N),
+ *                    k <= r), so the call copies nothing to the host, synchronises nothing, allocates nothing and is
+ *                    capturable like every other entry point.  rows[p] == 0: nothing of p is read or written.  Nothing is
+ *                    written outside the three ranges of a parameter -- not the gap between U_high and U_low, not a slab's
+ *                    or the buffers' tails.  small_dev is only read. */
+int svdq_plan_import(const svdq_plan *plan, const void *u_high_ptrs_dev /*[P]*/, const void *u_low_ptrs_dev /*[P]*/,
+                     const void *mean_ptrs_dev /*[P], NULL when center == 0*/, const void *small_dev, void *basis_dev,
+                     float *mean_dev, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

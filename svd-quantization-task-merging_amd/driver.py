@@ -10,8 +10,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .pipeline import (BatchResult, CompressPlan, NonFiniteInput, basis_dict, native_input_dtype, prepare_input,
-                       prepare_vector, resolve_device, task_artifact)
+from . import _native as nat
+from .pipeline import (BatchResult, CompressPlan, NonFiniteInput, basis_dict, native_input_dtype, pack_small,
+                       prepare_input, prepare_vector, resolve_device, small_views, task_artifact)
 from . import mask_loader as ml
 
 
@@ -345,3 +346,330 @@ def run_basis_and_compress_from_checkpoints(base_state: Dict[str, torch.Tensor],
     from .compress import compress_all_parameters
     bases = build_bases(finetuned_states, combined_masks, config, device, base_state=base_state, task_gram=task_gram)
     return bases, compress_all_parameters(finetuned_states, combined_masks or {}, bases, config, device)
+
+
+# ------------------------------------------------------------------------------------------------ stored artifacts
+_REGIONS = (("masked", "masked"), ("noise", "unmasked"))      # (key in a basis file, key in a task's artifact)
+
+
+def _adoptable(basis, artifacts) -> Optional[str]:
+    """Why the stored artifacts of ONE region of one parameter cannot be adopted into a plan (``adopt_artifacts``), or
+    None when they can.  ``basis``: the region's basis dictionary (U_high, U_low, k, mean, ...); ``artifacts``: the
+    region's artifact {c_high_fp16, c_low_quant} of every task that holds it, in plan order.  Reads shapes, dtypes and
+    scalars only -- no tensor data, no GPU."""
+    n = len(artifacts)
+    if n < 1:
+        return "no task holds the region"
+    if n > nat.MAX_TASKS:
+        return f"more than {nat.MAX_TASKS} tasks"
+    if not isinstance(basis, dict):
+        return "the basis is not a dictionary"
+    uh, ul, k = basis.get("U_high"), basis.get("U_low"), basis.get("k")
+    if not (isinstance(uh, torch.Tensor) and isinstance(ul, torch.Tensor) and uh.dim() == 2 and ul.dim() == 2):
+        return "U_high / U_low are not matrices"
+    if uh.dtype != ul.dtype:
+        return "U_high and U_low have different dtypes"
+    if uh.dtype not in (torch.float16, torch.float32):
+        return f"basis dtype {uh.dtype} is neither fp16 nor fp32"
+    D = int(uh.shape[0])
+    if D < 1 or int(ul.shape[0]) != D or int(basis.get("D", D)) != D:
+        return "U_high, U_low and D disagree on the row count"
+    if isinstance(k, bool) or not isinstance(k, int) or int(uh.shape[1]) != k:
+        return "U_high.shape[1] != k"
+    n_low = int(ul.shape[1])
+    r = k + n_low
+    if r > min(D, n):
+        return "k + n_low exceeds min(D, tasks that hold the region)"
+    mean, sv = basis.get("mean"), basis.get("singular_values")
+    if mean is not None and not (isinstance(mean, torch.Tensor) and mean.dtype is torch.float32 and mean.numel() == D):
+        return "mean is not an fp32 tensor of D elements"
+    if not (isinstance(sv, torch.Tensor) and sv.dim() == 1 and sv.is_floating_point()):
+        return "singular_values is not a vector"
+    bits = stages = None
+    for a in artifacts:
+        if not isinstance(a, dict):
+            return "a task's artifact is not a dictionary"
+        ch, q = a.get("c_high_fp16"), a.get("c_low_quant")
+        if not (isinstance(ch, torch.Tensor) and ch.dtype is torch.float16 and ch.dim() == 1 and ch.numel() == k):
+            return "c_high_fp16 is not an fp16 row of k elements"
+        if not isinstance(q, dict):
+            return "c_low_quant is not a dictionary"
+        b, s, shape, pays = q.get("num_bits"), q.get("num_stages"), q.get("original_shape"), q.get("payloads")
+        if not isinstance(b, int) or not 1 <= b <= 8:
+            return "num_bits outside 1..8"
+        if not isinstance(s, int) or not 1 <= s <= nat.MAX_STAGES:
+            return f"num_stages outside 1..{nat.MAX_STAGES}"
+        if bits is None:
+            bits, stages = b, s
+        elif (b, s) != (bits, stages):
+            return "the tasks disagree on num_bits / num_stages"
+        if shape is None or len(shape) != 1 or k + int(shape[0]) != r:
+            return "k + n_low != U_high.shape[1] + U_low.shape[1]"
+        if not isinstance(pays, (list, tuple)) or len(pays) != (s if n_low > 0 or pays else 0):
+            return "payload count != num_stages"
+        for pl in pays:
+            if not isinstance(pl, dict):
+                return "a payload is not a dictionary"
+            qz, sc, zp = pl.get("quantized"), pl.get("scale"), pl.get("zero_point")
+            if not (isinstance(qz, torch.Tensor) and qz.dtype is torch.uint8 and qz.numel() == n_low):
+                return "a quantized row is not uint8 of n_low elements"
+            for x in (sc, zp):
+                if not (isinstance(x, torch.Tensor) and x.dtype is torch.float32 and x.numel() == 1):
+                    return "scale / zero_point is not one fp32 value"
+    return None
+
+
+def _adoption_groups(bases, compressed_all):
+    """The GPU-free half of ``adopt_artifacts``: which (parameter, region) pairs go into which plan.  Returns
+    ``(groups, declined)``: groups = {(tasks present, num_stages, basis dtype, mean is None): [entry]} with entry =
+    {name, region, art_key, basis, tasks, artifacts, bits}, in the dictionaries' order; declined = {name: reason}.  A
+    parameter is adopted with ALL its regions or not at all (the batched consumers take both regions of a parameter
+    from plans, or neither); a task that lacks a region is simply not among that entry's tasks, as in ``build_bases``."""
+    groups: Dict[Tuple, List[dict]] = {}
+    declined: Dict[str, str] = {}
+    for name, b in bases.items():
+        per_task = compressed_all.get(name)
+        if not isinstance(b, dict) or not isinstance(per_task, dict):
+            declined[name] = "no basis / coefficient dictionaries"
+            continue
+        if isinstance(per_task, LazyArtifacts) and per_task._batch is not None:
+            declined[name] = "already backed by a plan"
+            continue
+        if b.get("masked") is None:
+            declined[name] = "no masked basis"
+            continue
+        found, why = [], None
+        for region, art_key in _REGIONS:
+            rb = b.get(region)
+            if rb is None:
+                continue
+            present = [(t, a[art_key]) for t, a in per_task.items() if isinstance(a, dict) and a.get(art_key) is not None]
+            try:
+                why = _adoptable(rb, [a for _, a in present])
+            except Exception as exc:      # adoption never raises on data: whatever is malformed goes per parameter
+                why = f"malformed ({type(exc).__name__})"
+            if why is not None:
+                why = f"[{region}] {why}"
+                break
+            q0 = present[0][1]["c_low_quant"]
+            found.append(((len(present), int(q0["num_stages"]), rb["U_high"].dtype, rb.get("mean") is None),
+                          {"name": name, "region": region, "art_key": art_key, "basis": rb,
+                           "tasks": [t for t, _ in present], "artifacts": [a for _, a in present],
+                           "bits": int(q0["num_bits"])}))
+        if why is not None:
+            declined[name] = why
+            continue
+        for key, e in found:
+            groups.setdefault(key, []).append(e)
+    return groups, declined
+
+
+class _AdoptedViews:
+    """What ``pipeline.task_artifact`` hands out for an adopted plan: the caller's own artifact dictionaries."""
+
+    def __init__(self, artifacts):
+        self.artifacts = artifacts
+
+
+def _host_arrays(tensors):
+    """numpy copies of many small tensors with one device-to-host copy per (device, dtype) instead of one per tensor
+    (artifacts loaded with ``device="cuda"`` hold ~10^4 payload tensors per model)."""
+    import numpy as np
+    out = [None] * len(tensors)
+    by_home: Dict[Tuple, List[int]] = {}
+    for i, t in enumerate(tensors):
+        if t.device.type == "cpu":
+            out[i] = t.detach().reshape(-1).numpy()
+        else:
+            by_home.setdefault((t.device, t.dtype), []).append(i)
+    for idx in by_home.values():
+        flat = torch.cat([tensors[i].detach().reshape(-1) for i in idx]).cpu().numpy()
+        pos = 0
+        for i in idx:
+            n = tensors[i].numel()
+            out[i] = flat[pos:pos + n]
+            pos += n
+    return out
+
+
+def _gather_each(entries, N: int, S: int) -> List[dict]:
+    """The ``pack_small`` entries of one plan, tensor by tensor (any shapes and devices ``_adoptable`` lets through)."""
+    import numpy as np
+    flat, packed = [], []
+    for e in entries:
+        flat.append(e["basis"]["singular_values"])
+        for a in e["artifacts"]:
+            flat.append(a["c_high_fp16"])
+            for pl in a["c_low_quant"]["payloads"]:
+                flat += [pl["quantized"], pl["scale"], pl["zero_point"]]
+    host = iter(_host_arrays(flat))
+    for e in entries:
+        b = e["basis"]
+        k, n_low = int(b["k"]), int(b["U_low"].shape[1])
+        sig = np.asarray(next(host), dtype=np.float32).reshape(-1)
+        sigma = np.zeros(k + n_low, dtype=np.float32)
+        sigma[:min(sig.size, k + n_low)] = sig[:k + n_low]
+        ch = np.zeros((N, k), dtype=np.float16)
+        codes = np.zeros((N, S, n_low), dtype=np.uint8)
+        sc, zp, rn = (np.zeros((N, S), dtype=np.float32) for _ in range(3))
+        for t, a in enumerate(e["artifacts"]):
+            ch[t] = next(host)
+            for s_, pl in enumerate(a["c_low_quant"]["payloads"]):
+                codes[t, s_] = next(host)
+                sc[t, s_] = next(host)[0]
+                zp[t, s_] = next(host)[0]
+                rn[t, s_] = np.float32(pl.get("residual_norm", 0.0))
+        packed.append({"rows": int(b["U_high"].shape[0]), "k": k, "r": k + n_low,
+                       "energy": b.get("energy_retained", 0.0), "sigma": sigma, "c_high": ch, "codes": codes,
+                       "scale": sc, "zero_point": zp, "residual_norm": rn})
+    return packed
+
+
+def _gather_bulk(entries, N: int, S: int) -> List[dict]:
+    """The same from ONE concatenation per field (and one device-to-host copy each when the artifacts were loaded onto
+    the GPU): a model's ~17 000 payload tensors cost 9 us each when taken to numpy one by one, more than everything else
+    in adoption together.  Needs what the writers produce -- 1-D rows, scales of one shape, every task of a parameter
+    with all its stages or (no low columns) none; raises otherwise, and ``_gather_small`` goes tensor by tensor."""
+    import numpy as np
+
+    def host(ts, dtype, join=torch.cat):
+        if not ts:
+            return np.zeros(0, dtype=dtype)
+        return join(ts).reshape(-1).cpu().numpy().astype(dtype, copy=False)
+
+    arts = [a for e in entries for a in e["artifacts"]]
+    pays = [pl for a in arts for pl in a["c_low_quant"]["payloads"]]
+    sig = [e["basis"]["singular_values"] for e in entries]
+    sigma = host(sig, np.float32)
+    ch = host([a["c_high_fp16"] for a in arts], np.float16)
+    qz = host([pl["quantized"] for pl in pays], np.uint8)
+    sc = host([pl["scale"] for pl in pays], np.float32, torch.stack)
+    zp = host([pl["zero_point"] for pl in pays], np.float32, torch.stack)
+    rn = np.array([pl.get("residual_norm", 0.0) for pl in pays], dtype=np.float32)
+    packed, i_sig, i_ch, i_qz, i_pl = [], 0, 0, 0, 0
+    for e, sv in zip(entries, sig):
+        b = e["basis"]
+        k, n_low = int(b["k"]), int(b["U_low"].shape[1])
+        r = k + n_low
+        counts = {len(a["c_low_quant"]["payloads"]) for a in e["artifacts"]}
+        if len(counts) != 1:
+            raise ValueError("the tasks of a parameter differ in their number of payloads")
+        stages = counts.pop()
+        n_sv = int(sv.numel())
+        sg = np.zeros(r, dtype=np.float32)
+        sg[:min(n_sv, r)] = sigma[i_sig:i_sig + min(n_sv, r)]
+        i_sig += n_sv
+        codes = np.zeros((N, S, n_low), dtype=np.uint8)
+        s_, z_, n_ = (np.zeros((N, S), dtype=np.float32) for _ in range(3))
+        if stages:
+            codes[:, :stages] = qz[i_qz:i_qz + N * stages * n_low].reshape(N, stages, n_low)
+            s_[:, :stages] = sc[i_pl:i_pl + N * stages].reshape(N, stages)
+            z_[:, :stages] = zp[i_pl:i_pl + N * stages].reshape(N, stages)
+            n_[:, :stages] = rn[i_pl:i_pl + N * stages].reshape(N, stages)
+        packed.append({"rows": int(b["U_high"].shape[0]), "k": k, "r": r, "energy": b.get("energy_retained", 0.0),
+                       "sigma": sg, "c_high": ch[i_ch:i_ch + N * k].reshape(N, k), "codes": codes, "scale": s_,
+                       "zero_point": z_, "residual_norm": n_})
+        i_ch, i_qz, i_pl = i_ch + N * k, i_qz + N * stages * n_low, i_pl + N * stages
+    if (i_sig, i_ch, i_qz, i_pl) != (sigma.size, ch.size, qz.size, sc.size) or sc.size != zp.size:
+        raise ValueError("the concatenated fields do not have the sizes the shapes promise")
+    return packed
+
+
+def _gather_small(entries, N: int, S: int) -> List[dict]:
+    try:
+        return _gather_bulk(entries, N, S)
+    except Exception:      # unusual shapes, tensors spread over devices: nothing is lost but time
+        return _gather_each(entries, N, S)
+
+
+def _device_source(t: Optional[torch.Tensor], dev, dtype) -> Optional[torch.Tensor]:
+    """A source tensor of svdq_plan_import: on ``dev``, contiguous, 16-byte aligned; the tensor itself when it is."""
+    if t is None or t.numel() == 0:
+        return None
+    v = t.detach()
+    if v.device != dev or v.dtype is not dtype:
+        v = v.to(device=dev, dtype=dtype)
+    v = v.contiguous()
+    return v.clone() if v.data_ptr() & 15 else v
+
+
+def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], config, device="cuda"
+                    ) -> Tuple[Dict[str, Dict], Dict[str, Dict]]:
+    """Put artifacts that did NOT come out of a fused run in this process -- the reference-layout dictionaries
+    ``load_all_artifacts`` returns, tensors on the CPU or the GPU -- into plans, so that ``merge_all_parameters``,
+    ``merge_with_clustering`` and ``reconstruct_from_artifacts`` serve them in two launches per plan (svdq_merge)
+    instead of a payload upload, a dequantize launch and a reconstruct launch per (parameter, task).
+
+    Returns ``(bases, compressed_all)``: new dictionaries with the same keys and the same values, field by field and
+    dtype by dtype (the basis tensors now views of a plan's packed buffers on ``device``; the per-task artifact
+    dictionaries the caller's own objects), whose entries are ``LazyArtifacts`` backed by adopted plans -- built as
+    ``build_bases`` / ``artifacts_from_batch`` build theirs, with ``BatchResult.mode = "plain"`` and no table, unit
+    starts or kept inputs: ``merge._batched_entry`` accepts them, masked parameters take the compacted-rows route with
+    the CALLER's mask (masks are not stored: reference reload.py:204-205), the batched diagnostics skip them (there are
+    no task vectors to measure against).  Assigning into an adopted entry sends that parameter back to the
+    per-parameter route, as for a fused run's.
+
+    One plan per (tasks that hold the region, num_stages, basis dtype, mean is None); "masked" and "noise" regions are
+    entries of their own; ``num_bits`` is per parameter (svdq_plan_set_low_bits).  What a plan cannot express is
+    declined silently, parameter by parameter, and handed back exactly as it came (``_adoptable`` lists the reasons:
+    more than 32 tasks, shapes that disagree with k / n_low, other dtypes, ...), so the per-parameter route serves it
+    as before.  Adoption never raises on data.
+
+    Memory: while a plan is being filled its sources and its packed copy coexist (4.9 GB twice at ViT-L-14 x 8).
+    Plans are filled one after the other, and the device copies made of CPU tensors are dropped before the next plan;
+    sources that already live on the device are read where they are and stay the caller's to release (drop the
+    dictionaries that were passed in)."""
+    dev = resolve_device(device)
+    groups, _ = _adoption_groups(bases, compressed_all)
+    new_bases = dict(bases)
+    new_comp = dict(compressed_all)
+    where: Dict[Tuple[str, str], Tuple[BatchResult, int]] = {}
+    for (n_tasks, stages, udt, no_mean), entries in groups.items():
+        P, N, S = len(entries), n_tasks, stages
+        try:
+            plan = CompressPlan([int(e["basis"]["U_high"].shape[0]) for e in entries], N,
+                                energy_threshold=config.svd_energy_threshold, max_rank=config.svd_max_rank,
+                                center=not no_mean, fp16=udt is torch.float16, low_bits=[e["bits"] for e in entries],
+                                rtvq_stages=S, device=dev, workspace=False)
+        except ValueError:      # a set the library has no plan for (SVDQ_EINVAL): these parameters stay as they came
+            continue
+        packed = _gather_small(entries, N, S)
+        small_host = pack_small(plan.layout, P, N, S, packed)
+        # the sources of the one copy launch; device copies of CPU tensors live until the end of this iteration only
+        uh = [_device_source(e["basis"]["U_high"], dev, udt) for e in entries]
+        ul = [_device_source(e["basis"]["U_low"], dev, udt) for e in entries]
+        mn = None if no_mean else [_device_source(e["basis"]["mean"].reshape(-1), dev, torch.float32) for e in entries]
+        plan.import_artifacts(uh, ul, mn, small_host)
+        del uh, ul, mn
+        small = small_views(small_host, plan.layout, P, N, S)
+        small._host_views = _AdoptedViews([e["artifacts"] for e in entries])
+        batch = BatchResult(plan, small, [(e["name"], e["region"]) for e in entries], [e["tasks"] for e in entries])
+        batch.keep = None
+        batch.mode, batch.table, batch.rows_dev = "plain", None, None
+        batch.mask_table, batch.unit_start, batch.mask_ident = None, None, {}
+        batch.from_base, batch.task_gram, batch.adopted = False, None, True
+        plan._keep = None
+        for i, e in enumerate(entries):
+            where[(e["name"], e["region"])] = (batch, i)
+    for (name, region), (batch, i) in where.items():
+        if new_bases[name] is bases[name]:
+            new_bases[name] = dict(bases[name])
+        orig = bases[name][region]
+
+        def fill_basis(pl=batch.plan, sm=batch.small, q=i, orig=orig):
+            d = basis_dict(pl, sm, q)
+            out = dict(orig.items())      # the caller's keys, order and scalars; the tensors that now live in the plan
+            out.update(U_high=d["U_high"], U_low=d["U_low"],
+                       mean=d["mean"].view(orig["mean"].shape) if d["mean"] is not None else None)
+            sv = orig["singular_values"]
+            if sv.dtype is torch.float32 and sv.numel() == d["singular_values"].numel():
+                out["singular_values"] = d["singular_values"]
+            return out
+        new_bases[name][region] = LazyArtifacts(fill_basis, (batch, i))
+    for name in {n for n, _ in where}:
+        per_task = compressed_all[name]
+        mb, mi = where[(name, "masked")]
+        new_comp[name] = LazyArtifacts((lambda d=per_task: dict(d.items())), batch=(mb, mi),
+                                       meta={"have": list(per_task.keys()), "tasks": mb.task_names[mi],
+                                             "noise": where.get((name, "noise"))})
+    return new_bases, new_comp

@@ -150,11 +150,16 @@ def _batched_entry(name, compressed_all, bases):
             npos = {t: q for q, t in enumerate(nb.task_names[j])}
         for t in meta["have"]:
             art = dict.__getitem__(ca, t)
-            if not isinstance(art, dict) or set(art.keys()) != {"masked", "unmasked"}:
+            if not isinstance(art, dict):
+                return None
+            # a fused run hands out both keys; stored files hold only the regions a task has (storage.py:137-174), and
+            # an adopted plan (driver.adopt_artifacts) answers with the caller's own artifact dictionaries
+            if not (set(art.keys()) <= {"masked", "unmasked"} if getattr(batch, "adopted", False)
+                    else set(art.keys()) == {"masked", "unmasked"}):
                 return None
             want_m = task_artifact(batch.plan, batch.small, i, pos[t]) if t in pos else None
             want_u = task_artifact(nb.plan, nb.small, j, npos[t]) if (npos is not None and t in npos) else None
-            if art["masked"] is not want_m or art["unmasked"] is not want_u:
+            if art.get("masked") is not want_m or art.get("unmasked") is not want_u:
                 return None
     return bm._batch[0], bm._batch[1], meta
 

@@ -142,13 +142,65 @@ class SmallArtifacts:
     coef: np.ndarray       # [P, N, N] f32
 
 
+def small_views(host: np.ndarray, L, P: int, N: int, S: int) -> SmallArtifacts:
+    """The typed views of one packed small-artifact buffer (``host``: its bytes as a uint8 array; ``L``: the
+    ``svdq_small_layout`` it was written in).  No copy: writing through a view writes the buffer."""
+    def view(off, dtype, shape):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return host[off:off + n].view(dtype).reshape(shape)
+
+    return SmallArtifacts(
+        sigma=view(L.sigma_off, np.float32, (P, N)), k=view(L.k_off, np.int32, (P,)),
+        r=view(L.r_off, np.int32, (P,)), energy=view(L.energy_off, np.float32, (P,)),
+        rows=view(L.rows_off, np.int64, (P,)), c_high=view(L.chigh_off, np.float16, (P, N, N)),
+        codes=view(L.codes_off, np.uint8, (P, N, S, N)), scale=view(L.scale_off, np.float32, (P, N, S)),
+        zero_point=view(L.zp_off, np.float32, (P, N, S)), residual_norm=view(L.rnorm_off, np.float32, (P, N, S)),
+        coef=view(L.coef_off, np.float32, (P, N, N)))
+
+
+def pack_small(layout, P: int, N: int, S: int, entries: Sequence[Optional[Dict]]) -> np.ndarray:
+    """The bytes of a plan's small-artifact buffer (include/svdq.h, svdq_small_layout) from per-parameter artifact
+    values -- what ``CompressPlan.import_artifacts`` uploads.  A pure function of its arguments (``layout`` is any object
+    with the ``*_off`` / ``total_bytes`` attributes), so it needs no GPU.  ``entries[p]`` is None (rows = 0: the
+    parameter is skipped by every consumer) or a dict of
+        rows, k, r, energy                scalars (r = singular values kept, k <= r <= N)
+        sigma [r]                         float32
+        c_high [N][k]                     float16
+        codes [N][S][r - k]               uint8
+        scale, zero_point, residual_norm  [N][S] float32
+    Only the valid elements are written: everything else -- the padding between fields, sigma beyond r, c_high beyond
+    k, codes beyond r - k, the fp32 coefficients ``coef`` (no stored artifact has them) and ``status`` -- is zero."""
+    if len(entries) != P:
+        raise ValueError(f"expected {P} entries, got {len(entries)}")
+    buf = np.zeros(int(layout.total_bytes), dtype=np.uint8)
+    v = small_views(buf, layout, P, N, S)
+    for p, e in enumerate(entries):
+        if e is None:
+            continue
+        k, r = int(e["k"]), int(e["r"])
+        if not (0 <= k <= r <= N):
+            raise ValueError(f"entry {p}: need 0 <= k <= r <= N, got k = {k}, r = {r}, N = {N}")
+        v.k[p], v.r[p], v.rows[p] = k, r, int(e["rows"])
+        v.energy[p] = np.float32(e["energy"])
+        v.sigma[p, :r] = np.asarray(e["sigma"], dtype=np.float32).reshape(-1)[:r]
+        if k > 0:
+            v.c_high[p, :, :k] = np.asarray(e["c_high"], dtype=np.float16).reshape(N, k)
+        if r > k:
+            v.codes[p, :, :, :r - k] = np.asarray(e["codes"], dtype=np.uint8).reshape(N, S, r - k)
+        v.scale[p] = np.asarray(e["scale"], dtype=np.float32).reshape(N, S)
+        v.zero_point[p] = np.asarray(e["zero_point"], dtype=np.float32).reshape(N, S)
+        v.residual_norm[p] = np.asarray(e["residual_norm"], dtype=np.float32).reshape(N, S)
+    return buf
+
+
 class CompressPlan:
     """Owns one ``svdq_plan`` plus its device buffers (workspace, basis slabs, means, small)."""
 
     def __init__(self, rows: Sequence[int], n_tasks: int, *, energy_threshold: float = 0.90,
                  max_rank: Optional[int] = None, center: bool = True, fp16: bool = True,
                  low_bits: int = 4, rtvq_stages: int = 2, device="cuda", unit_rows: int = 0, flags: int = 0,
-                 gram_only: bool = False, input_dtype: torch.dtype = torch.float32, task_gram: bool = False):
+                 gram_only: bool = False, input_dtype: torch.dtype = torch.float32, task_gram: bool = False,
+                 workspace: bool = True):
         if input_dtype not in INPUT_TYPES:
             raise ValueError(f"input_dtype must be one of {list(INPUT_TYPES)}, got {input_dtype}")
         if task_gram and gram_only:
@@ -197,7 +249,9 @@ class CompressPlan:
         self.slab_off = list(slab)
         self.mean_off = list(moff)
         dev = self.device
-        self.workspace = torch.empty(self.sizes.workspace_bytes, dtype=torch.uint8, device=dev)
+        # workspace=False: a plan that only adopts stored artifacts (import_artifacts) and feeds the consumers never
+        # compresses, so it carries no compress workspace (the run / stage methods then have nothing to write to)
+        self.workspace = torch.empty(self.sizes.workspace_bytes, dtype=torch.uint8, device=dev) if workspace else None
         self.small = torch.zeros(self.sizes.small_bytes, dtype=torch.uint8, device=dev)
         # gram_only: a plan used for svdq_task_gram alone needs no basis / mean storage
         self.basis, self.mean = (None, None) if gram_only else self._alloc_outputs()
@@ -363,6 +417,48 @@ class CompressPlan:
                                                           _ptr(index_table), _ptr(rows_dev), _ptr(self.workspace),
                                                           _ptr(self.small), _ptr(self.basis), _ptr(self.mean),
                                                           _stream_ptr()), "svdq_compress_gather_from_base")
+
+    # ---- stored artifacts in (svdq_import.hip)
+    def import_artifacts(self, u_high: Sequence[Optional[torch.Tensor]], u_low: Sequence[Optional[torch.Tensor]],
+                         mean: Optional[Sequence[Optional[torch.Tensor]]], small_host: np.ndarray) -> None:
+        """Adopt stored artifacts (include/svdq.h, svdq_plan_import): ``small_host`` -- the packed small buffer as
+        ``pack_small`` builds it -- goes to the device in one copy, and ONE launch copies every parameter's ``u_high[p]``
+        [rows, k], ``u_low[p]`` [rows, r - k] and ``mean[p]`` [rows] (``mean`` is None exactly on an uncentred plan) into
+        the plan's packed basis and mean buffers; k, r and rows are read from the small buffer on the device.  The
+        tensors must be on the plan's device, contiguous, 16-byte aligned, in the plan's basis dtype (means: float32);
+        an entry may be None or empty where the small buffer gives it no elements.  Asynchronous on the current stream;
+        the sources may be dropped as soon as this returns (the allocator orders their reuse behind the launch)."""
+        if self.basis is None:
+            raise ValueError("a gram_only plan has no basis storage to adopt artifacts into")
+        if (mean is None) == self.center:
+            raise ValueError("mean tensors are required exactly on a centred plan")
+        raw = np.ascontiguousarray(small_host).reshape(-1).view(np.uint8)
+        if raw.size != int(self.sizes.small_bytes):
+            raise ValueError(f"small buffer of {raw.size} bytes, the plan's layout has {int(self.sizes.small_bytes)}")
+        udt = torch.float16 if self.fp16 else torch.float32
+        ptrs = []
+        for what, seq, dt in (("U_high", u_high, udt), ("U_low", u_low, udt), ("mean", mean, torch.float32)):
+            if seq is None:
+                continue
+            if len(seq) != self.P:
+                raise ValueError(f"{what}: expected {self.P} tensors, got {len(seq)}")
+            for p, t in enumerate(seq):
+                if t is None or t.numel() == 0:
+                    ptrs.append(0)
+                    continue
+                if t.dtype is not dt or t.device != self.device or not t.is_contiguous() or t.data_ptr() & 15:
+                    raise ValueError(f"{what} of parameter {p} must be a contiguous, 16-byte aligned {dt} tensor on "
+                                     f"{self.device}")
+                ptrs.append(t.data_ptr())
+        with torch.cuda.device(self.device):
+            table = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
+            self.small.copy_(torch.from_numpy(raw))
+            P8 = self.P * 8
+            mp = c_void_p(table.data_ptr() + 2 * P8) if mean is not None else c_void_p(0)
+            nat.check(self.lib.svdq_plan_import(self._h, c_void_p(table.data_ptr()), c_void_p(table.data_ptr() + P8), mp,
+                                                _ptr(self.small), _ptr(self.basis), _ptr(self.mean), _stream_ptr()),
+                      "svdq_plan_import")
+        self._typed = None
 
     # ---- consumers of the artifacts, batched over the plan (svdq_merge.hip)
     def new_merged_outputs(self):
@@ -540,18 +636,7 @@ class CompressPlan:
         bad = nonfinite_parameters(host, L, P)    # on the host copy: no second copy, no second synchronisation
         if bad:
             raise NonFiniteInput(bad)
-
-        def view(off, dtype, shape):
-            n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-            return host[off:off + n].view(dtype).reshape(shape)
-
-        return SmallArtifacts(
-            sigma=view(L.sigma_off, np.float32, (P, N)), k=view(L.k_off, np.int32, (P,)),
-            r=view(L.r_off, np.int32, (P,)), energy=view(L.energy_off, np.float32, (P,)),
-            rows=view(L.rows_off, np.int64, (P,)), c_high=view(L.chigh_off, np.float16, (P, N, N)),
-            codes=view(L.codes_off, np.uint8, (P, N, S, N)), scale=view(L.scale_off, np.float32, (P, N, S)),
-            zero_point=view(L.zp_off, np.float32, (P, N, S)), residual_norm=view(L.rnorm_off, np.float32, (P, N, S)),
-            coef=view(L.coef_off, np.float32, (P, N, N)))
+        return small_views(host, L, P, N, S)
 
     def basis_tensors(self, p: int, k: int, r: int, rows: int) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """Zero-copy views (U_high [rows,k], U_low [rows,r-k], mean [rows,1] | None) of parameter p."""

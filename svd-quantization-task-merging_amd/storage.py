@@ -184,8 +184,12 @@ def reconstruct_from_artifacts(artifact_dir: str, base_model_path, output_path: 
     (reload.py:204-205), so this is exact for unmasked runs only -- as in the reference.
     ``base_model_path`` may also be an already-loaded state dict."""
     from .merge import apply_merged_deltas, merge_all_parameters
+    from .driver import adopt_artifacts
     art = load_all_artifacts(artifact_dir, device=device)
-    bases, compressed, config, diagnostics = art["bases"], art["compressed"], art["config"], art["diagnostics"]
+    config, diagnostics = art["config"], art["diagnostics"]
+    # into plans: the merge below then takes two launches per plan (svdq_plan_import + svdq_merge) instead of a payload
+    # upload, a dequantize and a reconstruct launch per (parameter, task); what adoption declines stays as loaded
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
     tasks = list(diagnostics.get("task_weights", {}).keys())
     if not tasks:
         tasks = list(next(iter(compressed.values())).keys())
