@@ -509,6 +509,36 @@ int svdq_diagnostics(const svdq_plan *plan, const void *delta_ptrs_dev, const in
                      const void *basis_dev, const float *mean_dev, int32_t add_mean, double *out_dev, void *work_dev,
                      void *stream);
 
+/* ---- every task's OWN reconstruction for a whole plan, in one pass over the basis: what the reference does per
+ *      (parameter, task) with RTVQQuantizer.dequantize (rtvq.py:85-103) + reconstruct_from_coefficients
+ *      (merge.py:144-194), and apply_merged_deltas (merge.py:429-552) when a base is given -- "give me task t's model
+ *      back" for one task, several or all.  Two launches per plan: the selected tasks' coefficients straight from the
+ *      small-artifact buffer (c_high, dequantized c_low), then ONE streaming launch over the plan's units that reads a
+ *      block of U_high / U_low / mean (and base) rows once and writes every selected task's rows:
+ *        out[p][j][d] = ((U_high c_j,high + U_low c_j,low)[d] + mean[d]) * scale[p]   (base[p][d] + that, given base)
+ *      with c_j the coefficients of plan task task_dev[j].  Per-row arithmetic is svdq_reconstruct's and
+ *      svdq_merge_reconstruct's (fp32 fma chains from 0 over the U_high columns in order, a separate chain over the U_low
+ *      columns, hi + lo, + mean on a centred plan, * scale, base + res): out[p][j] is bit for bit svdq_reconstruct on
+ *      that task's coefficients and bit for bit svdq_merge with the one-hot set {task_dev[j]: 1.0}.
+ *   task_dev      int32 [n_out] plan task indices, 1 <= n_out <= SVDQ_MAX_TASKS; duplicates are allowed.  NULL or an
+ *                 n_out outside the range is SVDQ_EINVAL before anything is launched.  The indices themselves live on the
+ *                 device, where this call cannot see them (it copies nothing to the host): the caller that builds the
+ *                 table checks them against [0, N) -- CompressPlan.reconstruct_tasks does, and refuses with the same
+ *                 error -- and on the device an index outside [0, N) is skipped like a NULL output.
+ *   out_ptrs_dev  [P][n_out] fp32 outputs of rows[p] elements (compacted rows for masked regions: svdq_mask_expand
+ *                 scatters them); a NULL entry = that (parameter, task) is neither formed nor written (a task that lacks
+ *                 the parameter).  Nothing is written past rows[p] elements of any output.
+ *   rows_dev, scale_dev, base_ptrs_dev: as for svdq_merge_reconstruct; rows[p] == 0: nothing of p is read or written.
+ *   work_dev      svdq_task_reconstruct_work_bytes(plan, n_out) bytes (0 for an n_out outside the range).
+ *   Allocates nothing, copies nothing to the host, synchronises nothing: capturable like every other entry point.
+ *   Works on plans filled by any compress route and on plans filled by svdq_plan_import. */
+int64_t svdq_task_reconstruct_work_bytes(const svdq_plan *plan, int32_t n_out);
+int svdq_task_reconstruct(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                          const float *mean_dev, const int32_t *task_dev /*[n_out] plan task indices*/, int32_t n_out,
+                          const float *scale_dev /*NULL or [P]*/, const void *base_ptrs_dev /*NULL or [P]*/,
+                          const void *out_ptrs_dev /*[P][n_out] fp32 outputs of rows[p] elements; NULL entry = skip*/,
+                          void *work_dev, void *stream);
+
 /* ---- the same for MASKED regions, with reconstruct_from_masked (mask_loader.py:712-763: zeros; result[mask] = signal;
  *      result[~mask] = noise) and apply_mask_to_tensor (:651-679, the "original" of the masked diagnostics,
  *      diagnostics.py:186-199) inside the streaming launch: the plan's artifacts describe the COMPACTED rows of every

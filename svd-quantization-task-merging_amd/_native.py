@@ -121,6 +121,9 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svdq_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "svdq_task_reconstruct_work_bytes": (c_int64, [c_void_p, c_int32]),
+    "svdq_task_reconstruct": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     "svdq_diagnostics_work_bytes": (c_int64, [c_void_p]),
     "svdq_diagnostics": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                    c_void_p, c_void_p]),

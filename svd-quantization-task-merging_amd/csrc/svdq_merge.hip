@@ -12,6 +12,9 @@
 //                        weighting.py:332-372 -- the merge is linear, so any number of clusters costs one pass over U),
 //                        + base (apply_merged_deltas merge.py:429-552) when asked.  HBM-bound: reads the basis once
 //                        (e (k + nl) B/row), mean and base, writes 4 B/row.
+//   k_task_coeff / k_task_reconstruct  every selected task's OWN reconstruction (RTVQQuantizer.dequantize rtvq.py:85-103 +
+//                        reconstruct_from_coefficients merge.py:144-194 per task, + base merge.py:429-552) from ONE pass over
+//                        the basis: n_out outputs per parameter, each the bits of a merge with that task as a one-hot set.
 //   k_merge_expand       the same for MASKED regions with reconstruct_from_masked (mask_loader.py:712-763) inside: walks the
 //                        source rows with the combined mask byte beside them, writes every merged row at its source
 //                        position (signal and noise regions each their own rows of the full tensor).
@@ -42,6 +45,22 @@ typedef const __attribute__((address_space(1))) f32x4 mg_gf32x4;
 // exactly as the reference does on the host (merge.py:123-124); < 0 = the task is not in the set.
 // order   [P or 1][N]: task indices in the order the reference adds them (sorted task names, merge.py:89); NULL = 0..N-1.
 // cbar    [P][n_sets][N] out: columns 0..k-1 the averaged c_high, k..r-1 the averaged dequantized c_low, 0 beyond.
+// coefficient i (< r) of task t of parameter p as the reference holds it in fp32: column i < k the fp16 c_high, else the
+// dequantized c_low
+__device__ __forceinline__ float task_coeff(int p, int t, int i, int n, int k, int stages,
+                                            const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
+                                            const float *__restrict__ scale, const float *__restrict__ zp) {
+    if (i < k) return __half2float(__ushort_as_half(chigh[((size_t)p * n + t) * n + i]));
+    // zeros + sum over stages of (q - zero_point) / scale (rtvq.py:29-36, :85-103)
+    float c = 0.f;
+    const size_t sb = ((size_t)p * n + t) * stages;
+    for (int st = 0; st < stages; ++st) {
+        const float q = (float)codes[(sb + st) * n + (i - k)];
+        c = __fadd_rn(c, __fdiv_rn(__fsub_rn(q, zp[sb + st]), scale[sb + st]));
+    }
+    return c;
+}
+
 __global__ __launch_bounds__(64) void k_merge_coeff(int NT, int stages, int n_sets, int per_param,
                                                     const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
                                                     const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
@@ -60,22 +79,31 @@ __global__ __launch_bounds__(64) void k_merge_coeff(int NT, int stages, int n_se
                 const int t = ord ? ord[tt] : tt;
                 const float wt = w[s * n + t];
                 if (wt < 0.f) continue;
-                float c;
-                if (i < k) {
-                    c = __half2float(__ushort_as_half(chigh[((size_t)p * n + t) * n + i]));
-                } else {
-                    // zeros + sum over stages of (q - zero_point) / scale (rtvq.py:29-36, :85-103)
-                    c = 0.f;
-                    const size_t sb = ((size_t)p * n + t) * stages;
-                    for (int st = 0; st < stages; ++st) {
-                        const float q = (float)codes[(sb + st) * n + (i - k)];
-                        c = __fadd_rn(c, __fdiv_rn(__fsub_rn(q, zp[sb + st]), scale[sb + st]));
-                    }
-                }
+                const float c = task_coeff(p, t, i, n, k, stages, chigh, codes, scale, zp);
                 acc = __fadd_rn(acc, __fmul_rn(c, wt));      // (stack * w).sum(0), task by task
             }
         }
         cbar[((size_t)p * n_sets + s) * n + i] = acc;
+    }
+}
+
+// The same for single tasks picked by index: cbar [P][n_out][N] = the coefficients of task[s] -- what k_merge_coeff
+// gives for the one-hot set {task[s]: 1.0} (0 + c * 1, rounded as there), without a weight table.  An index outside
+// [0, N) gives zeros (the streaming launch skips that output).
+__global__ __launch_bounds__(64) void k_task_coeff(int NT, int stages, int n_out, const int32_t *__restrict__ task,
+                                                   const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
+                                                   const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
+                                                   const float *__restrict__ scale, const float *__restrict__ zp,
+                                                   float *__restrict__ cbar) {
+    const int p = blockIdx.x, i = threadIdx.x, n = NT;
+    const int k = k_in[p], r = r_in[p];
+    if (i >= n) return;
+    for (int s = 0; s < n_out; ++s) {
+        const int t = task[s];
+        float acc = 0.f;
+        if (i < r && (unsigned)t < (unsigned)n)
+            acc = __fadd_rn(acc, __fmul_rn(task_coeff(p, t, i, n, k, stages, chigh, codes, scale, zp), 1.f));
+        cbar[((size_t)p * n_out + s) * n + i] = acc;
     }
 }
 
@@ -256,6 +284,161 @@ __global__ __launch_bounds__(64) void k_merge_reconstruct(const SvdqParam *__res
             }
             if (gbase) res = __fadd_rn(bv[m], res);      // base + delta (merge.py:429-552)
             if (64 * m + lane < rows_blk) gout[rb + 64 * m + lane] = res;
+        }
+        lds_fence();      // the basis rows are rewritten next
+    }
+}
+
+// ------------------------------------------------------------------------------------ every task's own rows
+// reconstruct_from_coefficients (merge.py:144-194) for n_out tasks of the plan in ONE pass over the basis: the block's
+// basis rows are staged once (k_merge_reconstruct's staging, LDS image and one-block pipeline) and read from LDS once per
+// group of TG tasks; every task of a group has its own pair of fma chains per row and its own store stream (lane l
+// owns rows l, 64 + l, ...: 256 contiguous bytes per task and store instruction).  Nothing is combined across tasks,
+// so out[p][j] is what k_merge_reconstruct writes for a single set that holds task j alone.
+//   cbar  [P][n_out][N]: the tasks' coefficients (k_task_coeff)
+//   task  [n_out] plan task indices; an index outside [0, N) is skipped like a NULL output
+//   out   [P][n_out] fp32 outputs; NULL = this (parameter, task) is not formed
+// TG x RPL accumulator pairs per lane: 8 x 4 as k_merge_reconstruct<., 8, 4>; more tasks = more groups, not registers.
+template <bool U16, int TG, int RPL>
+__global__ __launch_bounds__(64) void k_task_reconstruct(const SvdqParam *__restrict__ params,
+                                                         const SvdqUnit *__restrict__ units,
+                                                         const int64_t *__restrict__ rows_dev, int NT, int n_out,
+                                                         const int32_t *__restrict__ task,
+                                                         const int32_t *__restrict__ k_in,
+                                                         const int32_t *__restrict__ r_in,
+                                                         const uint8_t *__restrict__ basis,
+                                                         const float *__restrict__ meanbuf,
+                                                         const float *__restrict__ cbar,
+                                                         const float *__restrict__ scale_tab,
+                                                         const float *const *__restrict__ base_ptrs,
+                                                         float *const *__restrict__ out_ptrs) {
+    using T = typename UElem<U16>::type;
+    constexpr int ES = U16 ? 2 : 4;
+    constexpr int RB = 64 * RPL;
+    constexpr int NMAX = RPL == 4 ? 16 : 32;
+    constexpr int SV = (RB * NMAX * ES / 16 + 2 + 63) / 64;
+    // dynamic LDS: the staged basis rows (both parts + alignment slack), then the coefficients [column][nop]
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const int lane = threadIdx.x, n = NT;
+    const int nop = (n_out + TG - 1) / TG * TG;      // tasks padded to whole groups
+    const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
+    float *C = reinterpret_cast<float *>(lds_raw + ubytes);
+    const SvdqUnit ud = units[blockIdx.x];
+    const int p = ud.param;
+    const int64_t D = rows_dev ? rows_dev[p] : params[p].rows;
+    const int64_t r_begin = ud.row0;
+    int64_t r_end = r_begin + ud.nrows;
+    if (r_end > D) r_end = D;
+    if (r_begin >= r_end) return;
+    float *const *outp = out_ptrs + (size_t)p * n_out;
+    // bit j: task j of the call is formed for this parameter (wave-uniform)
+    const unsigned live = (unsigned)__ballot(lane < n_out && outp[lane < n_out ? lane : 0] != nullptr &&
+                                             (unsigned)task[lane < n_out ? lane : 0] < (unsigned)n);
+    if (!live) return;
+    const int k = k_in[p], r = r_in[p], nl = r - k;
+    for (int e = lane; e < nop * n; e += 64) {      // transposed: the tasks' coefficients of a column side by side
+        const int i = e / nop, s = e % nop;
+        C[e] = s < n_out ? cbar[((size_t)p * n_out + s) * n + i] : 0.f;
+    }
+    const float scale = scale_tab ? scale_tab[p] : 1.f;
+    const uint8_t *slab = basis + params[p].slab_off;
+    const uint8_t *gUh = slab;
+    const uint8_t *gUl = slab + svdq_align_up(D * (int64_t)k * ES, 256);
+    mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + params[p].mean_off) : nullptr;
+    mg_gfloat *gbase = base_ptrs ? (mg_gfloat *)base_ptrs[p] : nullptr;
+
+    // ---- the loads of one block into registers
+    f32x4 ureg[SV];
+    float mpf[RPL] = {}, bpf[RPL] = {};
+    auto prefetch = [&](int64_t rb) {
+        const int nr = (int)((r_end - rb < RB) ? (r_end - rb) : RB);
+        const UStage us = ustage_plan<ES>(rb, nr, k, nl);
+#pragma unroll
+        for (int s = 0; s < SV; ++s) {
+            const int v = lane + 64 * s;
+            if (v < us.nv) {
+                const uint8_t *gp = (v < us.nvh) ? gUh + us.a0h + 16ll * v : gUl + us.a0l + 16ll * (v - us.nvh);
+                ureg[s] = *(mg_gf32x4 *)gp;
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) {      // rows past the block's end are clamped into it (their results are not stored)
+            const int q = 64 * m + lane;
+            const int64_t row = rb + (q < nr ? q : nr - 1);
+            if (gmean) mpf[m] = gmean[row];
+            if (gbase) bpf[m] = gbase[row];
+        }
+    };
+    prefetch(r_begin);
+    for (int64_t rb = r_begin; rb < r_end; rb += RB) {
+        const int rows_blk = (int)((r_end - rb < RB) ? (r_end - rb) : RB);
+        // ---- registers -> LDS
+        const UStage cur = ustage_plan<ES>(rb, rows_blk, k, nl);
+#pragma unroll
+        for (int s = 0; s < SV; ++s) {
+            const int v = lane + 64 * s;
+            if (v < cur.nv) reinterpret_cast<f32x4 *>(lds_raw)[v] = ureg[s];
+        }
+        float mv[RPL], bv[RPL];
+        int rl[RPL];      // the lane's rows, clamped into the block
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) {
+            const int q = 64 * m + lane;
+            rl[m] = q < rows_blk ? q : rows_blk - 1;
+            mv[m] = mpf[m];
+            bv[m] = bpf[m];
+        }
+        lds_fence();
+        // ---- the next block's loads
+        if (rb + RB < r_end) prefetch(rb + RB);
+        // ---- compute: one pass over the LDS image per group of TG tasks
+        const T *Uh = reinterpret_cast<const T *>(lds_raw) + cur.offh;
+        const T *Ul = reinterpret_cast<const T *>(lds_raw + 16 * cur.nvh) + cur.offl;
+        for (int g0 = 0; g0 < n_out; g0 += TG) {
+            const unsigned gm = (live >> g0) & ((1u << TG) - 1u);
+            if (!gm) continue;
+            mg_gfloat_w *o[TG];
+#pragma unroll
+            for (int s = 0; s < TG; ++s) o[s] = (mg_gfloat_w *)outp[g0 + s < n_out ? g0 + s : g0];
+            float hi[RPL][TG], lo[RPL][TG];
+#pragma unroll
+            for (int m = 0; m < RPL; ++m)
+#pragma unroll
+                for (int s = 0; s < TG; ++s) hi[m][s] = lo[m][s] = 0.f;
+            for (int i = 0; i < k; ++i) {
+                float c[TG];
+#pragma unroll
+                for (int s = 0; s < TG; ++s) c[s] = C[i * nop + g0 + s];
+#pragma unroll
+                for (int m = 0; m < RPL; ++m) {
+                    const float u = u_val(Uh, rl[m] * k + i);
+#pragma unroll
+                    for (int s = 0; s < TG; ++s) hi[m][s] = fmaf(u, c[s], hi[m][s]);
+                }
+            }
+            for (int j = 0; j < nl; ++j) {
+                float c[TG];
+#pragma unroll
+                for (int s = 0; s < TG; ++s) c[s] = C[(k + j) * nop + g0 + s];
+#pragma unroll
+                for (int m = 0; m < RPL; ++m) {
+                    const float u = u_val(Ul, rl[m] * nl + j);
+#pragma unroll
+                    for (int s = 0; s < TG; ++s) lo[m][s] = fmaf(u, c[s], lo[m][s]);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < TG; ++s) {
+                if (!((gm >> s) & 1u)) continue;      // wave-uniform
+#pragma unroll
+                for (int m = 0; m < RPL; ++m) {
+                    float v = __fadd_rn(hi[m][s], lo[m][s]);
+                    if (gmean) v = __fadd_rn(v, mv[m]);
+                    v = __fmul_rn(v, scale);
+                    if (gbase) v = __fadd_rn(bv[m], v);      // base + delta (merge.py:429-552)
+                    if (64 * m + lane < rows_blk) o[s][rb + 64 * m + lane] = v;
+                }
+            }
         }
         lds_fence();      // the basis rows are rewritten next
     }
@@ -1065,6 +1248,61 @@ extern "C" int svdq_merge(const svdq_plan *pl, const int64_t *rows_dev, const vo
     if (int rc = svdq_merge_coeffs(pl, small, weights, order, n_sets, per_param, cbar, stream)) return rc;
     return svdq_merge_reconstruct(pl, rows_dev, small, basis, mean, cbar, n_sets, per_param, set_share, scale, base_ptrs,
                                   out_ptrs, stream);
+}
+
+// ---- every selected task's own reconstruction: the tasks' coefficients (k_task_coeff) + one streaming launch
+extern "C" int64_t svdq_task_reconstruct_work_bytes(const svdq_plan *pl, int32_t n_out) {
+    if (!pl || n_out < 1 || n_out > SVDQ_MAX_TASKS) return 0;
+    return svdq_align_up((int64_t)pl->n_params * n_out * pl->n_tasks * 4, 256);      // the tasks' coefficients
+}
+
+extern "C" int svdq_task_reconstruct(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
+                                     const float *mean, const int32_t *task, int32_t n_out, const float *scale,
+                                     const void *base_ptrs, const void *out_ptrs, void *work, void *stream) {
+    const char *who = "svdq_task_reconstruct";
+    if (!pl || !small || !basis || !task || !out_ptrs || !work) {
+        svdq_set_error("%s: plan, small, basis, task, out_ptrs and work are required", who);
+        return SVDQ_EINVAL;
+    }
+    if (n_out < 1 || n_out > SVDQ_MAX_TASKS) {
+        svdq_set_error("%s: n_out must be in [1, %d], got %d", who, SVDQ_MAX_TASKS, n_out);
+        return SVDQ_EINVAL;
+    }
+    if (pl->cfg.center && !mean) {
+        svdq_set_error("%s: mean is required on a centred plan", who);
+        return SVDQ_EINVAL;
+    }
+    const int n = pl->n_tasks;
+    hipStream_t st = (hipStream_t)stream;
+    float *cbar = reinterpret_cast<float *>(work);
+    const svdq_small_layout &L = pl->small;
+    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
+    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    hipLaunchKernelGGL(k_task_coeff, dim3(pl->n_params), dim3(64), 0, st, n, pl->cfg.rtvq_stages, (int)n_out, task, kk, rr,
+                       reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
+                       reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off),
+                       cbar);
+    auto bp = reinterpret_cast<const float *const *>(base_ptrs);
+    auto op = reinterpret_cast<float *const *>(out_ptrs);
+    const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
+    const float *mn = pl->cfg.center ? mean : nullptr;
+    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
+    const int rpl = n <= 16 ? 4 : 2;                           // rows per lane and block, as launch_reconstruct
+    const int nop = (n_out + tg - 1) / tg * tg;
+    const size_t lds = (size_t)svdq_align_up((int64_t)64 * rpl * n * (pl->cfg.fp16 ? 2 : 4) + 48, 16) + (size_t)nop * n * 4;
+    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
+        constexpr bool F16 = f16_c;
+        return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
+            constexpr int TG = tg_c;
+            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
+                constexpr int RPL = rpl_c;
+                hipLaunchKernelGGL((k_task_reconstruct<F16, TG, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
+                                   pl->d_units, rows_dev, n, (int)n_out, task, kk, rr, bs, mn, cbar, scale, bp, op);
+                return true;
+            });
+        });
+    });
+    return svdq_launch_status(ok, who);
 }
 
 extern "C" int64_t svdq_diagnostics_work_bytes(const svdq_plan *pl) {

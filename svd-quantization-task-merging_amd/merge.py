@@ -324,6 +324,137 @@ def merge_all_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict
     return merged
 
 
+def _reconstruct_tasks_batched(names, wanted, compressed_all, bases, masks, original_shapes, config, base_state_dict, dev):
+    """reconstruct_task_vectors for the parameters whose artifacts live in plans (a fused run's, or adopted ones): per
+    plan ONE svdq_task_reconstruct -- the selected tasks' coefficients + one pass over the basis that writes every
+    (parameter, task) output -- into a buffer of this call's own.  Unmasked parameters get ``base +`` inside the launch;
+    masked ones are formed in compacted rows (the noise plan with scale = svd_noise_shrink) and scattered per task
+    afterwards.  Returns {name: {task: tensor}} for the names it could take."""
+    import numpy as np
+    from .mask_loader import reconstruct_from_masked
+    jobs, metas = {}, {}      # id(plan) -> (plan batch, {entry index: (name, region)})
+    for name in names:
+        got = _batched_entry(name, compressed_all, bases)
+        if got is None:
+            continue
+        batch, i, meta = got
+        metas[name] = meta
+        jobs.setdefault(id(batch.plan), (batch, {}))[1][i] = (name, "masked")
+        if config.svd_include_noise and meta["noise"] is not None:
+            nb, j = meta["noise"]
+            jobs.setdefault(id(nb.plan), (nb, {}))[1][j] = (name, "noise")
+    want = set(wanted)
+    pieces = {}      # name -> task -> {"masked": rows, "noise": rows} (compacted rows where the parameter is masked)
+    with torch.cuda.device(dev):
+        for batch, entries in jobs.values():
+            plan, small = batch.plan, batch.small
+            P = plan.P
+            # the plan's task positions some entry wants; an entry whose task at a position is not wanted (plans group by
+            # task COUNT: two entries may name their tasks differently) leaves that output out
+            slots = sorted({q for i, (name, _) in entries.items() for q, t in enumerate(batch.task_names[i])
+                            if t in want and t in metas[name]["have"]})
+            if not slots:
+                continue
+            n_out = len(slots)
+            out_tab = np.zeros((P, n_out), dtype=np.int64)
+            base_tab = np.zeros(P, dtype=np.int64)
+            scale = np.ones(P, dtype=np.float32)
+            cuts, tot, keep = [], 0, []
+            for i, (name, region) in entries.items():
+                rows = int(small.rows[i])
+                if rows <= 0:
+                    continue
+                if region == "noise":
+                    scale[i] = np.float32(config.svd_noise_shrink)
+                b = base_state_dict.get(name) if base_state_dict is not None else None
+                if b is not None and masks.get(name) is None and b.dtype is torch.float32 and b.numel() == rows:
+                    keep.append(prepare_vector(b, plan.device))
+                    base_tab[i] = keep[-1].data_ptr()
+                for j, q in enumerate(slots):
+                    t = batch.task_names[i][q]
+                    if t in want and t in metas[name]["have"]:
+                        cuts.append((i, j, name, region, t, tot, rows, bool(base_tab[i])))
+                        tot += (rows + 63) // 64 * 64
+            # a buffer of this call's own: a later call must not overwrite what this one hands out
+            buf = torch.empty(tot, dtype=torch.float32, device=plan.device)
+            for i, j, _, _, _, off, _, _ in cuts:
+                out_tab[i, j] = buf.data_ptr() + 4 * off
+            rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+            plan.reconstruct_tasks(slots, torch.from_numpy(out_tab).to(plan.device),
+                                   scale=torch.from_numpy(scale).to(plan.device),
+                                   base_table=torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None,
+                                   rows_dev=rows_dev)
+            for _, _, name, region, t, off, rows, based in cuts:
+                pieces.setdefault(name, {}).setdefault(t, {})[region] = (buf[off:off + rows], based)
+        out = {}
+        for name, meta in metas.items():
+            shape, mask = original_shapes[name], masks.get(name)
+            b = base_state_dict.get(name) if base_state_dict is not None else None
+            res = {}
+            for t in meta["have"]:
+                if t not in want:
+                    continue
+                pc = pieces.get(name, {}).get(t, {})
+                based = False
+                if "masked" not in pc:
+                    delta = torch.zeros(shape, device=dev)      # merge_parameter's zeros (merge.py:297-299)
+                elif mask is not None:
+                    delta = reconstruct_from_masked(pc["masked"][0], pc["noise"][0] if "noise" in pc else None, mask, shape)
+                else:
+                    delta, based = pc["masked"][0].view(shape), pc["masked"][1]
+                res[t] = delta if (b is None or based) else b.to(delta.device) + delta
+            out[name] = res
+    return out
+
+
+def reconstruct_task_vectors(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                             masks: Optional[Dict[str, torch.Tensor]], original_shapes: Dict[str, torch.Size], config,
+                             tasks=None, device: str = "cpu", base_state_dict: Optional[Dict[str, torch.Tensor]] = None
+                             ) -> Dict[str, Dict[str, torch.Tensor]]:
+    """Every task's own task vector back out of the artifacts: {task: {param: U c_task + mean}}, what the reference
+    computes per (parameter, task) with RTVQQuantizer.dequantize (rtvq.py:85-103) + reconstruct_from_coefficients
+    (merge.py:144-194) -- here ``merge_parameter`` on that task alone with weight 1.0, bit for bit.  ``tasks``: the task
+    names wanted (None = every task of ``compressed_all``).  ``base_state_dict``: the values are ``base + delta`` for the
+    parameters it holds (apply_merged_deltas, merge.py:429-552).  A task that lacks a parameter has no such key.
+
+    Parameters whose dictionaries still are what a fused run or ``adopt_artifacts`` handed out take two launches per
+    plan for ALL selected tasks (svdq_task_reconstruct: one pass over the basis, n outputs); the rest goes per
+    (parameter, task) through ``merge_parameter``."""
+    known = []
+    for per_task in compressed_all.values():
+        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
+                  if t not in known]
+    wanted = list(known) if tasks is None else list(tasks)
+    for t in wanted:
+        if t not in known:
+            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    dev = resolve_device(device)
+    masks = masks or {}
+    quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
+    names = sorted(compressed_all.keys())
+    fast = _reconstruct_tasks_batched(names, wanted, compressed_all, bases, masks, original_shapes, config,
+                                      base_state_dict, dev)
+    out = {t: {} for t in wanted}
+    for name in names:
+        if name in fast:
+            per = fast[name]
+        else:
+            per = {}
+            b = base_state_dict.get(name) if base_state_dict is not None else None
+            for t in wanted:
+                if t not in compressed_all[name]:
+                    continue
+                delta = merge_parameter(name, {t: compressed_all[name][t]}, bases[name], {t: 1.0}, quantizer,
+                                        original_shapes[name], mask=masks.get(name),
+                                        include_noise=config.svd_include_noise, noise_shrink=config.svd_noise_shrink,
+                                        device=dev)
+                per[t] = delta if b is None else b.to(delta.device) + delta
+        for t in wanted:
+            if t in per:
+                out[t][name] = per[t].cpu() if wants_cpu(device) else per[t]
+    return out
+
+
 def apply_merged_deltas(base_state_dict: Dict[str, torch.Tensor], merged_deltas: Dict[str, torch.Tensor],
                         device: str = "cpu", verbose: bool = True) -> Dict[str, torch.Tensor]:
     """Reference merge.py:429-552: merged[param] = base[param] + delta[param]; others are cloned."""

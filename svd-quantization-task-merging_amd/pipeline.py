@@ -506,6 +506,40 @@ class CompressPlan:
                                       _ptr(base_table), _ptr(out_table), _ptr(work), _stream_ptr()), "svdq_merge")
         return (buf, offs) if own else None
 
+    def reconstruct_tasks(self, task_idx, out_table: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                          base_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None) -> None:
+        """Every selected task's own reconstruction of every parameter of the plan in two launches
+        (svdq_task_reconstruct): one pass over the basis writes n_out outputs per parameter, each the bits of ``merge``
+        with that task as a one-hot set.  ``task_idx``: plan task indices -- a sequence of ints (checked here against
+        [0, N), duplicates allowed) or an int32 device tensor (the caller's to have checked: the device skips an index
+        outside the range).  ``out_table``: int64 device tensor [P, n_out] of fp32 outputs of rows[p] elements, 0 = that
+        (parameter, task) is not formed.  ``scale`` / ``base_table`` / ``rows_dev``: as for ``merge``."""
+        if isinstance(task_idx, torch.Tensor) and task_idx.is_cuda:
+            if task_idx.dtype is not torch.int32 or not task_idx.is_contiguous() or task_idx.dim() != 1:
+                raise ValueError("svdq_task_reconstruct: a device task table must be a contiguous int32 vector")
+            tasks_d = task_idx
+        else:
+            idx = [int(t) for t in (task_idx.tolist() if isinstance(task_idx, torch.Tensor) else task_idx)]
+            if not 1 <= len(idx) <= nat.MAX_TASKS:
+                raise ValueError(f"svdq_task_reconstruct: n_out must be in [1, {nat.MAX_TASKS}], got {len(idx)}")
+            bad = [t for t in idx if not 0 <= t < self.N]
+            if bad:
+                raise ValueError(f"svdq_task_reconstruct: task index {bad[0]} is outside [0, {self.N})")
+            cache = self.__dict__.setdefault("_task_tables", {})
+            tasks_d = cache.get(tuple(idx))
+            if tasks_d is None:
+                tasks_d = cache[tuple(idx)] = torch.tensor(idx, dtype=torch.int32).to(self.device)
+        n_out = int(tasks_d.numel())
+        if out_table.numel() != self.P * n_out:
+            raise ValueError(f"svdq_task_reconstruct: out_table needs {self.P} x {n_out} entries, got {out_table.numel()}")
+        work = getattr(self, "_task_work", None)
+        need = int(self.lib.svdq_task_reconstruct_work_bytes(self._h, n_out))
+        if work is None or work.numel() < need:
+            work = self._task_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        nat.check(self.lib.svdq_task_reconstruct(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                 _ptr(self.mean), _ptr(tasks_d), n_out, _ptr(scale), _ptr(base_table),
+                                                 _ptr(out_table), _ptr(work), _stream_ptr()), "svdq_task_reconstruct")
+
     def merge_masked(self, weights: torch.Tensor, mask_table: torch.Tensor, unit_start: torch.Tensor,
                      rows_dev: torch.Tensor, out_table: torch.Tensor, order: Optional[torch.Tensor] = None,
                      set_share: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,

@@ -197,18 +197,54 @@ def reconstruct_from_artifacts(artifact_dir: str, base_model_path, output_path: 
     shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
               if d.get("original_shape") is not None}
     merged = merge_all_parameters(compressed, bases, {}, weights, shapes, config, device=device, verbose=False)
-    if isinstance(base_model_path, dict):
-        base = base_model_path
-    else:
-        base = torch.load(base_model_path, map_location=device, weights_only=True)
-        for key in ("state_dict", "model", "model_state_dict"):   # task_vector_loader.py unwraps these
-            if isinstance(base, dict) and key in base and isinstance(base[key], dict):
-                base = base[key]
-                break
+    base = _load_base(base_model_path, device)
     out = apply_merged_deltas(base, merged, device=device, verbose=False)
     if output_path:
         torch.save(out, output_path)
     return {"merged_state_dict": out, "diagnostics": diagnostics, "config": config}
+
+
+def _load_base(base_model_path, device):
+    """A base state dict from a path (wrappers unwrapped as task_vector_loader.py does) or as given."""
+    if isinstance(base_model_path, dict):
+        return base_model_path
+    base = torch.load(base_model_path, map_location=device, weights_only=True)
+    for key in ("state_dict", "model", "model_state_dict"):
+        if isinstance(base, dict) and key in base and isinstance(base[key], dict):
+            return base[key]
+    return base
+
+
+def reconstruct_tasks_from_artifacts(artifact_dir: str, base_state_dict, tasks=None, output_dir: str = None,
+                                     device: str = "cuda") -> Dict[str, Dict[str, torch.Tensor]]:
+    """Every task's own model back out of stored artifacts: {task: state dict} with ``base + delta_task`` for the
+    parameters the artifacts cover and a clone of the base tensor for the others (as apply_merged_deltas does).
+    load_all_artifacts -> adopt_artifacts -> merge.reconstruct_task_vectors: two launches per plan for all tasks.  Masks
+    are not stored (reload.py:204-205), so this is exact for unmasked runs only, like ``reconstruct_from_artifacts``.
+    ``base_state_dict``: a state dict or the path of one; ``tasks``: names (None = all); with ``output_dir`` each
+    task's state dict is written to ``<output_dir>/<task>.pt``."""
+    from .merge import reconstruct_task_vectors
+    from .driver import adopt_artifacts
+    art = load_all_artifacts(artifact_dir, device=device)
+    config, diagnostics = art["config"], art["diagnostics"]
+    if tasks is not None:      # before any device work
+        known = {t for per_task in art["compressed"].values() for t in per_task}
+        for t in tasks:
+            if t not in known:
+                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
+    base = _load_base(base_state_dict, device)
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
+              if d.get("original_shape") is not None}
+    covered = {n: b for n, b in base.items() if n in compressed}
+    models = reconstruct_task_vectors(compressed, bases, {}, shapes, config, tasks=tasks, device=device,
+                                      base_state_dict=covered)
+    out = {}
+    for t, params in models.items():
+        out[t] = {n: (params[n] if n in params else b.clone()) for n, b in base.items()}
+        if output_dir:
+            save_merged_model({n: v.cpu() for n, v in out[t].items()}, output_dir, filename=f"{_safe(t)}.pt")
+    return out
 
 
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
