@@ -556,6 +556,34 @@ int svdq_merge_masked(const svdq_plan *plan, const int64_t *rows_dev, const void
                       int32_t per_param, const float *set_share_dev, const float *scale_dev, const void *mask_ptrs_dev,
                       const int64_t *unit_start_dev, const int32_t *fill_dev, const void *base_ptrs_dev,
                       const void *out_ptrs_dev, void *work_dev, void *stream);
+
+/* ---- every task's OWN reconstruction of MASKED regions, inside the source walk (the one statement of the contract; the
+ *      sources point here): what the reference does per (parameter, task) with RTVQQuantizer.dequantize (rtvq.py:85-103)
+ *      + reconstruct_from_coefficients (merge.py:144-194) on the signal and the noise region, reconstruct_from_masked
+ *      (mask_loader.py:712-763) to put both back at their source rows, and apply_merged_deltas (merge.py:429-552) when a
+ *      base is given.  Two launches per plan: svdq_task_reconstruct's coefficient launch, unchanged, then ONE streaming
+ *      launch that walks the SOURCE rows as svdq_merge_masked does (same mask_ptrs_dev, unit_start_dev, fill_dev, ranks
+ *      by wave ballots clamped to the unit's compacted rows) and, from one staged run of U_high / U_low / mean rows,
+ *      writes every selected task's value at the source row:
+ *        out[p][j][s] = base[p][s] + ((U_high c_j,high + U_low c_j,low)[rank(s)] + mean[rank(s)]) * scale[p]
+ *      for a selected source row s; base[p][s] + 0 for an unselected row when fill[p] is set; an unselected row is
+ *      otherwise left untouched (the noise entry of the same parameter writes it).  Without base the value alone.
+ *   The contract on bits: out[p][j] is bit for bit svdq_merge_masked with the one-hot set {task_dev[j]: 1.0} and the same
+ *     scale, fill, base, masks and unit starts; and bit for bit svdq_task_reconstruct into compacted rows followed by
+ *     svdq_mask_expand, plus base.
+ *   task_dev, n_out, scale_dev, work_dev (svdq_task_reconstruct_work_bytes): as for svdq_task_reconstruct -- NULL
+ *     task_dev, an n_out outside [1, SVDQ_MAX_TASKS] or a missing mean on a centred plan is SVDQ_EINVAL before anything
+ *     is launched; a device index outside [0, N) is skipped like a NULL output.
+ *   mask_ptrs_dev, unit_start_dev, rows_dev, fill_dev, base_ptrs_dev: as for svdq_merge_masked (the first three required:
+ *     NULL is SVDQ_EINVAL).
+ *   out_ptrs_dev  [P][n_out] FULL fp32 tensors (params[p].rows elements); a NULL entry = that (parameter, task) is neither
+ *                 formed nor written; a parameter whose outputs are all skipped is not read at all.
+ *   Allocates nothing, copies nothing to the host, synchronises nothing: capturable like every other entry point. */
+int svdq_task_reconstruct_masked(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev,
+                                 const void *basis_dev, const float *mean_dev, const int32_t *task_dev, int32_t n_out,
+                                 const float *scale_dev, const void *mask_ptrs_dev, const int64_t *unit_start_dev,
+                                 const int32_t *fill_dev, const void *base_ptrs_dev,
+                                 const void *out_ptrs_dev /* [P][n_out] FULL tensors */, void *work_dev, void *stream);
 int svdq_diagnostics_masked(const svdq_plan *plan, const void *delta_ptrs_dev, const void *mask_ptrs_dev,
                             const int64_t *unit_start_dev, const int64_t *rows_dev, const void *small_dev,
                             const void *basis_dev, const float *mean_dev, int32_t add_mean, double *out_dev,
@@ -566,8 +594,10 @@ int svdq_diagnostics_masked(const svdq_plan *plan, const void *delta_ptrs_dev, c
  *      them again later, with other weights or another base model (load_all_artifacts storage.py:341-389 ->
  *      reconstruct_from_artifacts reload.py:142-238 -> merge_all_parameters merge.py:304-426).  svdq_plan_import puts such
  *      artifacts -- wherever they came from -- into the packed buffers of a plan, after which every plan-level consumer that
- *      needs only the artifacts works on them: svdq_merge, svdq_merge_coeffs, svdq_merge_reconstruct (and, given masks and
- *      unit starts of the caller's, svdq_merge_masked).
+ *      needs only the artifacts works on them: svdq_merge, svdq_merge_coeffs, svdq_merge_reconstruct, svdq_task_reconstruct
+ *      (and, given masks and unit starts of the caller's, the source walks svdq_merge_masked and
+ *      svdq_task_reconstruct_masked -- on a plan created with rows[p] = the element count of the mask: a walk ends where
+ *      the plan's rows end, so a plan created with rows[p] = D would stop at source row D; rows_dev carries D).
  *   the plan         svdq_plan_create with rows[p] = D of the stored basis, n_tasks = the tasks that hold the parameters,
  *                    cfg.fp16 = the stored basis is fp16 (else fp32), cfg.center = means are stored, cfg.rtvq_stages as
  *                    stored.  It needs no compress workspace.

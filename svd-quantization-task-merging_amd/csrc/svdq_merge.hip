@@ -18,6 +18,8 @@
 //   k_merge_expand       the same for MASKED regions with reconstruct_from_masked (mask_loader.py:712-763) inside: walks the
 //                        source rows with the combined mask byte beside them, writes every merged row at its source
 //                        position (signal and noise regions each their own rows of the full tensor).
+//   k_task_expand        k_task_reconstruct's task groups on k_merge_expand's source walk: every selected task's own rows of
+//                        the MASKED regions, written at their source positions (+ base) in the same pass.
 //   k_diag / k_diag_finish  compute_parameter_diagnostics' inner loop (diagnostics.py:186-215) for all N tasks of a
 //                        parameter in one pass over U and the N deltas: N error tuples per parameter; walk mode =
 //                        masked regions, apply_mask_to_tensor (mask_loader.py:651-679) inside the pass.
@@ -670,6 +672,209 @@ __global__ __launch_bounds__(64) void k_merge_expand(const SvdqParam *__restrict
     }
 }
 
+// ------------------------------------------------------------------------------------ masked parameters: every task's own rows
+// k_task_reconstruct's task groups on k_merge_expand's source walk: reconstruct_from_masked (mask_loader.py:712-763)
+// inside the one pass over the basis that forms every selected task's own rows.  The walk, the selection (ballot ranks
+// clamped to the unit's compacted rows), the staging and the one-chunk pipeline are k_merge_expand's; the chunk's LDS
+// image is read once per group of TG tasks, every task of a group has its own pair of fma chains per row (indexed by the
+// row's rank) and its own store stream at the SOURCE row (256 contiguous bytes per task and store instruction).  Nothing
+// is combined across tasks, so out[p][j] is what k_merge_expand<., 1, .> writes for the one-hot set {task[j]: 1.0}.
+//   cbar  [P][n_out][N]: the tasks' coefficients (k_task_coeff)
+//   task  [n_out] plan task indices; an index outside [0, N) is skipped like a NULL output
+//   out   [P][n_out] FULL fp32 tensors; NULL = this (parameter, task) is not formed.  All NULL = the unit reads nothing.
+template <bool U16, int TG, int RPL>
+__global__ __launch_bounds__(64) void k_task_expand(const SvdqParam *__restrict__ params,
+                                                    const SvdqUnit *__restrict__ units,
+                                                    const int64_t *__restrict__ rows_dev, int NT, int n_out,
+                                                    const int32_t *__restrict__ task, const int32_t *__restrict__ k_in,
+                                                    const int32_t *__restrict__ r_in,
+                                                    const uint8_t *__restrict__ basis,
+                                                    const float *__restrict__ meanbuf, const float *__restrict__ cbar,
+                                                    const float *__restrict__ scale_tab,
+                                                    const uint8_t *const *__restrict__ mask_ptrs,
+                                                    const int64_t *__restrict__ ustart,
+                                                    const int32_t *__restrict__ fill_tab,
+                                                    const float *const *__restrict__ base_ptrs,
+                                                    float *const *__restrict__ out_ptrs) {
+    using T = typename UElem<U16>::type;
+    constexpr int ES = U16 ? 2 : 4;
+    constexpr int RB = 64 * RPL;
+    constexpr int NMAX = RPL == 4 ? 16 : 32;
+    constexpr int SV = (RB * NMAX * ES / 16 + 2 + 63) / 64;
+    // dynamic LDS: the staged basis rows, the staged mean values, the coefficients [column][nop]
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const int lane = threadIdx.x, u = blockIdx.x, n = NT;
+    const int nop = (n_out + TG - 1) / TG * TG;      // tasks padded to whole groups
+    const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
+    float *M = reinterpret_cast<float *>(lds_raw + ubytes);      // [RB]
+    float *C = M + RB;                                           // [column][nop]
+    const SvdqUnit ud = units[u];
+    const int p = ud.param;
+    float *const *outp = out_ptrs + (size_t)p * n_out;
+    // bit j: task j of the call is formed for this parameter (wave-uniform)
+    const unsigned live = (unsigned)__ballot(lane < n_out && outp[lane < n_out ? lane : 0] != nullptr &&
+                                             (unsigned)task[lane < n_out ? lane : 0] < (unsigned)n);
+    if (!live) return;      // an entry the caller does not reconstruct
+    const SvdqParam pd = params[p];
+    const SrcRange sr = unit_source_range(pd, u, ustart);
+    if (sr.lo >= sr.hi) return;
+    const int64_t D = rows_dev ? rows_dev[p] : pd.rows;      // compacted rows of the region
+    int64_t cpos = ud.row0;
+    int64_t cend = ud.row0 + ud.nrows;
+    if (cend > D) cend = D;
+    if (cpos > cend) cpos = cend;
+    const int k = k_in[p], r = r_in[p], nl = r - k;
+    for (int e = lane; e < nop * n; e += 64) {      // transposed: the tasks' coefficients of a column side by side
+        const int i = e / nop, s = e % nop;
+        C[e] = s < n_out ? cbar[((size_t)p * n_out + s) * n + i] : 0.f;
+    }
+    const float scale = scale_tab ? scale_tab[p] : 1.f;
+    const bool fill = fill_tab ? fill_tab[p] != 0 : false;
+    const uint8_t *slab = basis + pd.slab_off;
+    const uint8_t *gUh = slab;
+    const uint8_t *gUl = slab + svdq_align_up(D * (int64_t)k * ES, 256);
+    mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
+    mg_gfloat *gbase = base_ptrs ? (mg_gfloat *)base_ptrs[p] : nullptr;
+    mg_gbyte *gmask = (mg_gbyte *)mask_ptrs[p];
+
+    // ---- the loads of one chunk into registers
+    unsigned mk[RPL];      // mask bytes; 0x100 = past the end of the range: selected by neither polarity
+    float bpf[RPL] = {}, mpf[RPL] = {};
+    f32x4 ureg[SV];
+    auto prefetch = [&](int64_t s0, int64_t c0) {
+        const int64_t r0 = s0 + lane;
+        if (s0 + RB <= sr.hi) {
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) {
+                mk[e] = (unsigned)gmask[r0 + 64 * e];
+                if (gbase) bpf[e] = gbase[r0 + 64 * e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) {
+                const bool in = r0 + 64 * e < sr.hi;
+                mk[e] = in ? (unsigned)gmask[r0 + 64 * e] : 0x100u;
+                if (gbase) bpf[e] = in ? gbase[r0 + 64 * e] : 0.f;
+            }
+        }
+        const int nr = (int)((cend - c0 < RB) ? (cend - c0) : RB);
+        if (gmean) {
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) mpf[e] = (64 * e + lane < nr) ? gmean[c0 + 64 * e + lane] : 0.f;
+        }
+        const UStage us = ustage_plan<ES>(c0, nr, k, nl);
+#pragma unroll
+        for (int s = 0; s < SV; ++s) {
+            const int v = lane + 64 * s;
+            if (v < us.nv) {
+                const uint8_t *gp = (v < us.nvh) ? gUh + us.a0h + 16ll * v : gUl + us.a0l + 16ll * (v - us.nvh);
+                ureg[s] = *(mg_gf32x4 *)gp;
+            }
+        }
+    };
+    prefetch(sr.lo, cpos);
+    for (int64_t src = sr.lo; src < sr.hi; src += RB) {
+        // ---- the chunk's selection: rank of each of the lane's rows among the chunk's selected rows, and their number
+        // (the lane's own flags in one vector register: bit m = row m is selected, bit 4 + m = it is inside the range --
+        // as lane masks they would hold sixteen scalar registers across the task groups)
+        unsigned flags = 0;
+        int rank[RPL], count;
+        {
+            int base = 0;
+            const int64_t room = cend - cpos;
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) {
+                if (mk[e] != 0x100u) flags |= 16u << e;
+                const bool sb = sr.inv ? (mk[e] == 0u) : (mk[e] != 0u && mk[e] != 0x100u);
+                const unsigned long long bal = __ballot(sb);
+                rank[e] = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+                if (sb && rank[e] < room) flags |= 1u << e;      // never past the unit's compacted rows, whatever the mask says
+                base += (int)__popcll(bal);
+            }
+            count = base < room ? base : (int)room;
+        }
+        // ---- registers -> LDS
+        const UStage cur = ustage_plan<ES>(cpos, (int)((cend - cpos < RB) ? (cend - cpos) : RB), k, nl);
+#pragma unroll
+        for (int s = 0; s < SV; ++s) {
+            const int v = lane + 64 * s;
+            if (v < cur.nv) reinterpret_cast<f32x4 *>(lds_raw)[v] = ureg[s];
+        }
+        if (gmean) {
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) M[64 * e + lane] = mpf[e];
+        }
+        float bv[RPL];
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) bv[m] = bpf[m];
+        lds_fence();
+        // ---- the next chunk's loads
+        if (src + RB < sr.hi) prefetch(src + RB, cpos + count);
+        // ---- compute: one pass over the LDS image per group of TG tasks
+        const T *Uh = reinterpret_cast<const T *>(lds_raw) + cur.offh;
+        const T *Ul = reinterpret_cast<const T *>(lds_raw + 16 * cur.nvh) + cur.offl;
+        int rl[RPL];
+        float mv[RPL];
+#pragma unroll
+        for (int m = 0; m < RPL; ++m) {
+            rl[m] = ((flags >> m) & 1u) ? rank[m] : 0;
+            mv[m] = (gmean && count > 0) ? M[rl[m]] : 0.f;
+        }
+        for (int g0 = 0; g0 < n_out; g0 += TG) {
+            const unsigned gm = (live >> g0) & ((1u << TG) - 1u);
+            if (!gm) continue;
+            float hi[RPL][TG], lo[RPL][TG];
+#pragma unroll
+            for (int m = 0; m < RPL; ++m)
+#pragma unroll
+                for (int s = 0; s < TG; ++s) hi[m][s] = lo[m][s] = 0.f;
+            if (count > 0) {      // wave-uniform; a chunk that selects nothing only fills
+                for (int i = 0; i < k; ++i) {
+                    float c[TG];
+#pragma unroll
+                    for (int s = 0; s < TG; ++s) c[s] = C[i * nop + g0 + s];
+#pragma unroll
+                    for (int m = 0; m < RPL; ++m) {
+                        const float uv = u_val(Uh, rl[m] * k + i);
+#pragma unroll
+                        for (int s = 0; s < TG; ++s) hi[m][s] = fmaf(uv, c[s], hi[m][s]);
+                    }
+                }
+                for (int j = 0; j < nl; ++j) {
+                    float c[TG];
+#pragma unroll
+                    for (int s = 0; s < TG; ++s) c[s] = C[(k + j) * nop + g0 + s];
+#pragma unroll
+                    for (int m = 0; m < RPL; ++m) {
+                        const float uv = u_val(Ul, rl[m] * nl + j);
+#pragma unroll
+                        for (int s = 0; s < TG; ++s) lo[m][s] = fmaf(uv, c[s], lo[m][s]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < TG; ++s) {
+                if (!((gm >> s) & 1u)) continue;      // wave-uniform
+                // the task's pointer is fetched here, one at a time: eight of them held across the fma loops cost
+                // sixteen scalar registers the walk has no room for (the stores of the task before are still draining)
+                mg_gfloat_w *o = (mg_gfloat_w *)outp[g0 + s];
+#pragma unroll
+                for (int m = 0; m < RPL; ++m) {
+                    float v = __fadd_rn(hi[m][s], lo[m][s]);
+                    if (gmean) v = __fadd_rn(v, mv[m]);
+                    v = __fmul_rn(v, scale);
+                    const bool sel = (flags >> m) & 1u, in = (flags >> (4 + m)) & 1u;
+                    v = sel ? v : 0.f;
+                    if (gbase) v = __fadd_rn(bv[m], v);      // base + delta (merge.py:429-552)
+                    if (in && (sel || fill)) o[src + 64 * m + lane] = v;
+                }
+            }
+        }
+        lds_fence();
+        cpos += count;
+    }
+}
+
 // ------------------------------------------------------------------------------------ diagnostics
 // One pass over U and the N task deltas of a parameter: per task t the reconstruction U_high c_high[t] + U_low c_low[t]
 // (+ mean when add_mean: the reference's diagnostics do NOT add it back) is formed per row and compared with
@@ -1298,6 +1503,65 @@ extern "C" int svdq_task_reconstruct(const svdq_plan *pl, const int64_t *rows_de
                 constexpr int RPL = rpl_c;
                 hipLaunchKernelGGL((k_task_reconstruct<F16, TG, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
                                    pl->d_units, rows_dev, n, (int)n_out, task, kk, rr, bs, mn, cbar, scale, bp, op);
+                return true;
+            });
+        });
+    });
+    return svdq_launch_status(ok, who);
+}
+
+// ---- the same for masked regions: the tasks' coefficients (k_task_coeff) + one source-walk launch
+extern "C" int svdq_task_reconstruct_masked(const svdq_plan *pl, const int64_t *rows_dev, const void *small,
+                                            const void *basis, const float *mean, const int32_t *task, int32_t n_out,
+                                            const float *scale, const void *mask_ptrs, const int64_t *unit_start,
+                                            const int32_t *fill, const void *base_ptrs, const void *out_ptrs, void *work,
+                                            void *stream) {
+    const char *who = "svdq_task_reconstruct_masked";
+    if (!pl || !small || !basis || !task || !out_ptrs || !work) {
+        svdq_set_error("%s: plan, small, basis, task, out_ptrs and work are required", who);
+        return SVDQ_EINVAL;
+    }
+    if (!mask_ptrs || !unit_start || !rows_dev) {
+        svdq_set_error("%s: mask_ptrs, unit_start and rows_dev are required", who);
+        return SVDQ_EINVAL;
+    }
+    if (n_out < 1 || n_out > SVDQ_MAX_TASKS) {
+        svdq_set_error("%s: n_out must be in [1, %d], got %d", who, SVDQ_MAX_TASKS, n_out);
+        return SVDQ_EINVAL;
+    }
+    if (pl->cfg.center && !mean) {
+        svdq_set_error("%s: mean is required on a centred plan", who);
+        return SVDQ_EINVAL;
+    }
+    const int n = pl->n_tasks;
+    hipStream_t st = (hipStream_t)stream;
+    float *cbar = reinterpret_cast<float *>(work);
+    const svdq_small_layout &L = pl->small;
+    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
+    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    hipLaunchKernelGGL(k_task_coeff, dim3(pl->n_params), dim3(64), 0, st, n, pl->cfg.rtvq_stages, (int)n_out, task, kk, rr,
+                       reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
+                       reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off),
+                       cbar);
+    auto bp = reinterpret_cast<const float *const *>(base_ptrs);
+    auto op = reinterpret_cast<float *const *>(out_ptrs);
+    auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
+    const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
+    const float *mn = pl->cfg.center ? mean : nullptr;
+    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a chunk's LDS image
+    const int rpl = n <= 16 ? 4 : 2;                           // source rows per lane and chunk, as launch_reconstruct
+    const int nop = (n_out + tg - 1) / tg * tg;
+    const size_t lds = (size_t)svdq_align_up((int64_t)64 * rpl * n * (pl->cfg.fp16 ? 2 : 4) + 48, 16) +
+                       (size_t)64 * rpl * 4 + (size_t)nop * n * 4;
+    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
+        constexpr bool F16 = f16_c;
+        return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
+            constexpr int TG = tg_c;
+            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
+                constexpr int RPL = rpl_c;
+                hipLaunchKernelGGL((k_task_expand<F16, TG, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
+                                   pl->d_units, rows_dev, n, (int)n_out, task, kk, rr, bs, mn, cbar, scale, mp, unit_start,
+                                   fill, bp, op);
                 return true;
             });
         });

@@ -184,7 +184,10 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                 # (svdq_merge_masked / svdq_diagnostics_masked) put the merged rows back with, whichever mode compressed
                 ms = entries[0]["ms"]
                 mtab = torch.tensor([ms._s["mb"][e["q"]].data_ptr() for e in entries], dtype=torch.int64).to(dev)
-                us = ms.unit_starts(plan, rows_dev, entry_map=[(e["q"], e["inv"]) for e in entries], mask_table=mtab)
+                # the unit starts look a mask up by its index q in the mask set, the streaming kernels by plan entry:
+                # two tables (they differ as soon as a plan holds both regions of a parameter)
+                qtab = torch.tensor([b.data_ptr() for b in ms._s["mb"]], dtype=torch.int64).to(dev)
+                us = ms.unit_starts(plan, rows_dev, entry_map=[(e["q"], e["inv"]) for e in entries], mask_table=qtab)
                 keep.append((mtab, us))
             if mode == "walk":
                 if btab is not None:
@@ -593,8 +596,75 @@ def _device_source(t: Optional[torch.Tensor], dev, dtype) -> Optional[torch.Tens
     return v.clone() if v.data_ptr() & 15 else v
 
 
-def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], config, device="cuda"
-                    ) -> Tuple[Dict[str, Dict], Dict[str, Dict]]:
+def _planned_rows(entry, masks) -> int:
+    """Rows an adopted entry is planned with: the stored D, or the element count of the caller's mask for it."""
+    D = int(entry["basis"]["U_high"].shape[0])
+    m = masks.get(entry["name"]) if masks else None
+    return int(m.numel()) if isinstance(m, torch.Tensor) and m.numel() >= D else D
+
+
+def _walk_usable(entries, q_of, plan_rows, stored_rows, numels, count_true, count_false) -> List[int]:
+    """The mask-count check of ``adopted_mask_walk``, on host numbers: entry i = (name, region) can be walked with mask
+    q_of[name] when the plan holds that mask's element count as its source rows and the mask selects -- set elements
+    for "masked", cleared ones for "noise" -- exactly the stored rows."""
+    ok = []
+    for i, (name, region) in enumerate(entries):
+        q = q_of.get(name)
+        if q is None or int(stored_rows[i]) <= 0 or int(plan_rows[i]) != int(numels[q]):
+            continue
+        if int(count_false[q] if region == "noise" else count_true[q]) == int(stored_rows[i]):
+            ok.append(i)
+    return ok
+
+
+def adopted_mask_walk(batch, masks):
+    """For an ADOPTED batch and the caller's ``masks``: what the source-walk consumer (svdq_task_reconstruct_masked)
+    puts compacted rows back with.  Masks are not stored (reference reload.py:204-205), so the tables a fused run
+    keeps are built here: one MaskSet over the batch's masked parameters, one count + scan, ONE small device-to-host
+    copy of the counts.  An entry is usable only if its counts equal the stored ``rows`` (``_walk_usable``); one whose
+    mask does not fit keeps the compacted route, and so raises what it raises today.  Returns ``(mask_table [P],
+    unit_start [plan units], usable entry indices)`` or None when nothing fits; cached on the batch by mask identity."""
+    import numpy as np
+    from . import mask_loader as ml
+    plan, small = batch.plan, batch.small
+    names = []
+    for name, _ in batch.entries:
+        m = masks.get(name) if masks else None
+        if isinstance(m, torch.Tensor) and m.numel() > 0 and name not in names:
+            names.append(name)
+    if not names:
+        return None
+    ident = tuple((n, masks[n].data_ptr(), masks[n].numel(), str(masks[n].device), masks[n].dtype) for n in names)
+    cached = getattr(batch, "_mask_walk", None)
+    if cached is not None and cached[0] == ident:
+        return cached[1]
+    dev = plan.device
+    result = None
+    with torch.cuda.device(dev):
+        numels = [int(masks[n].numel()) for n in names]
+        ms = ml.MaskSet(numels, dev)
+        ct, cf = ms.count_scan([masks[n] for n in names])
+        counts = torch.stack([ct, cf]).cpu()
+        q_of = {n: q for q, n in enumerate(names)}
+        usable = _walk_usable(batch.entries, q_of, plan.rows, small.rows, numels, counts[0].tolist(), counts[1].tolist())
+        if usable:
+            rows = np.zeros(plan.P, dtype=np.int64)      # entries that do not fit: no unit of theirs is walked
+            mtab = np.zeros(plan.P, dtype=np.int64)
+            emap = [(0, False)] * plan.P
+            for i in usable:
+                name, region = batch.entries[i]
+                rows[i] = int(small.rows[i])
+                mtab[i] = ms._s["mb"][q_of[name]].data_ptr()
+                emap[i] = (q_of[name], region == "noise")
+            us = ms.unit_starts(plan, torch.from_numpy(rows).to(dev), entry_map=emap)
+            result = (torch.from_numpy(mtab).to(dev), us, frozenset(usable))
+    # the mask set owns the mask bytes the table points at; the caller's tensors are held so that their identity stays theirs
+    batch._mask_walk = (ident, result, ms, [masks[n] for n in names])
+    return result
+
+
+def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], config, device="cuda",
+                    masks: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[Dict[str, Dict], Dict[str, Dict]]:
     """Put artifacts that did NOT come out of a fused run in this process -- the reference-layout dictionaries
     ``load_all_artifacts`` returns, tensors on the CPU or the GPU -- into plans, so that ``merge_all_parameters``,
     ``merge_with_clustering`` and ``reconstruct_from_artifacts`` serve them in two launches per plan (svdq_merge)
@@ -615,6 +685,11 @@ def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], con
     more than 32 tasks, shapes that disagree with k / n_low, other dtypes, ...), so the per-parameter route serves it
     as before.  Adoption never raises on data.
 
+    ``masks``: the masks the caller will reconstruct with.  A masked parameter's entries are then planned with as many
+    rows as its mask has elements (the stored D rows are what is filled and read), which is what the source walk of
+    ``reconstruct_task_vectors_masked`` needs to put the rows back inside the launch
+    (``adopted_mask_walk``); every other consumer reads the stored row counts and works as before.
+
     Memory: while a plan is being filled its sources and its packed copy coexist (4.9 GB twice at ViT-L-14 x 8).
     Plans are filled one after the other, and the device copies made of CPU tensors are dropped before the next plan;
     sources that already live on the device are read where they are and stay the caller's to release (drop the
@@ -627,7 +702,7 @@ def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], con
     for (n_tasks, stages, udt, no_mean), entries in groups.items():
         P, N, S = len(entries), n_tasks, stages
         try:
-            plan = CompressPlan([int(e["basis"]["U_high"].shape[0]) for e in entries], N,
+            plan = CompressPlan([_planned_rows(e, masks) for e in entries], N,
                                 energy_threshold=config.svd_energy_threshold, max_rank=config.svd_max_rank,
                                 center=not no_mean, fp16=udt is torch.float16, low_bits=[e["bits"] for e in entries],
                                 rtvq_stages=S, device=dev, workspace=False)

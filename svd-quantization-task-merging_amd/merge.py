@@ -185,6 +185,28 @@ def _mask_identity(mask) -> Optional[tuple]:
     return None if mask is None else (mask.data_ptr(), mask.numel(), str(mask.device), mask.dtype)
 
 
+def _source_walk_decline(batch, noise_batch, name, mask) -> Optional[str]:
+    """Why a masked parameter of a fused run cannot take the source-walk consumers (svdq_merge_masked,
+    svdq_task_reconstruct_masked), or None when it can: they put the rows back with the mask table and unit starts the
+    run compressed with, so the caller's ``mask`` must be that very tensor -- for the signal batch and, when the
+    parameter has a noise entry to merge, for its ``noise_batch`` too."""
+    if getattr(batch, "mode", "plain") == "plain":
+        return "the batch was not compressed through masks"
+    ident = getattr(batch, "mask_ident", {}).get(name)
+    if ident is None:
+        return "the run recorded no mask for the parameter"
+    if ident != _mask_identity(mask):
+        return "the caller's mask is not the tensor the run compressed with"
+    if batch.unit_start is None:
+        return "the batch has no unit starts"
+    if noise_batch is not None:
+        if noise_batch.unit_start is None:
+            return "the noise batch has no unit starts"
+        if getattr(noise_batch, "mask_ident", {}).get(name) != ident:
+            return "the noise batch was compressed with another mask"
+    return None
+
+
 def _merge_batched(names, compressed_all, bases, masks, sets, original_shapes, config, device):
     """merge_all_parameters / merge_with_clustering for the parameters whose artifacts still live in the buffers of a
     fused run: per plan ONE coefficient kernel + ONE streaming reconstruction (svdq_merge) instead of, per parameter
@@ -234,14 +256,9 @@ def _merge_batched(names, compressed_all, bases, masks, sets, original_shapes, c
         if "masked" not in regs:
             continue
         batch = jobs[regs["masked"][0]][0]
-        if getattr(batch, "mode", "plain") == "plain":
-            continue
-        ident = getattr(batch, "mask_ident", {}).get(name)
         nb = jobs[regs["noise"][0]][0] if "noise" in regs else None
-        if (ident is None or ident != _mask_identity(masks.get(name)) or batch.unit_start is None
-                or (nb is not None and (nb.unit_start is None or getattr(nb, "mask_ident", {}).get(name) != ident))):
-            continue
-        fused.add(name)
+        if _source_walk_decline(batch, nb, name, masks.get(name)) is None:
+            fused.add(name)
     pieces = {}    # name -> {"masked": tensor, "noise": tensor} (compacted rows; the unfused way)
     with torch.cuda.device(dev):
         for key, (batch, entries) in jobs.items():
@@ -324,68 +341,150 @@ def merge_all_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict
     return merged
 
 
-def _reconstruct_tasks_batched(names, wanted, compressed_all, bases, masks, original_shapes, config, base_state_dict, dev):
+def _task_walk_plans(where, masks, original_shapes, config):
+    """``fused_masks``: the masked parameters whose rows go back at their source positions inside the launch
+    (svdq_task_reconstruct_masked), and per plan the tables it walks with.  A parameter of a fused run qualifies exactly
+    when ``_merge_batched`` sends it through svdq_merge_masked (``_source_walk_decline``); one of adopted plans when the
+    caller's mask fits the stored row counts (``driver.adopted_mask_walk``).  Returns ({id(plan): (mask_table,
+    unit_start)}, names, names with a live noise entry)."""
+    import math
+    from .driver import adopted_mask_walk
+    walk = {}
+
+    def tables(batch):
+        key = id(batch.plan)
+        if key not in walk:
+            walk[key] = (adopted_mask_walk(batch, masks) if getattr(batch, "adopted", False)
+                         else (batch.mask_table, batch.unit_start, None))
+        return walk[key]
+
+    def fits(batch, i):      # an adopted entry: the caller's mask selects exactly its stored rows
+        t = tables(batch)
+        return t is not None and i in t[2]
+
+    fused, noisy = set(), set()
+    for name, (batch, i, meta) in where.items():
+        mask = masks.get(name)
+        if mask is None or int(batch.small.rows[i]) <= 0:
+            continue
+        if batch.plan.rows[i] != mask.numel() or math.prod(original_shapes[name]) != mask.numel():
+            continue
+        nb = j = None
+        if config.svd_include_noise and meta["noise"] is not None and int(meta["noise"][0].small.rows[meta["noise"][1]]) > 0:
+            nb, j = meta["noise"]
+            # fill is per parameter: the noise entry must cover every task the signal entry has
+            if nb.task_names[j] != batch.task_names[i] or nb.plan.rows[j] != mask.numel():
+                continue
+        adopted = getattr(batch, "adopted", False)
+        if nb is not None and getattr(nb, "adopted", False) != adopted:
+            continue
+        if adopted:
+            ok = fits(batch, i) and (nb is None or fits(nb, j))
+        else:
+            ok = _source_walk_decline(batch, nb, name, mask) is None
+            if ok:
+                tables(batch)
+                if nb is not None:
+                    tables(nb)
+        if ok:
+            fused.add(name)
+            if nb is not None:
+                noisy.add(name)
+    return {key: t[:2] for key, t in walk.items() if t is not None}, fused, noisy
+
+
+def _reconstruct_tasks_batched(names, wanted, compressed_all, bases, masks, original_shapes, config, base_state_dict, dev,
+                               fused_masks=False):
     """reconstruct_task_vectors for the parameters whose artifacts live in plans (a fused run's, or adopted ones): per
     plan ONE svdq_task_reconstruct -- the selected tasks' coefficients + one pass over the basis that writes every
     (parameter, task) output -- into a buffer of this call's own.  Unmasked parameters get ``base +`` inside the launch;
     masked ones are formed in compacted rows (the noise plan with scale = svd_noise_shrink) and scattered per task
-    afterwards.  Returns {name: {task: tensor}} for the names it could take."""
+    afterwards -- or, with ``fused_masks``, written at their source rows by ONE svdq_task_reconstruct_masked per plan
+    (full tensors of this call's own; fill = 1 on a signal entry without a live noise entry; a fp32 base of the right
+    size inside the launch).  Returns {name: {task: tensor}} for the names it could take."""
     import numpy as np
     from .mask_loader import reconstruct_from_masked
-    jobs, metas = {}, {}      # id(plan) -> (plan batch, {entry index: (name, region)})
+    jobs, metas, where = {}, {}, {}      # id(plan) -> (plan batch, {entry index: (name, region)})
     for name in names:
         got = _batched_entry(name, compressed_all, bases)
         if got is None:
             continue
         batch, i, meta = got
-        metas[name] = meta
+        metas[name], where[name] = meta, got
         jobs.setdefault(id(batch.plan), (batch, {}))[1][i] = (name, "masked")
         if config.svd_include_noise and meta["noise"] is not None:
             nb, j = meta["noise"]
             jobs.setdefault(id(nb.plan), (nb, {}))[1][j] = (name, "noise")
     want = set(wanted)
+    walk, fused, noisy = _task_walk_plans(where, masks, original_shapes, config) if fused_masks else ({}, set(), set())
     pieces = {}      # name -> task -> {"masked": rows, "noise": rows} (compacted rows where the parameter is masked)
+    full, based_in = {}, set()      # name -> task -> full tensor (fused masks); names whose base went inside the launch
     with torch.cuda.device(dev):
-        for batch, entries in jobs.values():
+        for key, (batch, all_entries) in jobs.items():
             plan, small = batch.plan, batch.small
             P = plan.P
-            # the plan's task positions some entry wants; an entry whose task at a position is not wanted (plans group by
-            # task COUNT: two entries may name their tasks differently) leaves that output out
-            slots = sorted({q for i, (name, _) in entries.items() for q, t in enumerate(batch.task_names[i])
-                            if t in want and t in metas[name]["have"]})
-            if not slots:
-                continue
-            n_out = len(slots)
-            out_tab = np.zeros((P, n_out), dtype=np.int64)
-            base_tab = np.zeros(P, dtype=np.int64)
-            scale = np.ones(P, dtype=np.float32)
-            cuts, tot, keep = [], 0, []
-            for i, (name, region) in entries.items():
-                rows = int(small.rows[i])
-                if rows <= 0:
-                    continue
-                if region == "noise":
-                    scale[i] = np.float32(config.svd_noise_shrink)
-                b = base_state_dict.get(name) if base_state_dict is not None else None
-                if b is not None and masks.get(name) is None and b.dtype is torch.float32 and b.numel() == rows:
-                    keep.append(prepare_vector(b, plan.device))
-                    base_tab[i] = keep[-1].data_ptr()
-                for j, q in enumerate(slots):
-                    t = batch.task_names[i][q]
-                    if t in want and t in metas[name]["have"]:
-                        cuts.append((i, j, name, region, t, tot, rows, bool(base_tab[i])))
-                        tot += (rows + 63) // 64 * 64
-            # a buffer of this call's own: a later call must not overwrite what this one hands out
-            buf = torch.empty(tot, dtype=torch.float32, device=plan.device)
-            for i, j, _, _, _, off, _, _ in cuts:
-                out_tab[i, j] = buf.data_ptr() + 4 * off
             rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
-            plan.reconstruct_tasks(slots, torch.from_numpy(out_tab).to(plan.device),
-                                   scale=torch.from_numpy(scale).to(plan.device),
-                                   base_table=torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None,
-                                   rows_dev=rows_dev)
-            for _, _, name, region, t, off, rows, based in cuts:
-                pieces.setdefault(name, {}).setdefault(t, {})[region] = (buf[off:off + rows], based)
+            for walked in (True, False):
+                entries = {i: e for i, e in all_entries.items() if (e[0] in fused) == walked}
+                # the plan's task positions some entry wants; an entry whose task at a position is not wanted (plans group
+                # by task COUNT: two entries may name their tasks differently) leaves that output out
+                slots = sorted({q for i, (name, _) in entries.items() for q, t in enumerate(batch.task_names[i])
+                                if t in want and t in metas[name]["have"]})
+                if not slots:
+                    continue
+                n_out = len(slots)
+                out_tab = np.zeros((P, n_out), dtype=np.int64)
+                base_tab = np.zeros(P, dtype=np.int64)
+                scale = np.ones(P, dtype=np.float32)
+                fill = np.zeros(P, dtype=np.int32)
+                cuts, tot, keep = [], 0, []
+                for i, (name, region) in entries.items():
+                    rows = int(small.rows[i])
+                    if rows <= 0:
+                        continue
+                    if region == "noise":
+                        scale[i] = np.float32(config.svd_noise_shrink)
+                    b = base_state_dict.get(name) if base_state_dict is not None else None
+                    if walked:
+                        fill[i] = int(region == "masked" and name not in noisy)
+                        if b is not None and b.dtype is torch.float32 and b.numel() == plan.rows[i]:
+                            keep.append(prepare_vector(b, plan.device))
+                            base_tab[i] = keep[-1].data_ptr()
+                            based_in.add(name)
+                    elif b is not None and masks.get(name) is None and b.dtype is torch.float32 and b.numel() == rows:
+                        keep.append(prepare_vector(b, plan.device))
+                        base_tab[i] = keep[-1].data_ptr()
+                    for j, q in enumerate(slots):
+                        t = batch.task_names[i][q]
+                        if not (t in want and t in metas[name]["have"]):
+                            continue
+                        if walked:
+                            # full tensors of this call's own; the signal and the noise entry write their own rows of it
+                            ft = full.setdefault(name, {}).get(t)
+                            if ft is None:
+                                ft = full[name][t] = torch.empty(plan.rows[i], dtype=torch.float32, device=plan.device)
+                            out_tab[i, j] = ft.data_ptr()
+                        else:
+                            cuts.append((i, j, name, region, t, tot, rows, bool(base_tab[i])))
+                            tot += (rows + 63) // 64 * 64
+                sc_d = torch.from_numpy(scale).to(plan.device)
+                bt_d = torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None
+                if walked:
+                    if not out_tab.any():      # only entries without rows (a noise region that was not built)
+                        continue
+                    mask_table, unit_start = walk[key]
+                    plan.reconstruct_tasks_masked(slots, mask_table, unit_start, rows_dev,
+                                                  torch.from_numpy(out_tab).to(plan.device), scale=sc_d,
+                                                  fill=torch.from_numpy(fill).to(plan.device), base_table=bt_d)
+                    continue
+                # a buffer of this call's own: a later call must not overwrite what this one hands out
+                buf = torch.empty(tot, dtype=torch.float32, device=plan.device)
+                for i, j, _, _, _, off, _, _ in cuts:
+                    out_tab[i, j] = buf.data_ptr() + 4 * off
+                plan.reconstruct_tasks(slots, torch.from_numpy(out_tab).to(plan.device), scale=sc_d, base_table=bt_d,
+                                       rows_dev=rows_dev)
+                for _, _, name, region, t, off, rows, based in cuts:
+                    pieces.setdefault(name, {}).setdefault(t, {})[region] = (buf[off:off + rows], based)
         out = {}
         for name, meta in metas.items():
             shape, mask = original_shapes[name], masks.get(name)
@@ -396,7 +495,9 @@ def _reconstruct_tasks_batched(names, wanted, compressed_all, bases, masks, orig
                     continue
                 pc = pieces.get(name, {}).get(t, {})
                 based = False
-                if "masked" not in pc:
+                if name in fused and t in full.get(name, {}):
+                    delta, based = full[name][t].view(shape), name in based_in
+                elif "masked" not in pc:
                     delta = torch.zeros(shape, device=dev)      # merge_parameter's zeros (merge.py:297-299)
                 elif mask is not None:
                     delta = reconstruct_from_masked(pc["masked"][0], pc["noise"][0] if "noise" in pc else None, mask, shape)
@@ -419,7 +520,26 @@ def reconstruct_task_vectors(compressed_all: Dict[str, Dict[str, Dict]], bases: 
 
     Parameters whose dictionaries still are what a fused run or ``adopt_artifacts`` handed out take two launches per
     plan for ALL selected tasks (svdq_task_reconstruct: one pass over the basis, n outputs); the rest goes per
-    (parameter, task) through ``merge_parameter``."""
+    (parameter, task) through ``merge_parameter``.  Masked parameters of such plans are formed in compacted rows and put
+    back per (parameter, task); ``reconstruct_task_vectors_masked`` does that inside the streaming launch."""
+    return reconstruct_task_vectors_masked(compressed_all, bases, masks, original_shapes, config, tasks=tasks,
+                                           device=device, base_state_dict=base_state_dict, fused_masks=False)
+
+
+def reconstruct_task_vectors_masked(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                                    masks: Optional[Dict[str, torch.Tensor]], original_shapes: Dict[str, torch.Size],
+                                    config, tasks=None, device: str = "cpu",
+                                    base_state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                                    fused_masks: bool = True) -> Dict[str, Dict[str, torch.Tensor]]:
+    """``reconstruct_task_vectors`` for masked runs: the same arguments, the same result bit for bit, and one keyword.
+    (A function of its own because the signature of ``reconstruct_task_vectors`` is part of the surface this package
+    holds fixed; that function is this one with ``fused_masks=False``.)
+
+    ``fused_masks``: masked parameters of such plans get reconstruct_from_masked (mask_loader.py:712-763) and ``base +``
+    INSIDE the streaming launch (svdq_task_reconstruct_masked) instead of compacted rows scattered per (parameter,
+    task) afterwards -- when ``masks[name]`` is the tensor the run compressed with, or, for adopted plans
+    (``adopt_artifacts(..., masks=masks)``), a mask that selects exactly the stored rows; any other masked parameter
+    keeps the compacted route.  Same bits either way."""
     known = []
     for per_task in compressed_all.values():
         known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
@@ -433,7 +553,7 @@ def reconstruct_task_vectors(compressed_all: Dict[str, Dict[str, Dict]], bases: 
     quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
     names = sorted(compressed_all.keys())
     fast = _reconstruct_tasks_batched(names, wanted, compressed_all, bases, masks, original_shapes, config,
-                                      base_state_dict, dev)
+                                      base_state_dict, dev, fused_masks=fused_masks)
     out = {t: {} for t in wanted}
     for name in names:
         if name in fast:

@@ -506,6 +506,26 @@ class CompressPlan:
                                       _ptr(base_table), _ptr(out_table), _ptr(work), _stream_ptr()), "svdq_merge")
         return (buf, offs) if own else None
 
+    def _task_table(self, task_idx, who: str) -> torch.Tensor:
+        """The int32 device table of plan task indices a task-reconstruction call takes: a device tensor as it is, host
+        indices checked against [0, N) and cached per index tuple."""
+        if isinstance(task_idx, torch.Tensor) and task_idx.is_cuda:
+            if task_idx.dtype is not torch.int32 or not task_idx.is_contiguous() or task_idx.dim() != 1:
+                raise ValueError(f"{who}: a device task table must be a contiguous int32 vector")
+            tasks_d = task_idx
+        else:
+            idx = [int(t) for t in (task_idx.tolist() if isinstance(task_idx, torch.Tensor) else task_idx)]
+            if not 1 <= len(idx) <= nat.MAX_TASKS:
+                raise ValueError(f"{who}: n_out must be in [1, {nat.MAX_TASKS}], got {len(idx)}")
+            bad = [t for t in idx if not 0 <= t < self.N]
+            if bad:
+                raise ValueError(f"{who}: task index {bad[0]} is outside [0, {self.N})")
+            cache = self.__dict__.setdefault("_task_tables", {})
+            tasks_d = cache.get(tuple(idx))
+            if tasks_d is None:
+                tasks_d = cache[tuple(idx)] = torch.tensor(idx, dtype=torch.int32).to(self.device)
+        return tasks_d
+
     def reconstruct_tasks(self, task_idx, out_table: torch.Tensor, scale: Optional[torch.Tensor] = None,
                           base_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None) -> None:
         """Every selected task's own reconstruction of every parameter of the plan in two launches
@@ -514,21 +534,7 @@ class CompressPlan:
         [0, N), duplicates allowed) or an int32 device tensor (the caller's to have checked: the device skips an index
         outside the range).  ``out_table``: int64 device tensor [P, n_out] of fp32 outputs of rows[p] elements, 0 = that
         (parameter, task) is not formed.  ``scale`` / ``base_table`` / ``rows_dev``: as for ``merge``."""
-        if isinstance(task_idx, torch.Tensor) and task_idx.is_cuda:
-            if task_idx.dtype is not torch.int32 or not task_idx.is_contiguous() or task_idx.dim() != 1:
-                raise ValueError("svdq_task_reconstruct: a device task table must be a contiguous int32 vector")
-            tasks_d = task_idx
-        else:
-            idx = [int(t) for t in (task_idx.tolist() if isinstance(task_idx, torch.Tensor) else task_idx)]
-            if not 1 <= len(idx) <= nat.MAX_TASKS:
-                raise ValueError(f"svdq_task_reconstruct: n_out must be in [1, {nat.MAX_TASKS}], got {len(idx)}")
-            bad = [t for t in idx if not 0 <= t < self.N]
-            if bad:
-                raise ValueError(f"svdq_task_reconstruct: task index {bad[0]} is outside [0, {self.N})")
-            cache = self.__dict__.setdefault("_task_tables", {})
-            tasks_d = cache.get(tuple(idx))
-            if tasks_d is None:
-                tasks_d = cache[tuple(idx)] = torch.tensor(idx, dtype=torch.int32).to(self.device)
+        tasks_d = self._task_table(task_idx, "svdq_task_reconstruct")
         n_out = int(tasks_d.numel())
         if out_table.numel() != self.P * n_out:
             raise ValueError(f"svdq_task_reconstruct: out_table needs {self.P} x {n_out} entries, got {out_table.numel()}")
@@ -539,6 +545,27 @@ class CompressPlan:
         nat.check(self.lib.svdq_task_reconstruct(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
                                                  _ptr(self.mean), _ptr(tasks_d), n_out, _ptr(scale), _ptr(base_table),
                                                  _ptr(out_table), _ptr(work), _stream_ptr()), "svdq_task_reconstruct")
+
+    def reconstruct_tasks_masked(self, task_idx, mask_table: torch.Tensor, unit_start: torch.Tensor,
+                                 rows_dev: torch.Tensor, out_table: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                                 fill: Optional[torch.Tensor] = None, base_table: Optional[torch.Tensor] = None) -> None:
+        """``reconstruct_tasks`` for a plan of masked regions, with reconstruct_from_masked inside the streaming launch
+        (svdq_task_reconstruct_masked): ``out_table`` int64 [P, n_out] names FULL tensors (0 = that (parameter, task) is
+        not formed), ``mask_table`` / ``unit_start`` / ``fill`` are ``merge_masked``'s.  Every output is the bits of
+        ``merge_masked`` with that task as a one-hot set.  ``task_idx`` as for ``reconstruct_tasks``."""
+        who = "svdq_task_reconstruct_masked"
+        tasks_d = self._task_table(task_idx, who)
+        n_out = int(tasks_d.numel())
+        if out_table.numel() != self.P * n_out:
+            raise ValueError(f"{who}: out_table needs {self.P} x {n_out} entries, got {out_table.numel()}")
+        work = getattr(self, "_task_work", None)
+        need = int(self.lib.svdq_task_reconstruct_work_bytes(self._h, n_out))
+        if work is None or work.numel() < need:
+            work = self._task_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        nat.check(self.lib.svdq_task_reconstruct_masked(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                        _ptr(self.mean), _ptr(tasks_d), n_out, _ptr(scale),
+                                                        _ptr(mask_table), _ptr(unit_start), _ptr(fill), _ptr(base_table),
+                                                        _ptr(out_table), _ptr(work), _stream_ptr()), who)
 
     def merge_masked(self, weights: torch.Tensor, mask_table: torch.Tensor, unit_start: torch.Tensor,
                      rows_dev: torch.Tensor, out_table: torch.Tensor, order: Optional[torch.Tensor] = None,

@@ -17,7 +17,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import asdict
-from typing import Any, Dict
+from typing import Any, Dict, Optional
 
 import torch
 
@@ -217,13 +217,25 @@ def _load_base(base_model_path, device):
 
 def reconstruct_tasks_from_artifacts(artifact_dir: str, base_state_dict, tasks=None, output_dir: str = None,
                                      device: str = "cuda") -> Dict[str, Dict[str, torch.Tensor]]:
+    """Every task's own model back out of stored artifacts of an UNMASKED run (masks are not stored, reload.py:204-205):
+    ``reconstruct_tasks_from_artifacts_masked`` without masks, which see."""
+    return reconstruct_tasks_from_artifacts_masked(artifact_dir, base_state_dict, None, tasks=tasks, output_dir=output_dir,
+                                                   device=device, fused_masks=False)
+
+
+def reconstruct_tasks_from_artifacts_masked(artifact_dir: str, base_state_dict, masks: Optional[Dict[str, torch.Tensor]],
+                                            tasks=None, output_dir: str = None, device: str = "cuda",
+                                            fused_masks: bool = True) -> Dict[str, Dict[str, torch.Tensor]]:
     """Every task's own model back out of stored artifacts: {task: state dict} with ``base + delta_task`` for the
     parameters the artifacts cover and a clone of the base tensor for the others (as apply_merged_deltas does).
     load_all_artifacts -> adopt_artifacts -> merge.reconstruct_task_vectors: two launches per plan for all tasks.  Masks
-    are not stored (reload.py:204-205), so this is exact for unmasked runs only, like ``reconstruct_from_artifacts``.
+    are not stored (reload.py:204-205): without ``masks`` this is exact for unmasked runs only, like
+    ``reconstruct_from_artifacts``; a masked run needs the combined masks it compressed with ({parameter: mask}, on
+    ``device``), and with ``fused_masks`` the rows go back at their source positions inside the streaming launch
+    (svdq_task_reconstruct_masked) wherever a mask selects exactly the stored rows.
     ``base_state_dict``: a state dict or the path of one; ``tasks``: names (None = all); with ``output_dir`` each
     task's state dict is written to ``<output_dir>/<task>.pt``."""
-    from .merge import reconstruct_task_vectors
+    from .merge import reconstruct_task_vectors_masked
     from .driver import adopt_artifacts
     art = load_all_artifacts(artifact_dir, device=device)
     config, diagnostics = art["config"], art["diagnostics"]
@@ -233,12 +245,14 @@ def reconstruct_tasks_from_artifacts(artifact_dir: str, base_state_dict, tasks=N
             if t not in known:
                 raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
     base = _load_base(base_state_dict, device)
-    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    masks = masks or {}
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device,
+                                        masks=masks if fused_masks else None)
     shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
               if d.get("original_shape") is not None}
     covered = {n: b for n, b in base.items() if n in compressed}
-    models = reconstruct_task_vectors(compressed, bases, {}, shapes, config, tasks=tasks, device=device,
-                                      base_state_dict=covered)
+    models = reconstruct_task_vectors_masked(compressed, bases, masks, shapes, config, tasks=tasks, device=device,
+                                             base_state_dict=covered, fused_masks=fused_masks)
     out = {}
     for t, params in models.items():
         out[t] = {n: (params[n] if n in params else b.clone()) for n, b in base.items()}
