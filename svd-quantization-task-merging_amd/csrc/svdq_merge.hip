@@ -26,21 +26,19 @@
 //
 // Per-row arithmetic is that of k_reconstruct / k_recon_error (svdq_elem.hip): fp32 fma chains from 0 over the columns
 // in order, hi + lo, + mean, * scale -- so a parameter's merged rows are the same bits as the per-parameter route's
-// (the diagnostics' sums run in another order: equal to the last digits of the fp64 accumulators).
+// (the diagnostics' sums run in another order: equal to the last digits of the fp64 accumulators).  The four streaming
+// kernels are one program in four arrangements.  Three of them (k_merge_reconstruct, k_task_reconstruct, k_task_expand)
+// are built from the steps of svdq_merge_stream.h (geometry and LDS carve, unit setup, basis staging, row loads, mask
+// selection, coefficient image, fma chains) and keep the order of the steps and their family's epilogue (combine_sets
+// for the merge kernels, task_value for the task kernels).  k_merge_expand carries its own copy of every step and k_diag
+// its own selection and registers -> LDS loop: the comments at the two kernels say why.
 
 #include "svdq_common.h"
 #include "svdq_dispatch.h"
 #include "svdq_input.h"
-#include <hip/hip_fp16.h>
+#include "svdq_merge_stream.h"
 
 #define MRG_MAX_SETS 8
-
-// pointers read out of device tables are generic to the compiler: without the address space it emits flat_load /
-// flat_store, which count on lgkmcnt as well and so make every LDS wait a wait for HBM
-typedef const __attribute__((address_space(1))) float mg_gfloat;
-typedef __attribute__((address_space(1))) float mg_gfloat_w;
-typedef const __attribute__((address_space(1))) uint8_t mg_gbyte;
-typedef const __attribute__((address_space(1))) f32x4 mg_gf32x4;
 
 // ------------------------------------------------------------------------------------ coefficients
 // weights [P or 1][n_sets][N]: weight of task t inside set s, renormalised over the set's present tasks by the caller
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(64) void k_merge_coeff(int NT, int stages, int n_se
 
 // The same for single tasks picked by index: cbar [P][n_out][N] = the coefficients of task[s] -- what k_merge_coeff
 // gives for the one-hot set {task[s]: 1.0} (0 + c * 1, rounded as there), without a weight table.  An index outside
-// [0, N) gives zeros (the streaming launch skips that output).
+// [0, N) gives zeros (the streaming launch skips that output).  task == NULL: task s is s (the diagnostics: all N).
 __global__ __launch_bounds__(64) void k_task_coeff(int NT, int stages, int n_out, const int32_t *__restrict__ task,
                                                    const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
                                                    const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(64) void k_task_coeff(int NT, int stages, int n_out
     const int k = k_in[p], r = r_in[p];
     if (i >= n) return;
     for (int s = 0; s < n_out; ++s) {
-        const int t = task[s];
+        const int t = task ? task[s] : s;
         float acc = 0.f;
         if (i < r && (unsigned)t < (unsigned)n)
             acc = __fadd_rn(acc, __fmul_rn(task_coeff(p, t, i, n, k, stages, chigh, codes, scale, zp), 1.f));
@@ -110,46 +108,12 @@ __global__ __launch_bounds__(64) void k_task_coeff(int NT, int stages, int n_out
 }
 
 // ------------------------------------------------------------------------------------ streaming pass
-template <bool U16> struct UElem;
-template <> struct UElem<true> { using type = __half; };
-template <> struct UElem<false> { using type = float; };
-__device__ __forceinline__ float u_val(const __half *u, int i) { return __half2float(u[i]); }
-__device__ __forceinline__ float u_val(const float *u, int i) { return u[i]; }
-
-__device__ __forceinline__ void lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// where a block's staged basis rows sit (wave-uniform): the two parts are fetched with aligned 16-byte loads and kept
-// row-major, one after the other, in LDS
-struct UStage {
-    int nvh, nv;     // 16-byte vectors of the U_high part, of both parts
-    int offh, offl;  // element offset of the block's first row inside each part
-    int64_t a0h, a0l;
-};
-template <int ES>
-__device__ __forceinline__ UStage ustage_plan(int64_t c0, int nr, int k, int nl) {
-    UStage u;
-    const int64_t b0h = c0 * k * ES, b1h = (c0 + nr) * (int64_t)k * ES;
-    const int64_t b0l = c0 * nl * ES, b1l = (c0 + nr) * (int64_t)nl * ES;
-    u.a0h = b0h & ~15ll;
-    u.a0l = b0l & ~15ll;
-    u.nvh = k > 0 ? (int)((b1h - u.a0h + 15) >> 4) : 0;
-    u.nv = u.nvh + (nl > 0 ? (int)((b1l - u.a0l + 15) >> 4) : 0);
-    u.offh = (int)(b0h - u.a0h) / ES;
-    u.offl = (int)(b0l - u.a0l) / ES;
-    return u;
-}
-
-// One wavefront per work unit of the plan.  Blocks of RB = 64 RPL rows (256 for N <= 16, 128 above: the block's basis
-// rows then fit 9 (fp16) / 17 (fp32) 16-byte registers per lane); lane l owns rows l, 64 + l, ... of a block (conflict-free
-// row reads from the row-major LDS image).  Software pipeline, one block deep: while block b is computed from LDS, the
-// loads of block b + 1 -- its run of basis rows (16-byte loads), its mean and base rows -- are in flight into registers
-// (round 3 loaded a tile, fenced, computed, fenced: nothing was in flight during the compute phase and the counters showed
-// 84 % of the wave cycles waiting).  Columns outermost: one coefficient read serves the lane's rows, the fma chains are
-// independent.  NS = compiled-in number of sets (1, 2, 4, 8 >= n_sets).
+// One wavefront per work unit of the plan, blocks of RB = 64 RPL rows (StreamGeom).  Software pipeline, one block deep:
+// while block b is computed from LDS, the loads of block b + 1 -- its run of basis rows (16-byte loads), its mean and
+// base rows -- are in flight into registers (round 3 loaded a tile, fenced, computed, fenced: nothing was in flight
+// during the compute phase and the counters showed 84 % of the wave cycles waiting).  The staging (ustage_*), the row
+// loads, the coefficient image and the fma chains are the shared pieces of svdq_merge_stream.h; this kernel's own part
+// is combine_sets.  NS = compiled-in number of sets (1, 2, 4, 8 >= n_sets).
 template <bool U16, int NS, int RPL>
 __global__ __launch_bounds__(64) void k_merge_reconstruct(const SvdqParam *__restrict__ params,
                                                           const SvdqUnit *__restrict__ units,
@@ -163,128 +127,56 @@ __global__ __launch_bounds__(64) void k_merge_reconstruct(const SvdqParam *__res
                                                           const float *__restrict__ scale_tab,
                                                           const float *const *__restrict__ base_ptrs,
                                                           float *const *__restrict__ out_ptrs) {
-    using T = typename UElem<U16>::type;
-    constexpr int ES = U16 ? 2 : 4;
-    constexpr int RB = 64 * RPL;
-    constexpr int NMAX = RPL == 4 ? 16 : 32;                          // tasks this block size is launched for
-    constexpr int SV = (RB * NMAX * ES / 16 + 2 + 63) / 64;          // 16-byte vectors of one block's basis rows per lane
-    // dynamic LDS: the staged basis rows (both parts + alignment slack), then the coefficient sets
+    using G = StreamGeom<U16, RPL>;
+    using L = StreamLds<U16, RPL, false>;
+    using T = typename G::T;
+    constexpr int ES = G::ES, RB = G::RB;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NT;
-    const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
-    float *C = reinterpret_cast<float *>(lds_raw + ubytes);   // [column][NS]
-    float *SH = C + NS * n;
+    float *C = reinterpret_cast<float *>(lds_raw + L::coeff_off(n));           // [column][NS]
+    float *SH = reinterpret_cast<float *>(lds_raw + L::share_off(n, NS));
     const SvdqUnit ud = units[blockIdx.x];
     const int p = ud.param;
-    const int64_t D = rows_dev ? rows_dev[p] : params[p].rows;
+    const UnitView uv = unit_view<ES>(params[p], p, rows_dev, k_in, r_in, basis, meanbuf, base_ptrs);
     const int64_t r_begin = ud.row0;
     int64_t r_end = r_begin + ud.nrows;
-    if (r_end > D) r_end = D;
+    if (r_end > uv.D) r_end = uv.D;
     if (r_begin >= r_end) return;
-    const int k = k_in[p], r = r_in[p], nl = r - k;
-    for (int e = lane; e < NS * n; e += 64) {      // transposed: the NS coefficients of a column side by side
-        const int i = e / NS, s = e % NS;
-        C[e] = s < n_sets ? cbar[((size_t)p * n_sets + s) * n + i] : 0.f;
-    }
-    if (lane < NS)
-        SH[lane] = (set_share && lane < n_sets) ? set_share[(per_param ? (size_t)p * n_sets : 0) + lane] : -1.f;
+    const int k = uv.k, nl = uv.nl;
+    stage_coeffs(C, cbar + (size_t)p * n_sets * n, n, n_sets, NS, lane);
+    stage_shares<NS>(SH, set_share, per_param, p, n_sets, lane);
     const float scale = scale_tab ? scale_tab[p] : 1.f;
-    const uint8_t *slab = basis + params[p].slab_off;
-    const uint8_t *gUh = slab;
-    const uint8_t *gUl = slab + svdq_align_up(D * (int64_t)k * ES, 256);
-    mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + params[p].mean_off) : nullptr;
-    mg_gfloat *gbase = base_ptrs ? (mg_gfloat *)base_ptrs[p] : nullptr;
     mg_gfloat_w *gout = (mg_gfloat_w *)out_ptrs[p];
 
     // ---- the loads of one block into registers
-    f32x4 ureg[SV];
+    f32x4 ureg[G::SV];
     float mpf[RPL] = {}, bpf[RPL] = {};
     auto prefetch = [&](int64_t rb) {
-        const int nr = (int)((r_end - rb < RB) ? (r_end - rb) : RB);
-        const UStage us = ustage_plan<ES>(rb, nr, k, nl);
-#pragma unroll
-        for (int s = 0; s < SV; ++s) {
-            const int v = lane + 64 * s;
-            if (v < us.nv) {
-                const uint8_t *gp = (v < us.nvh) ? gUh + us.a0h + 16ll * v : gUl + us.a0l + 16ll * (v - us.nvh);
-                ureg[s] = *(mg_gf32x4 *)gp;
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < RPL; ++m) {      // rows past the block's end are clamped into it (their results are not stored)
-            const int q = 64 * m + lane;
-            const int64_t row = rb + (q < nr ? q : nr - 1);
-            if (gmean) mpf[m] = gmean[row];
-            if (gbase) bpf[m] = gbase[row];
-        }
+        const int nr = block_rows<RB>(rb, r_end);
+        ustage_fetch(ureg, ustage_plan<ES>(rb, nr, k, nl), uv.gUh, uv.gUl, lane);
+        load_rows(mpf, bpf, uv.gmean, uv.gbase, rb, nr, lane);
     };
     prefetch(r_begin);
     for (int64_t rb = r_begin; rb < r_end; rb += RB) {
-        const int rows_blk = (int)((r_end - rb < RB) ? (r_end - rb) : RB);
+        const int rows_blk = block_rows<RB>(rb, r_end);
         // ---- registers -> LDS
         const UStage cur = ustage_plan<ES>(rb, rows_blk, k, nl);
-#pragma unroll
-        for (int s = 0; s < SV; ++s) {
-            const int v = lane + 64 * s;
-            if (v < cur.nv) reinterpret_cast<f32x4 *>(lds_raw)[v] = ureg[s];
-        }
+        ustage_commit(lds_raw, ureg, cur, lane);
         float mv[RPL], bv[RPL];
-        int rl[RPL];      // the lane's rows, clamped into the block
+        int rl[RPL];
+        block_rows_of_lane(rl, rows_blk, lane);
 #pragma unroll
-        for (int m = 0; m < RPL; ++m) {
-            const int q = 64 * m + lane;
-            rl[m] = q < rows_blk ? q : rows_blk - 1;
-            mv[m] = mpf[m];
-            bv[m] = bpf[m];
-        }
+        for (int m = 0; m < RPL; ++m) mv[m] = mpf[m], bv[m] = bpf[m];
         lds_fence();
         // ---- the next block's loads
         if (rb + RB < r_end) prefetch(rb + RB);
         // ---- compute
-        const T *Uh = reinterpret_cast<const T *>(lds_raw) + cur.offh;
-        const T *Ul = reinterpret_cast<const T *>(lds_raw + 16 * cur.nvh) + cur.offl;
         float hi[RPL][NS], lo[RPL][NS];
-#pragma unroll
-        for (int m = 0; m < RPL; ++m)
-#pragma unroll
-            for (int s = 0; s < NS; ++s) hi[m][s] = lo[m][s] = 0.f;
-        for (int i = 0; i < k; ++i) {
-            float c[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) c[s] = C[i * NS + s];
-#pragma unroll
-            for (int m = 0; m < RPL; ++m) {
-                const float u = u_val(Uh, rl[m] * k + i);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) hi[m][s] = fmaf(u, c[s], hi[m][s]);
-            }
-        }
-        for (int j = 0; j < nl; ++j) {
-            float c[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) c[s] = C[(k + j) * NS + s];
-#pragma unroll
-            for (int m = 0; m < RPL; ++m) {
-                const float u = u_val(Ul, rl[m] * nl + j);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) lo[m][s] = fmaf(u, c[s], lo[m][s]);
-            }
-        }
+        fma_chains<T, NS, RPL>(hi, lo, ustage_high<T>(lds_raw, cur), ustage_low<T>(lds_raw, cur), rl, k, nl, C, NS, 0);
 #pragma unroll
         for (int m = 0; m < RPL; ++m) {
-            float res = 0.f;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float v = __fadd_rn(hi[m][s], lo[m][s]);
-                if (gmean) v = __fadd_rn(v, mv[m]);
-                v = __fmul_rn(v, scale);
-                if (set_share) {
-                    if (SH[s] >= 0.f) res = __fadd_rn(res, __fmul_rn(v, SH[s]));   // (stack * w).sum(0), set by set
-                } else if (s == 0) {
-                    res = v;
-                }
-            }
-            if (gbase) res = __fadd_rn(bv[m], res);      // base + delta (merge.py:429-552)
+            float res = combine_sets<NS>(hi[m], lo[m], uv.gmean != nullptr, mv[m], scale, set_share != nullptr, SH);
+            if (uv.gbase) res = __fadd_rn(bv[m], res);      // base + delta (merge.py:429-552)
             if (64 * m + lane < rows_blk) gout[rb + 64 * m + lane] = res;
         }
         lds_fence();      // the basis rows are rewritten next
@@ -292,11 +184,18 @@ __global__ __launch_bounds__(64) void k_merge_reconstruct(const SvdqParam *__res
 }
 
 // ------------------------------------------------------------------------------------ every task's own rows
+// bit j: task j of the call is formed for this parameter (wave-uniform); outp = the parameter's n_out output pointers
+__device__ __forceinline__ unsigned task_live_mask(float *const *outp, const int32_t *__restrict__ task, int n_out, int n,
+                                                   int lane) {
+    return (unsigned)__ballot(lane < n_out && outp[lane < n_out ? lane : 0] != nullptr &&
+                              (unsigned)task[lane < n_out ? lane : 0] < (unsigned)n);
+}
+
 // reconstruct_from_coefficients (merge.py:144-194) for n_out tasks of the plan in ONE pass over the basis: the block's
-// basis rows are staged once (k_merge_reconstruct's staging, LDS image and one-block pipeline) and read from LDS once per
-// group of TG tasks; every task of a group has its own pair of fma chains per row and its own store stream (lane l
-// owns rows l, 64 + l, ...: 256 contiguous bytes per task and store instruction).  Nothing is combined across tasks,
-// so out[p][j] is what k_merge_reconstruct writes for a single set that holds task j alone.
+// basis rows are staged once (the shared staging, LDS image and one-block pipeline of k_merge_reconstruct) and read from
+// LDS once per group of TG tasks; every task of a group has its own pair of fma chains per row and its own store stream
+// (lane l owns rows l, 64 + l, ...: 256 contiguous bytes per task and store instruction).  Nothing is combined across
+// tasks (task_value), so out[p][j] is what k_merge_reconstruct writes for a single set that holds task j alone.
 //   cbar  [P][n_out][N]: the tasks' coefficients (k_task_coeff)
 //   task  [n_out] plan task indices; an index outside [0, N) is skipped like a NULL output
 //   out   [P][n_out] fp32 outputs; NULL = this (parameter, task) is not formed
@@ -314,88 +213,52 @@ __global__ __launch_bounds__(64) void k_task_reconstruct(const SvdqParam *__rest
                                                          const float *__restrict__ scale_tab,
                                                          const float *const *__restrict__ base_ptrs,
                                                          float *const *__restrict__ out_ptrs) {
-    using T = typename UElem<U16>::type;
-    constexpr int ES = U16 ? 2 : 4;
-    constexpr int RB = 64 * RPL;
-    constexpr int NMAX = RPL == 4 ? 16 : 32;
-    constexpr int SV = (RB * NMAX * ES / 16 + 2 + 63) / 64;
-    // dynamic LDS: the staged basis rows (both parts + alignment slack), then the coefficients [column][nop]
+    using G = StreamGeom<U16, RPL>;
+    using L = StreamLds<U16, RPL, false>;
+    using T = typename G::T;
+    constexpr int ES = G::ES, RB = G::RB;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NT;
     const int nop = (n_out + TG - 1) / TG * TG;      // tasks padded to whole groups
-    const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
-    float *C = reinterpret_cast<float *>(lds_raw + ubytes);
+    float *C = reinterpret_cast<float *>(lds_raw + L::coeff_off(n));           // [column][nop]
     const SvdqUnit ud = units[blockIdx.x];
     const int p = ud.param;
-    const int64_t D = rows_dev ? rows_dev[p] : params[p].rows;
+    const UnitView uv = unit_view<ES>(params[p], p, rows_dev, k_in, r_in, basis, meanbuf, base_ptrs);
     const int64_t r_begin = ud.row0;
     int64_t r_end = r_begin + ud.nrows;
-    if (r_end > D) r_end = D;
+    if (r_end > uv.D) r_end = uv.D;
     if (r_begin >= r_end) return;
     float *const *outp = out_ptrs + (size_t)p * n_out;
-    // bit j: task j of the call is formed for this parameter (wave-uniform)
-    const unsigned live = (unsigned)__ballot(lane < n_out && outp[lane < n_out ? lane : 0] != nullptr &&
-                                             (unsigned)task[lane < n_out ? lane : 0] < (unsigned)n);
+    const unsigned live = task_live_mask(outp, task, n_out, n, lane);
     if (!live) return;
-    const int k = k_in[p], r = r_in[p], nl = r - k;
-    for (int e = lane; e < nop * n; e += 64) {      // transposed: the tasks' coefficients of a column side by side
-        const int i = e / nop, s = e % nop;
-        C[e] = s < n_out ? cbar[((size_t)p * n_out + s) * n + i] : 0.f;
-    }
+    const int k = uv.k, nl = uv.nl;
+    stage_coeffs(C, cbar + (size_t)p * n_out * n, n, n_out, nop, lane);
     const float scale = scale_tab ? scale_tab[p] : 1.f;
-    const uint8_t *slab = basis + params[p].slab_off;
-    const uint8_t *gUh = slab;
-    const uint8_t *gUl = slab + svdq_align_up(D * (int64_t)k * ES, 256);
-    mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + params[p].mean_off) : nullptr;
-    mg_gfloat *gbase = base_ptrs ? (mg_gfloat *)base_ptrs[p] : nullptr;
 
     // ---- the loads of one block into registers
-    f32x4 ureg[SV];
+    f32x4 ureg[G::SV];
     float mpf[RPL] = {}, bpf[RPL] = {};
     auto prefetch = [&](int64_t rb) {
-        const int nr = (int)((r_end - rb < RB) ? (r_end - rb) : RB);
-        const UStage us = ustage_plan<ES>(rb, nr, k, nl);
-#pragma unroll
-        for (int s = 0; s < SV; ++s) {
-            const int v = lane + 64 * s;
-            if (v < us.nv) {
-                const uint8_t *gp = (v < us.nvh) ? gUh + us.a0h + 16ll * v : gUl + us.a0l + 16ll * (v - us.nvh);
-                ureg[s] = *(mg_gf32x4 *)gp;
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < RPL; ++m) {      // rows past the block's end are clamped into it (their results are not stored)
-            const int q = 64 * m + lane;
-            const int64_t row = rb + (q < nr ? q : nr - 1);
-            if (gmean) mpf[m] = gmean[row];
-            if (gbase) bpf[m] = gbase[row];
-        }
+        const int nr = block_rows<RB>(rb, r_end);
+        ustage_fetch(ureg, ustage_plan<ES>(rb, nr, k, nl), uv.gUh, uv.gUl, lane);
+        load_rows(mpf, bpf, uv.gmean, uv.gbase, rb, nr, lane);
     };
     prefetch(r_begin);
     for (int64_t rb = r_begin; rb < r_end; rb += RB) {
-        const int rows_blk = (int)((r_end - rb < RB) ? (r_end - rb) : RB);
+        const int rows_blk = block_rows<RB>(rb, r_end);
         // ---- registers -> LDS
         const UStage cur = ustage_plan<ES>(rb, rows_blk, k, nl);
-#pragma unroll
-        for (int s = 0; s < SV; ++s) {
-            const int v = lane + 64 * s;
-            if (v < cur.nv) reinterpret_cast<f32x4 *>(lds_raw)[v] = ureg[s];
-        }
+        ustage_commit(lds_raw, ureg, cur, lane);
         float mv[RPL], bv[RPL];
-        int rl[RPL];      // the lane's rows, clamped into the block
+        int rl[RPL];
+        block_rows_of_lane(rl, rows_blk, lane);
 #pragma unroll
-        for (int m = 0; m < RPL; ++m) {
-            const int q = 64 * m + lane;
-            rl[m] = q < rows_blk ? q : rows_blk - 1;
-            mv[m] = mpf[m];
-            bv[m] = bpf[m];
-        }
+        for (int m = 0; m < RPL; ++m) mv[m] = mpf[m], bv[m] = bpf[m];
         lds_fence();
         // ---- the next block's loads
         if (rb + RB < r_end) prefetch(rb + RB);
         // ---- compute: one pass over the LDS image per group of TG tasks
-        const T *Uh = reinterpret_cast<const T *>(lds_raw) + cur.offh;
-        const T *Ul = reinterpret_cast<const T *>(lds_raw + 16 * cur.nvh) + cur.offl;
+        const T *Uh = ustage_high<T>(lds_raw, cur), *Ul = ustage_low<T>(lds_raw, cur);
         for (int g0 = 0; g0 < n_out; g0 += TG) {
             const unsigned gm = (live >> g0) & ((1u << TG) - 1u);
             if (!gm) continue;
@@ -403,41 +266,14 @@ __global__ __launch_bounds__(64) void k_task_reconstruct(const SvdqParam *__rest
 #pragma unroll
             for (int s = 0; s < TG; ++s) o[s] = (mg_gfloat_w *)outp[g0 + s < n_out ? g0 + s : g0];
             float hi[RPL][TG], lo[RPL][TG];
-#pragma unroll
-            for (int m = 0; m < RPL; ++m)
-#pragma unroll
-                for (int s = 0; s < TG; ++s) hi[m][s] = lo[m][s] = 0.f;
-            for (int i = 0; i < k; ++i) {
-                float c[TG];
-#pragma unroll
-                for (int s = 0; s < TG; ++s) c[s] = C[i * nop + g0 + s];
-#pragma unroll
-                for (int m = 0; m < RPL; ++m) {
-                    const float u = u_val(Uh, rl[m] * k + i);
-#pragma unroll
-                    for (int s = 0; s < TG; ++s) hi[m][s] = fmaf(u, c[s], hi[m][s]);
-                }
-            }
-            for (int j = 0; j < nl; ++j) {
-                float c[TG];
-#pragma unroll
-                for (int s = 0; s < TG; ++s) c[s] = C[(k + j) * nop + g0 + s];
-#pragma unroll
-                for (int m = 0; m < RPL; ++m) {
-                    const float u = u_val(Ul, rl[m] * nl + j);
-#pragma unroll
-                    for (int s = 0; s < TG; ++s) lo[m][s] = fmaf(u, c[s], lo[m][s]);
-                }
-            }
+            fma_chains<T, TG, RPL>(hi, lo, Uh, Ul, rl, k, nl, C, nop, g0);
 #pragma unroll
             for (int s = 0; s < TG; ++s) {
                 if (!((gm >> s) & 1u)) continue;      // wave-uniform
 #pragma unroll
                 for (int m = 0; m < RPL; ++m) {
-                    float v = __fadd_rn(hi[m][s], lo[m][s]);
-                    if (gmean) v = __fadd_rn(v, mv[m]);
-                    v = __fmul_rn(v, scale);
-                    if (gbase) v = __fadd_rn(bv[m], v);      // base + delta (merge.py:429-552)
+                    const float v = task_value(hi[m][s], lo[m][s], uv.gmean != nullptr, mv[m], scale, true,
+                                               uv.gbase != nullptr, bv[m]);
                     if (64 * m + lane < rows_blk) o[s][rb + 64 * m + lane] = v;
                 }
             }
@@ -450,32 +286,33 @@ __global__ __launch_bounds__(64) void k_task_reconstruct(const SvdqParam *__rest
 // reconstruct_from_masked (mask_loader.py:712-763) fused into the merge: the artifacts of a masked region describe the
 // COMPACTED rows, the merged tensor wants them back at their source positions.  A unit of the plan owns the source rows
 // from its first selected element (ustart[u], svdq_maskset_*_starts -- the table the mask-walk compressor uses) to the
-// next unit's; the first unit of a parameter starts at 0, the last ends with the tensor.  Per chunk of 256 source rows
-// (lane l owns rows src + 64 e + l: every load and store is 256 contiguous bytes):
-//   mask bytes -> four ballots -> compacted row of every selected source row (no index list, no scan through memory);
+// next unit's; the first unit of a parameter starts at 0, the last ends with the tensor (unit_source_range).  Per chunk
+// of RB source rows (lane l owns rows src + 64 e + l: every load and store is 256 contiguous bytes):
+//   mask bytes -> ballots -> compacted row of every selected source row (no index list, no scan through memory);
 //   the chunk's run of basis rows [cpos, cpos + selected) is contiguous in U_high / U_low: staged in LDS by 16-byte loads;
 //   selected rows get the merged value (same per-row arithmetic as k_merge_reconstruct), the others 0 when ``fill``
 //   (no noise region writes them) or are left to the noise region's launch; base is added at the SOURCE row.
-#define MRG_POS_MASK ((1ll << 62) - 1)      // ustart: bit 62 = the region takes the cleared mask elements
-
-struct SrcRange {
-    int64_t lo, hi;
-    int inv;
-};
-__device__ __forceinline__ SrcRange unit_source_range(const SvdqParam &pd, int u, const int64_t *__restrict__ ustart) {
-    const int64_t us = ustart[u];
-    SrcRange s;
-    s.inv = (int)((us >> 62) & 1);
-    s.lo = (u == pd.unit_begin) ? 0 : (us & MRG_POS_MASK);
-    s.hi = (u == pd.unit_begin + pd.unit_count - 1) ? pd.rows : (ustart[u + 1] & MRG_POS_MASK);
-    return s;
+//
+// One wavefront per work unit; chunk = RB = 64 RPL SOURCE rows (256 for N <= 16, 128 above).  The same one-block
+// software pipeline as k_merge_reconstruct: while chunk c is computed from LDS, chunk c + 1's mask bytes and base rows
+// and -- from the compacted position where chunk c ends, known once c's mask has been counted -- the next RB basis rows
+// and mean values (clamped to the unit; how many of them chunk c + 1 selects is not known before its mask is, so a full
+// block is fetched) are in flight into registers.
+//
+// This kernel keeps its own text for every step (k_task_expand is the same walk built from the shared pieces, with
+// walk_select's bit field where this kernel has the lane masks in[] / sel[]): at 128-row
+// chunks of an fp32 basis it sits at 124 (NS 1) and 126 (NS 2) vector registers, four waves per SIMD, and every
+// arrangement of the shared pieces that was compiled -- walk_select's bit field or the lane masks below, the staging as
+// functions or as loops, down to replacing the LDS carve alone -- came out at 129 to 154 registers there: three waves.
+// StreamLds<U16, RPL, true>::bytes(n, NS, NS), which sizes the launch, is the carve written out below; the
+// static_assert in the kernel holds the two to each other at every task count.
+template <bool U16, int NS, int RPL> constexpr bool merge_expand_carve_fits() {
+    for (int n = 1; n <= SVDQ_MAX_TASKS; ++n) {      // ubytes + M[RB] + C[n][NS] + SH[NS], as carved below
+        const size_t ubytes = (size_t)(((int64_t)64 * RPL * n * (U16 ? 2 : 4) + 48 + 15) / 16 * 16);
+        if (ubytes + 64 * RPL * 4 + (size_t)(NS * n + NS) * 4 != StreamLds<U16, RPL, true>::bytes(n, NS, NS)) return false;
+    }
+    return true;
 }
-
-// One wavefront per work unit; chunk = RB = 64 RPL SOURCE rows (256 for N <= 16, 128 above), lane l owns rows
-// src + 64 e + l.  The same one-block software pipeline as k_merge_reconstruct: while chunk c is computed from LDS, chunk
-// c + 1's mask bytes and base rows and -- from the compacted position where chunk c ends, known once c's mask has been
-// counted -- the next RB basis rows and mean values (clamped to the unit; how many of them chunk c + 1 selects is not
-// known before its mask is, so a full block is fetched) are in flight into registers.
 template <bool U16, int NS, int RPL>
 __global__ __launch_bounds__(64) void k_merge_expand(const SvdqParam *__restrict__ params,
                                                      const SvdqUnit *__restrict__ units,
@@ -497,6 +334,7 @@ __global__ __launch_bounds__(64) void k_merge_expand(const SvdqParam *__restrict
     constexpr int NMAX = RPL == 4 ? 16 : 32;
     constexpr int SV = (RB * NMAX * ES / 16 + 2 + 63) / 64;
     // dynamic LDS: the staged basis rows, the staged mean values, the coefficient sets
+    static_assert(merge_expand_carve_fits<U16, NS, RPL>(), "the launch is sized by StreamLds: the carve must end where it ends");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, u = blockIdx.x, n = NT;
     const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
@@ -675,10 +513,11 @@ __global__ __launch_bounds__(64) void k_merge_expand(const SvdqParam *__restrict
 // ------------------------------------------------------------------------------------ masked parameters: every task's own rows
 // k_task_reconstruct's task groups on k_merge_expand's source walk: reconstruct_from_masked (mask_loader.py:712-763)
 // inside the one pass over the basis that forms every selected task's own rows.  The walk, the selection (ballot ranks
-// clamped to the unit's compacted rows), the staging and the one-chunk pipeline are k_merge_expand's; the chunk's LDS
-// image is read once per group of TG tasks, every task of a group has its own pair of fma chains per row (indexed by the
-// row's rank) and its own store stream at the SOURCE row (256 contiguous bytes per task and store instruction).  Nothing
-// is combined across tasks, so out[p][j] is what k_merge_expand<., 1, .> writes for the one-hot set {task[j]: 1.0}.
+// clamped to the unit's compacted rows), the staging and the one-chunk pipeline are the shared pieces k_merge_expand is
+// made of; the chunk's LDS image is read once per group of TG tasks, every task of a group has its own pair of fma
+// chains per row (indexed by the row's rank) and its own store stream at the SOURCE row (256 contiguous bytes per task
+// and store instruction).  Nothing is combined across tasks (task_value), so out[p][j] is what k_merge_expand<., 1, .>
+// writes for the one-hot set {task[j]: 1.0}.
 //   cbar  [P][n_out][N]: the tasks' coefficients (k_task_coeff)
 //   task  [n_out] plan task indices; an index outside [0, N) is skipped like a NULL output
 //   out   [P][n_out] FULL fp32 tensors; NULL = this (parameter, task) is not formed.  All NULL = the unit reads nothing.
@@ -696,111 +535,51 @@ __global__ __launch_bounds__(64) void k_task_expand(const SvdqParam *__restrict_
                                                     const int32_t *__restrict__ fill_tab,
                                                     const float *const *__restrict__ base_ptrs,
                                                     float *const *__restrict__ out_ptrs) {
-    using T = typename UElem<U16>::type;
-    constexpr int ES = U16 ? 2 : 4;
-    constexpr int RB = 64 * RPL;
-    constexpr int NMAX = RPL == 4 ? 16 : 32;
-    constexpr int SV = (RB * NMAX * ES / 16 + 2 + 63) / 64;
-    // dynamic LDS: the staged basis rows, the staged mean values, the coefficients [column][nop]
+    using G = StreamGeom<U16, RPL>;
+    using L = StreamLds<U16, RPL, true>;
+    using T = typename G::T;
+    constexpr int ES = G::ES, RB = G::RB;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, u = blockIdx.x, n = NT;
     const int nop = (n_out + TG - 1) / TG * TG;      // tasks padded to whole groups
-    const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
-    float *M = reinterpret_cast<float *>(lds_raw + ubytes);      // [RB]
-    float *C = M + RB;                                           // [column][nop]
+    float *M = reinterpret_cast<float *>(lds_raw + L::mean_off(n));            // [RB]
+    float *C = reinterpret_cast<float *>(lds_raw + L::coeff_off(n));           // [column][nop]
     const SvdqUnit ud = units[u];
     const int p = ud.param;
     float *const *outp = out_ptrs + (size_t)p * n_out;
-    // bit j: task j of the call is formed for this parameter (wave-uniform)
-    const unsigned live = (unsigned)__ballot(lane < n_out && outp[lane < n_out ? lane : 0] != nullptr &&
-                                             (unsigned)task[lane < n_out ? lane : 0] < (unsigned)n);
+    const unsigned live = task_live_mask(outp, task, n_out, n, lane);
     if (!live) return;      // an entry the caller does not reconstruct
     const SvdqParam pd = params[p];
     const SrcRange sr = unit_source_range(pd, u, ustart);
     if (sr.lo >= sr.hi) return;
-    const int64_t D = rows_dev ? rows_dev[p] : pd.rows;      // compacted rows of the region
+    const UnitView uv = unit_view<ES>(pd, p, rows_dev, k_in, r_in, basis, meanbuf, base_ptrs);
     int64_t cpos = ud.row0;
     int64_t cend = ud.row0 + ud.nrows;
-    if (cend > D) cend = D;
+    if (cend > uv.D) cend = uv.D;
     if (cpos > cend) cpos = cend;
-    const int k = k_in[p], r = r_in[p], nl = r - k;
-    for (int e = lane; e < nop * n; e += 64) {      // transposed: the tasks' coefficients of a column side by side
-        const int i = e / nop, s = e % nop;
-        C[e] = s < n_out ? cbar[((size_t)p * n_out + s) * n + i] : 0.f;
-    }
+    const int k = uv.k, nl = uv.nl;
+    stage_coeffs(C, cbar + (size_t)p * n_out * n, n, n_out, nop, lane);
     const float scale = scale_tab ? scale_tab[p] : 1.f;
     const bool fill = fill_tab ? fill_tab[p] != 0 : false;
-    const uint8_t *slab = basis + pd.slab_off;
-    const uint8_t *gUh = slab;
-    const uint8_t *gUl = slab + svdq_align_up(D * (int64_t)k * ES, 256);
-    mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
-    mg_gfloat *gbase = base_ptrs ? (mg_gfloat *)base_ptrs[p] : nullptr;
     mg_gbyte *gmask = (mg_gbyte *)mask_ptrs[p];
 
     // ---- the loads of one chunk into registers
-    unsigned mk[RPL];      // mask bytes; 0x100 = past the end of the range: selected by neither polarity
+    unsigned mk[RPL];
     float bpf[RPL] = {}, mpf[RPL] = {};
-    f32x4 ureg[SV];
+    f32x4 ureg[G::SV];
     auto prefetch = [&](int64_t s0, int64_t c0) {
-        const int64_t r0 = s0 + lane;
-        if (s0 + RB <= sr.hi) {
-#pragma unroll
-            for (int e = 0; e < RPL; ++e) {
-                mk[e] = (unsigned)gmask[r0 + 64 * e];
-                if (gbase) bpf[e] = gbase[r0 + 64 * e];
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < RPL; ++e) {
-                const bool in = r0 + 64 * e < sr.hi;
-                mk[e] = in ? (unsigned)gmask[r0 + 64 * e] : 0x100u;
-                if (gbase) bpf[e] = in ? gbase[r0 + 64 * e] : 0.f;
-            }
-        }
-        const int nr = (int)((cend - c0 < RB) ? (cend - c0) : RB);
-        if (gmean) {
-#pragma unroll
-            for (int e = 0; e < RPL; ++e) mpf[e] = (64 * e + lane < nr) ? gmean[c0 + 64 * e + lane] : 0.f;
-        }
-        const UStage us = ustage_plan<ES>(c0, nr, k, nl);
-#pragma unroll
-        for (int s = 0; s < SV; ++s) {
-            const int v = lane + 64 * s;
-            if (v < us.nv) {
-                const uint8_t *gp = (v < us.nvh) ? gUh + us.a0h + 16ll * v : gUl + us.a0l + 16ll * (v - us.nvh);
-                ureg[s] = *(mg_gf32x4 *)gp;
-            }
-        }
+        const int nr = block_rows<RB>(c0, cend);
+        load_rows_walk(mk, bpf, mpf, gmask, uv.gbase, uv.gmean, s0, sr.hi, c0, nr, lane);
+        ustage_fetch(ureg, ustage_plan<ES>(c0, nr, k, nl), uv.gUh, uv.gUl, lane);
     };
     prefetch(sr.lo, cpos);
     for (int64_t src = sr.lo; src < sr.hi; src += RB) {
         // ---- the chunk's selection: rank of each of the lane's rows among the chunk's selected rows, and their number
-        // (the lane's own flags in one vector register: bit m = row m is selected, bit 4 + m = it is inside the range --
-        // as lane masks they would hold sixteen scalar registers across the task groups)
-        unsigned flags = 0;
-        int rank[RPL], count;
-        {
-            int base = 0;
-            const int64_t room = cend - cpos;
-#pragma unroll
-            for (int e = 0; e < RPL; ++e) {
-                if (mk[e] != 0x100u) flags |= 16u << e;
-                const bool sb = sr.inv ? (mk[e] == 0u) : (mk[e] != 0u && mk[e] != 0x100u);
-                const unsigned long long bal = __ballot(sb);
-                rank[e] = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                if (sb && rank[e] < room) flags |= 1u << e;      // never past the unit's compacted rows, whatever the mask says
-                base += (int)__popcll(bal);
-            }
-            count = base < room ? base : (int)room;
-        }
+        const WalkSel<RPL> w = walk_select(mk, sr.inv, cend - cpos);
         // ---- registers -> LDS
-        const UStage cur = ustage_plan<ES>(cpos, (int)((cend - cpos < RB) ? (cend - cpos) : RB), k, nl);
-#pragma unroll
-        for (int s = 0; s < SV; ++s) {
-            const int v = lane + 64 * s;
-            if (v < cur.nv) reinterpret_cast<f32x4 *>(lds_raw)[v] = ureg[s];
-        }
-        if (gmean) {
+        const UStage cur = ustage_plan<ES>(cpos, block_rows<RB>(cpos, cend), k, nl);
+        ustage_commit(lds_raw, ureg, cur, lane);
+        if (uv.gmean) {
 #pragma unroll
             for (int e = 0; e < RPL; ++e) M[64 * e + lane] = mpf[e];
         }
@@ -809,49 +588,19 @@ __global__ __launch_bounds__(64) void k_task_expand(const SvdqParam *__restrict_
         for (int m = 0; m < RPL; ++m) bv[m] = bpf[m];
         lds_fence();
         // ---- the next chunk's loads
-        if (src + RB < sr.hi) prefetch(src + RB, cpos + count);
+        if (src + RB < sr.hi) prefetch(src + RB, cpos + w.count);
         // ---- compute: one pass over the LDS image per group of TG tasks
-        const T *Uh = reinterpret_cast<const T *>(lds_raw) + cur.offh;
-        const T *Ul = reinterpret_cast<const T *>(lds_raw + 16 * cur.nvh) + cur.offl;
+        const T *Uh = ustage_high<T>(lds_raw, cur), *Ul = ustage_low<T>(lds_raw, cur);
         int rl[RPL];
         float mv[RPL];
-#pragma unroll
-        for (int m = 0; m < RPL; ++m) {
-            rl[m] = ((flags >> m) & 1u) ? rank[m] : 0;
-            mv[m] = (gmean && count > 0) ? M[rl[m]] : 0.f;
-        }
+        walk_rows_of_lane(rl, mv, w, M, uv.gmean && w.count > 0);
+        // a chunk that selects nothing only fills: its chains have no columns (wave-uniform)
+        const int kc = w.count > 0 ? k : 0, nlc = w.count > 0 ? nl : 0;
         for (int g0 = 0; g0 < n_out; g0 += TG) {
             const unsigned gm = (live >> g0) & ((1u << TG) - 1u);
             if (!gm) continue;
             float hi[RPL][TG], lo[RPL][TG];
-#pragma unroll
-            for (int m = 0; m < RPL; ++m)
-#pragma unroll
-                for (int s = 0; s < TG; ++s) hi[m][s] = lo[m][s] = 0.f;
-            if (count > 0) {      // wave-uniform; a chunk that selects nothing only fills
-                for (int i = 0; i < k; ++i) {
-                    float c[TG];
-#pragma unroll
-                    for (int s = 0; s < TG; ++s) c[s] = C[i * nop + g0 + s];
-#pragma unroll
-                    for (int m = 0; m < RPL; ++m) {
-                        const float uv = u_val(Uh, rl[m] * k + i);
-#pragma unroll
-                        for (int s = 0; s < TG; ++s) hi[m][s] = fmaf(uv, c[s], hi[m][s]);
-                    }
-                }
-                for (int j = 0; j < nl; ++j) {
-                    float c[TG];
-#pragma unroll
-                    for (int s = 0; s < TG; ++s) c[s] = C[(k + j) * nop + g0 + s];
-#pragma unroll
-                    for (int m = 0; m < RPL; ++m) {
-                        const float uv = u_val(Ul, rl[m] * nl + j);
-#pragma unroll
-                        for (int s = 0; s < TG; ++s) lo[m][s] = fmaf(uv, c[s], lo[m][s]);
-                    }
-                }
-            }
+            fma_chains<T, TG, RPL>(hi, lo, Uh, Ul, rl, kc, nlc, C, nop, g0);
 #pragma unroll
             for (int s = 0; s < TG; ++s) {
                 if (!((gm >> s) & 1u)) continue;      // wave-uniform
@@ -860,18 +609,14 @@ __global__ __launch_bounds__(64) void k_task_expand(const SvdqParam *__restrict_
                 mg_gfloat_w *o = (mg_gfloat_w *)outp[g0 + s];
 #pragma unroll
                 for (int m = 0; m < RPL; ++m) {
-                    float v = __fadd_rn(hi[m][s], lo[m][s]);
-                    if (gmean) v = __fadd_rn(v, mv[m]);
-                    v = __fmul_rn(v, scale);
-                    const bool sel = (flags >> m) & 1u, in = (flags >> (4 + m)) & 1u;
-                    v = sel ? v : 0.f;
-                    if (gbase) v = __fadd_rn(bv[m], v);      // base + delta (merge.py:429-552)
-                    if (in && (sel || fill)) o[src + 64 * m + lane] = v;
+                    const float v = task_value(hi[m][s], lo[m][s], uv.gmean != nullptr, mv[m], scale, w.sel(m),
+                                               uv.gbase != nullptr, bv[m]);
+                    if (w.in(m) && (w.sel(m) || fill)) o[src + 64 * m + lane] = v;
                 }
             }
         }
         lds_fence();
-        cpos += count;
+        cpos += w.count;
     }
 }
 
@@ -957,9 +702,8 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = FULL ? NTP : NT, u = blockIdx.x;
     const int g = lane >> 4, col = lane & 15;
-    const int ubytes = (int)svdq_align_up((int64_t)RB * n * ES + 48, 16);
     uint8_t *Ubuf = lds_raw;
-    float *X = reinterpret_cast<float *>(lds_raw + ubytes);      // [NTP tasks + mean][XSD]
+    float *X = reinterpret_cast<float *>(lds_raw + stream_ubytes(RB, n, ES));      // [NTP tasks + mean][XSD]
     const SvdqUnit ud = units[u];
     const int p = ud.param;
     const SvdqParam pd = params[p];
@@ -1083,19 +827,12 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
 #pragma unroll
                 for (int e = 0; e < RPL; ++e) mpf[e] = (64 * e + lane < nr) ? gmean[c0 + 64 * e + lane] : 0.f;
             }
-            const UStage us = ustage_plan<ES>(c0, nr, k, nl);
-#pragma unroll
-            for (int s = 0; s < SV; ++s) {
-                const int v = lane + 64 * s;
-                if (v < us.nv) {
-                    const uint8_t *gp = (v < us.nvh) ? gUh + us.a0h + 16ll * v : gUl + us.a0l + 16ll * (v - us.nvh);
-                    ureg[s] = *(mg_gf32x4 *)gp;
-                }
-            }
+            ustage_fetch(ureg, ustage_plan<ES>(c0, nr, k, nl), gUh, gUl, lane);
         };
         prefetch(src, cpos);
         while (true) {
-            // ---- selection of the block whose data sits in the registers
+            // ---- selection of the block whose data sits in the registers (walk_select's ranks, written out with the
+            // slot taken straight from the lane mask: from the bit field the kernel is 19 instructions longer and ran 2-3 % slower)
             int count;
             int slot[RPL];      // WALK: where the lane's rows go in the strips
             if constexpr (WALK) {
@@ -1116,7 +853,8 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                 count = (int)((src_hi - src < RB) ? (src_hi - src) : RB);
             }
             // ---- registers -> LDS (the staging layout is a function of the block's first row: recomputed, not kept)
-            const UStage cur = ustage_plan<ES>(cpos, (int)((cend - cpos < RB) ? (cend - cpos) : RB), k, nl);
+            const UStage cur = ustage_plan<ES>(cpos, block_rows<RB>(cpos, cend), k, nl);
+            // (ustage_commit's loop, written out: as a call it costs this kernel two to fourteen more scalar spills)
 #pragma unroll
             for (int s = 0; s < SV; ++s) {
                 const int v = lane + 64 * s;
@@ -1331,6 +1069,21 @@ __global__ __launch_bounds__(64) void k_diag_finish(const SvdqParam *__restrict_
 }
 
 // ------------------------------------------------------------------------------------ entry points
+// typed pointers into the packed small-artifact buffer the compressor left in HBM
+struct SmallView {
+    const int32_t *k, *r;
+    const uint16_t *chigh;
+    const uint8_t *codes;
+    const float *scale, *zp;
+};
+static SmallView small_view(const svdq_plan *pl, const void *small) {
+    const svdq_small_layout &L = pl->small;
+    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
+    return {reinterpret_cast<const int32_t *>(sm + L.k_off),   reinterpret_cast<const int32_t *>(sm + L.r_off),
+            reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
+            reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off)};
+}
+
 static int merge_args_ok(const svdq_plan *pl, const void *small, int32_t n_sets, const char *who) {
     if (!pl || !small) {
         svdq_set_error("%s: plan and small are required", who);
@@ -1355,15 +1108,23 @@ extern "C" int svdq_merge_coeffs(const svdq_plan *pl, const void *small, const f
         svdq_set_error("svdq_merge_coeffs: weights and cbar are required");
         return SVDQ_EINVAL;
     }
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
+    const SmallView sv = small_view(pl, small);
     hipLaunchKernelGGL(k_merge_coeff, dim3(pl->n_params), dim3(64), 0, (hipStream_t)stream, pl->n_tasks,
-                       pl->cfg.rtvq_stages, n_sets, per_param, reinterpret_cast<const int32_t *>(sm + L.k_off),
-                       reinterpret_cast<const int32_t *>(sm + L.r_off), reinterpret_cast<const uint16_t *>(sm + L.chigh_off),
-                       sm + L.codes_off, reinterpret_cast<const float *>(sm + L.scale_off),
-                       reinterpret_cast<const float *>(sm + L.zp_off), weights, order, cbar);
+                       pl->cfg.rtvq_stages, n_sets, per_param, sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, weights,
+                       order, cbar);
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
+
+// the coefficients of single tasks: task [n_out] plan task indices, NULL = tasks 0 .. n_out - 1
+static void launch_task_coeff(const svdq_plan *pl, const void *small, const int32_t *task, int n_out, float *cbar,
+                              hipStream_t st) {
+    const SmallView sv = small_view(pl, small);
+    hipLaunchKernelGGL(k_task_coeff, dim3(pl->n_params), dim3(64), 0, st, pl->n_tasks, pl->cfg.rtvq_stages, n_out, task,
+                       sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, cbar);
+}
+
+// rows per lane and block of the four streaming kernels (256 / 128 rows: a block's basis rows stay <= 17 vectors per lane)
+static int stream_rpl(const svdq_plan *pl) { return pl->n_tasks <= 16 ? 4 : 2; }
 
 // the streaming launch of svdq_merge_reconstruct (mask_ptrs == NULL) and svdq_merge_masked (source walk)
 static int launch_reconstruct(const char *who, const svdq_plan *pl, const int64_t *rows_dev, const void *small,
@@ -1384,33 +1145,31 @@ static int launch_reconstruct(const char *who, const svdq_plan *pl, const int64_
         svdq_set_error("%s: set_share is required when n_sets > 1", who);
         return SVDQ_EINVAL;
     }
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    const SmallView sv = small_view(pl, small);
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
     hipStream_t st = (hipStream_t)stream;
+    const int n = pl->n_tasks;
     const int ns = n_sets == 1 ? 1 : (n_sets == 2 ? 2 : (n_sets <= 4 ? 4 : 8));
-    const int rpl = pl->n_tasks <= 16 ? 4 : 2;      // rows per lane and block (256 / 128 rows: a block's basis rows stay <= 17 vectors per lane)
-    const size_t lds = (size_t)svdq_align_up((int64_t)64 * rpl * pl->n_tasks * (pl->cfg.fp16 ? 2 : 4) + 48, 16) +
-                       (mp ? (size_t)64 * rpl * 4 : 0) + (size_t)(ns * pl->n_tasks + ns) * 4;
     const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
     const float *mn = pl->cfg.center ? mean : nullptr;
     const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
         constexpr bool F16 = f16_c;
         return svdq_dispatch_int<1, 2, 4, 8>(ns, [&](auto ns_c) {
             constexpr int NS = ns_c;
-            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
+            return svdq_dispatch_int<4, 2>(stream_rpl(pl), [&](auto rpl_c) {
                 constexpr int RPL = rpl_c;
+                using Walk = StreamLds<F16, RPL, true>;
+                using Plain = StreamLds<F16, RPL, false>;
                 if (mp)
-                    hipLaunchKernelGGL((k_merge_expand<F16, NS, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
-                                       pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn, cbar,
-                                       set_share, scale, mp, unit_start, fill, bp, op);
+                    hipLaunchKernelGGL((k_merge_expand<F16, NS, RPL>), dim3(pl->n_units), dim3(64), Walk::bytes(n, NS, NS),
+                                       st, pl->d_params, pl->d_units, rows_dev, n, n_sets, per_param, sv.k, sv.r, bs, mn,
+                                       cbar, set_share, scale, mp, unit_start, fill, bp, op);
                 else
-                    hipLaunchKernelGGL((k_merge_reconstruct<F16, NS, RPL>), dim3(pl->n_units), dim3(64), lds, st,
-                                       pl->d_params, pl->d_units, rows_dev, pl->n_tasks, n_sets, per_param, kk, rr, bs, mn,
-                                       cbar, set_share, scale, bp, op);
+                    hipLaunchKernelGGL((k_merge_reconstruct<F16, NS, RPL>), dim3(pl->n_units), dim3(64),
+                                       Plain::bytes(n, NS, NS), st, pl->d_params, pl->d_units, rows_dev, n, n_sets,
+                                       per_param, sv.k, sv.r, bs, mn, cbar, set_share, scale, bp, op);
                 return true;
             });
         });
@@ -1461,67 +1220,18 @@ extern "C" int64_t svdq_task_reconstruct_work_bytes(const svdq_plan *pl, int32_t
     return svdq_align_up((int64_t)pl->n_params * n_out * pl->n_tasks * 4, 256);      // the tasks' coefficients
 }
 
-extern "C" int svdq_task_reconstruct(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
-                                     const float *mean, const int32_t *task, int32_t n_out, const float *scale,
-                                     const void *base_ptrs, const void *out_ptrs, void *work, void *stream) {
-    const char *who = "svdq_task_reconstruct";
+// behind svdq_task_reconstruct (masked == false) and svdq_task_reconstruct_masked (source walk: mask_ptrs, unit_start
+// and rows_dev are required)
+static int launch_task_reconstruct(const char *who, bool masked, const svdq_plan *pl, const int64_t *rows_dev,
+                                   const void *small, const void *basis, const float *mean, const int32_t *task,
+                                   int32_t n_out, const float *scale, const void *mask_ptrs, const int64_t *unit_start,
+                                   const int32_t *fill, const void *base_ptrs, const void *out_ptrs, void *work,
+                                   void *stream) {
     if (!pl || !small || !basis || !task || !out_ptrs || !work) {
         svdq_set_error("%s: plan, small, basis, task, out_ptrs and work are required", who);
         return SVDQ_EINVAL;
     }
-    if (n_out < 1 || n_out > SVDQ_MAX_TASKS) {
-        svdq_set_error("%s: n_out must be in [1, %d], got %d", who, SVDQ_MAX_TASKS, n_out);
-        return SVDQ_EINVAL;
-    }
-    if (pl->cfg.center && !mean) {
-        svdq_set_error("%s: mean is required on a centred plan", who);
-        return SVDQ_EINVAL;
-    }
-    const int n = pl->n_tasks;
-    hipStream_t st = (hipStream_t)stream;
-    float *cbar = reinterpret_cast<float *>(work);
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
-    hipLaunchKernelGGL(k_task_coeff, dim3(pl->n_params), dim3(64), 0, st, n, pl->cfg.rtvq_stages, (int)n_out, task, kk, rr,
-                       reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
-                       reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off),
-                       cbar);
-    auto bp = reinterpret_cast<const float *const *>(base_ptrs);
-    auto op = reinterpret_cast<float *const *>(out_ptrs);
-    const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
-    const float *mn = pl->cfg.center ? mean : nullptr;
-    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
-    const int rpl = n <= 16 ? 4 : 2;                           // rows per lane and block, as launch_reconstruct
-    const int nop = (n_out + tg - 1) / tg * tg;
-    const size_t lds = (size_t)svdq_align_up((int64_t)64 * rpl * n * (pl->cfg.fp16 ? 2 : 4) + 48, 16) + (size_t)nop * n * 4;
-    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
-        constexpr bool F16 = f16_c;
-        return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
-            constexpr int TG = tg_c;
-            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
-                constexpr int RPL = rpl_c;
-                hipLaunchKernelGGL((k_task_reconstruct<F16, TG, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
-                                   pl->d_units, rows_dev, n, (int)n_out, task, kk, rr, bs, mn, cbar, scale, bp, op);
-                return true;
-            });
-        });
-    });
-    return svdq_launch_status(ok, who);
-}
-
-// ---- the same for masked regions: the tasks' coefficients (k_task_coeff) + one source-walk launch
-extern "C" int svdq_task_reconstruct_masked(const svdq_plan *pl, const int64_t *rows_dev, const void *small,
-                                            const void *basis, const float *mean, const int32_t *task, int32_t n_out,
-                                            const float *scale, const void *mask_ptrs, const int64_t *unit_start,
-                                            const int32_t *fill, const void *base_ptrs, const void *out_ptrs, void *work,
-                                            void *stream) {
-    const char *who = "svdq_task_reconstruct_masked";
-    if (!pl || !small || !basis || !task || !out_ptrs || !work) {
-        svdq_set_error("%s: plan, small, basis, task, out_ptrs and work are required", who);
-        return SVDQ_EINVAL;
-    }
-    if (!mask_ptrs || !unit_start || !rows_dev) {
+    if (masked && (!mask_ptrs || !unit_start || !rows_dev)) {
         svdq_set_error("%s: mask_ptrs, unit_start and rows_dev are required", who);
         return SVDQ_EINVAL;
     }
@@ -1536,32 +1246,31 @@ extern "C" int svdq_task_reconstruct_masked(const svdq_plan *pl, const int64_t *
     const int n = pl->n_tasks;
     hipStream_t st = (hipStream_t)stream;
     float *cbar = reinterpret_cast<float *>(work);
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
-    hipLaunchKernelGGL(k_task_coeff, dim3(pl->n_params), dim3(64), 0, st, n, pl->cfg.rtvq_stages, (int)n_out, task, kk, rr,
-                       reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
-                       reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off),
-                       cbar);
+    launch_task_coeff(pl, small, task, (int)n_out, cbar, st);
+    const SmallView sv = small_view(pl, small);
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
     const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
     const float *mn = pl->cfg.center ? mean : nullptr;
-    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a chunk's LDS image
-    const int rpl = n <= 16 ? 4 : 2;                           // source rows per lane and chunk, as launch_reconstruct
+    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
     const int nop = (n_out + tg - 1) / tg * tg;
-    const size_t lds = (size_t)svdq_align_up((int64_t)64 * rpl * n * (pl->cfg.fp16 ? 2 : 4) + 48, 16) +
-                       (size_t)64 * rpl * 4 + (size_t)nop * n * 4;
     const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
         constexpr bool F16 = f16_c;
         return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
             constexpr int TG = tg_c;
-            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
+            return svdq_dispatch_int<4, 2>(stream_rpl(pl), [&](auto rpl_c) {
                 constexpr int RPL = rpl_c;
-                hipLaunchKernelGGL((k_task_expand<F16, TG, RPL>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params,
-                                   pl->d_units, rows_dev, n, (int)n_out, task, kk, rr, bs, mn, cbar, scale, mp, unit_start,
-                                   fill, bp, op);
+                using Walk = StreamLds<F16, RPL, true>;
+                using Plain = StreamLds<F16, RPL, false>;
+                if (masked)
+                    hipLaunchKernelGGL((k_task_expand<F16, TG, RPL>), dim3(pl->n_units), dim3(64), Walk::bytes(n, nop, 0),
+                                       st, pl->d_params, pl->d_units, rows_dev, n, (int)n_out, task, sv.k, sv.r, bs, mn,
+                                       cbar, scale, mp, unit_start, fill, bp, op);
+                else
+                    hipLaunchKernelGGL((k_task_reconstruct<F16, TG, RPL>), dim3(pl->n_units), dim3(64),
+                                       Plain::bytes(n, nop, 0), st, pl->d_params, pl->d_units, rows_dev, n, (int)n_out, task,
+                                       sv.k, sv.r, bs, mn, cbar, scale, bp, op);
                 return true;
             });
         });
@@ -1569,17 +1278,28 @@ extern "C" int svdq_task_reconstruct_masked(const svdq_plan *pl, const int64_t *
     return svdq_launch_status(ok, who);
 }
 
+extern "C" int svdq_task_reconstruct(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
+                                     const float *mean, const int32_t *task, int32_t n_out, const float *scale,
+                                     const void *base_ptrs, const void *out_ptrs, void *work, void *stream) {
+    return launch_task_reconstruct("svdq_task_reconstruct", false, pl, rows_dev, small, basis, mean, task, n_out, scale,
+                                   nullptr, nullptr, nullptr, base_ptrs, out_ptrs, work, stream);
+}
+
+// ---- the same for masked regions: the tasks' coefficients (k_task_coeff) + one source-walk launch
+extern "C" int svdq_task_reconstruct_masked(const svdq_plan *pl, const int64_t *rows_dev, const void *small,
+                                            const void *basis, const float *mean, const int32_t *task, int32_t n_out,
+                                            const float *scale, const void *mask_ptrs, const int64_t *unit_start,
+                                            const int32_t *fill, const void *base_ptrs, const void *out_ptrs, void *work,
+                                            void *stream) {
+    return launch_task_reconstruct("svdq_task_reconstruct_masked", true, pl, rows_dev, small, basis, mean, task, n_out,
+                                   scale, mask_ptrs, unit_start, fill, base_ptrs, out_ptrs, work, stream);
+}
+
 extern "C" int64_t svdq_diagnostics_work_bytes(const svdq_plan *pl) {
     if (!pl) return 0;
     const int64_t n = pl->n_tasks;
     return svdq_align_up((int64_t)pl->n_params * n * n * 4, 256) +              // per-task coefficients
-           svdq_align_up(n * n * 4, 256) +                                      // one-hot weights [N][N]
            svdq_align_up((int64_t)pl->n_units * n * (int64_t)sizeof(DiagPart), 256);
-}
-
-__global__ void k_one_hot(int n, float *w) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n * n) w[e] = (e / n == e % n) ? 1.f : -1.f;
 }
 
 #ifndef SVDQ_DIAG_RPL_MID
@@ -1596,15 +1316,11 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
     hipStream_t st = (hipStream_t)stream;
     uint8_t *wb = reinterpret_cast<uint8_t *>(work);
     float *ctask = reinterpret_cast<float *>(wb);
-    float *onehot = reinterpret_cast<float *>(wb + svdq_align_up((int64_t)pl->n_params * n * n * 4, 256));
-    DiagPart *part = reinterpret_cast<DiagPart *>(wb + svdq_align_up((int64_t)pl->n_params * n * n * 4, 256) +
-                                                  svdq_align_up(n * n * 4, 256));
-    // per-task coefficients = the "average" of one task with weight 1: sets = tasks, one-hot weights
-    hipLaunchKernelGGL(k_one_hot, dim3(((int)(n * n) + 255) / 256), dim3(256), 0, st, (int)n, onehot);
-    if (int rc = svdq_merge_coeffs(pl, small, onehot, nullptr, (int32_t)n, 0, ctask, stream)) return rc;
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    DiagPart *part = reinterpret_cast<DiagPart *>(wb + svdq_align_up((int64_t)pl->n_params * n * n * 4, 256));
+    // every task's own coefficients: what k_merge_coeff gives for the one-hot sets, without a weight table
+    launch_task_coeff(pl, small, nullptr, (int)n, ctask, st);
+    if (hipGetLastError() != hipSuccess) return SVDQ_EHIP;
+    const SmallView sv = small_view(pl, small);
     auto bs = reinterpret_cast<const uint8_t *>(basis);
     auto pp = reinterpret_cast<const float *const *>(delta_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
@@ -1616,7 +1332,7 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
         constexpr int RPL = NTP <= 8 ? 4 : (NTP <= 24 ? SVDQ_DIAG_RPL_MID : 1);   // rows per lane and block
         constexpr int SETS = NTP == 4 ? 4 : (NTP == 8 ? 2 : 1);                   // row sets packed into one tile
         using G = DiagGeom<NTP, RPL, SETS>;
-        const size_t lds = (size_t)svdq_align_up((int64_t)G::RB * n * (pl->cfg.fp16 ? 2 : 4) + 48, 16) +
+        const size_t lds = (size_t)stream_ubytes(G::RB, (int)n, pl->cfg.fp16 ? 2 : 4) +
                            (size_t)(NTP + 1) * diag_xs(G::RB, mp != nullptr) * 4;
         return svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
             using TIN = typename decltype(tin_c)::type;
@@ -1630,8 +1346,8 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
                         if constexpr (WALK && !CAN_WALK) return false;
                         else {
                             hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK, TIN>), dim3(pl->n_units), dim3(64),
-                                               lds, st, pl->d_params, pl->d_units, pp, mp, unit_start, rows_dev, (int)n, kk,
-                                               rr, bs, mean, add_mean, ctask, part);
+                                               lds, st, pl->d_params, pl->d_units, pp, mp, unit_start, rows_dev, (int)n, sv.k,
+                                               sv.r, bs, mean, add_mean, ctask, part);
                             return true;
                         }
                     });

@@ -466,8 +466,53 @@ def test_edited_dictionaries_leave_the_batched_route(sq):
     assert set(diag["per_parameter"]) == set(shapes)
 
 
+@pytest.mark.parametrize("n_tasks,fp16,n_sets", [(8, True, 1), (8, False, 8), (12, False, 2), (16, True, 4), (20, True, 8),
+                                                  (20, False, 4), (32, True, 2)])
+def test_plain_merge_variants_are_the_per_parameter_route(sq, n_tasks, fp16, n_sets):
+    """svdq_merge (k_merge_coeff + k_merge_reconstruct) at every compiled set count (1, 2, 4, 8), both block sizes (256
+    rows up to 16 tasks, 128 above) and both basis types, against code outside svdq_merge.hip: every set is ONE task with
+    weight 1.0, so its coefficients are that task's own and its rows are merge_parameter's for a one-task dictionary
+    (RTVQQuantizer.dequantize + reconstruct_from_coefficients: k_reconstruct of svdq_elem.hip); the sets are then
+    combined with their shares and added to the base by torch, elementwise in fp32, in the kernel's order -- bit for bit."""
+    from oracle import svd_hybrid_oracle as orc
+    from svdq_amd.pipeline import CompressPlan, task_artifact
+    dev = torch.device("cuda", 0)
+    sizes = [9000, 300, 4096 * 3 + 5, 61]      # several blocks, less than one, a ragged end, less than a wavefront
+    gen = torch.Generator().manual_seed(300 + n_tasks)
+    vecs = [[d.to(dev) for d in orc.synthetic_deltas(D, n_tasks, 700 + i, rank=3)] for i, D in enumerate(sizes)]
+    plan = CompressPlan(sizes, n_tasks, energy_threshold=0.9, max_rank=None, center=True, fp16=fp16, low_bits=4,
+                        rtvq_stages=2, device=dev)
+    plan.run(plan.pointer_table(vecs))
+    sm = plan.fetch_small()
+    w = torch.full((n_sets, n_tasks), -1.0)
+    for s in range(n_sets):
+        w[s, s] = 1.0                            # set s = {task s: 1.0}
+    w = w.to(dev)
+    share = torch.softmax(torch.arange(n_sets, dtype=torch.float32), 0).to(dev) if n_sets > 1 else None
+    base = [torch.randn(D, generator=gen).to(dev) for D in sizes]
+    btab = torch.tensor([b.data_ptr() for b in base], dtype=torch.int64).to(dev)
+    cbuf, coffs, ctab = plan.new_merged_outputs()
+    plan.merge(w, set_share=share, base_table=btab, out_table=ctab)
+    torch.cuda.synchronize()
+    quant = sq.RTVQQuantizer(4, 2)
+    for p, D in enumerate(sizes):
+        k, r = int(sm.k[p]), int(sm.r[p])
+        U_high, U_low, mean = plan.basis_tensors(p, k, r, D)
+        basis = {"masked": {"U_high": U_high, "U_low": U_low, "mean": mean}}
+        v = [sq.merge_parameter(f"p{p}", {"t": {"masked": task_artifact(plan, sm, p, s)}}, basis, {"t": 1.0}, quant,
+                                torch.Size([D]), device="cuda") for s in range(n_sets)]
+        if share is None:
+            res = v[0]
+        else:
+            res = torch.zeros(D, device=dev)
+            for s in range(n_sets):
+                res = res + v[s] * share[s]      # (stack * w).sum(0), set by set
+        assert _same_bits(cbuf[coffs[p]:coffs[p] + D], base[p] + res), (p, D)
+    plan.close()
+
+
 @pytest.mark.parametrize("n_tasks,fp16,inverted,n_sets", [(8, True, False, 1), (12, False, True, 2), (20, True, False, 2),
-                                                          (20, False, True, 1), (32, True, False, 4)])
+                                                          (20, False, True, 1), (32, True, False, 4), (20, True, True, 8)])
 def test_plan_merge_masked_at_every_block_size(sq, n_tasks, fp16, inverted, n_sets):
     """svdq_merge_masked (k_merge_expand: 256-row chunks up to 16 tasks, 128-row chunks above -- round 3 stopped at 16) against
     merging in the compacted row space (svdq_merge) and torch's own boolean assignment: bit for bit, + base, both
