@@ -589,6 +589,32 @@ int svdq_diagnostics_masked(const svdq_plan *plan, const void *delta_ptrs_dev, c
                             const void *basis_dev, const float *mean_dev, int32_t add_mean, double *out_dev,
                             void *work_dev, void *stream);
 
+/* ---- the diagnostics straight from checkpoints (the one statement of the contract; the sources point here): what the
+ *      reference does with compute_task_vector (task_vector_loader.py:103-141: delta = finetuned - base, per parameter)
+ *      followed by the per-task loop of compute_parameter_diagnostics (diagnostics.py:186-215), without the N task
+ *      vectors ever existing in memory.  finetuned_ptrs_dev [P*N] names the FINE-TUNED tensors (parameter-major, as
+ *      delta_ptrs_dev of svdq_diagnostics), base_ptrs_dev [P] the base model's; inside the one pass over U every block's
+ *      base row is loaded once beside its N task rows, widened to fp32 as they are, and each element becomes
+ *      x = finetuned - base, a single fp32 subtraction; everything after it is svdq_diagnostics' own code.
+ *   The contract on bits: out_dev is bit for bit what svdq_diagnostics gives on fp32 tensors holding
+ *     (float)finetuned - (float)base; svdq_diagnostics_masked_from_base is bit for bit svdq_diagnostics_masked on such
+ *     tensors.
+ *   Element type: the plan's input type (svdq_plan_set_input_type) governs the fine-tuned and the base tensors alike,
+ *     with the alignment of svdq_compress_from_base (16 bytes for fp32, 8 for fp16 / bf16).  The masked form reads fp32
+ *     only (SVDQ_EUNSUPPORTED on a half plan, as svdq_diagnostics_masked).  Any N <= SVDQ_MAX_TASKS, masked form included.
+ *   A NULL base_ptrs_dev is SVDQ_EINVAL before anything is launched; the masked form also requires mask_ptrs_dev,
+ *     unit_start_dev and rows_dev, as svdq_diagnostics_masked.  work_dev: svdq_diagnostics_work_bytes(plan).
+ *   Allocates nothing, copies nothing to the host, synchronises nothing: capturable like every other entry point.
+ *   Works on plans filled by any compress route and on plans filled by svdq_plan_import. */
+int svdq_diagnostics_from_base(const svdq_plan *plan, const void *finetuned_ptrs_dev /*[P*N]*/,
+                               const void *base_ptrs_dev /*[P]*/, const int64_t *rows_dev, const void *small_dev,
+                               const void *basis_dev, const float *mean_dev, int32_t add_mean, double *out_dev,
+                               void *work_dev, void *stream);
+int svdq_diagnostics_masked_from_base(const svdq_plan *plan, const void *finetuned_ptrs_dev, const void *base_ptrs_dev,
+                                      const void *mask_ptrs_dev, const int64_t *unit_start_dev, const int64_t *rows_dev,
+                                      const void *small_dev, const void *basis_dev, const float *mean_dev,
+                                      int32_t add_mean, double *out_dev, void *work_dev, void *stream);
+
 /* ---- adopt STORED artifacts into a plan (the one statement of the contract; the sources point here).  The reference
  *      writes its artifacts one file per parameter (save_basis / save_compressed_coefficients storage.py:52-174) and merges
  *      them again later, with other weights or another base model (load_all_artifacts storage.py:341-389 ->

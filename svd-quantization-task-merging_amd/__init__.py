@@ -30,7 +30,7 @@ from .clustering import (cluster_tasks, task_gram, cluster_from_gram, cluster_st
                          get_cluster_members, compute_cluster_statistics, merge_by_cluster, merge_cluster_results,
                          compute_kmeans_clustering, compute_hierarchical_clustering)
 from .diagnostics import (compute_reconstruction_error, compute_parameter_diagnostics, compute_all_diagnostics,
-                          compute_compression_statistics, print_detailed_compression_report,
+                          compute_all_diagnostics_from_checkpoints, compute_compression_statistics, print_detailed_compression_report,
                           print_diagnostics_summary, compute_coefficient_histograms)
 from .storage import (save_basis, load_basis, save_compressed_coefficients, load_compressed_coefficients,
                       save_diagnostics, load_diagnostics, save_config, load_config, save_all_artifacts,

@@ -11,7 +11,8 @@ HIP entry points of this package:
   Step 6  compute_weights / cluster_tasks   N x N task Gram: a by-product of Step 4's first pass (svdq_plan_task_gram);
                                       masked parameters add one pass over their unmasked deltas (svdq_task_gram)
   Step 7  merge_all_parameters / merge_with_clustering, apply_merged_deltas (svdq_reconstruct, svdq_mask_expand)
-  Step 8  compute_all_diagnostics     fused reconstruction error (svdq_recon_error)
+  Step 8  compute_all_diagnostics     fused reconstruction error (svdq_recon_error); with --eval-from-checkpoints
+                                      compute_all_diagnostics_from_checkpoints (svdq_diagnostics_from_base)
 
 There is no CPU path: without a GPU the driver raises (the reference silently falls back to "cpu", cli.py:135).
 """
@@ -26,8 +27,8 @@ import torch
 
 from .clustering import cluster_tasks, get_cluster_members
 from .config import SVDHybridConfig
-from .diagnostics import (compute_all_diagnostics, compute_compression_statistics, print_detailed_compression_report,
-                          print_diagnostics_summary)
+from .diagnostics import (compute_all_diagnostics, compute_all_diagnostics_from_checkpoints,
+                          compute_compression_statistics, print_detailed_compression_report, print_diagnostics_summary)
 from .driver import run_basis_and_compress, run_basis_and_compress_from_checkpoints
 from .mask_loader import combine_masks, combine_tall_masks_packed, load_task_masks
 from .merge import apply_merged_deltas, merge_all_parameters, merge_with_clustering
@@ -48,8 +49,10 @@ def _find_tall_mask_file(mask_dir: str, n_tasks: int):
     return None
 
 
-def run_svd_hybrid_pipeline(config: SVDHybridConfig) -> Dict:
-    """cli.py:73-778.  Returns {"merged_state_dict", "diagnostics", "bases", "compressed"}."""
+def run_svd_hybrid_pipeline(config: SVDHybridConfig, eval_from_checkpoints: bool = False) -> Dict:
+    """cli.py:73-778.  Returns {"merged_state_dict", "diagnostics", "bases", "compressed"}.  ``eval_from_checkpoints``:
+    a run with reconstruction diagnostics takes the from-checkpoints route too (no task vectors are formed; Step 8
+    measures against finetuned - base inside its pass)."""
     device = str(resolve_device(config.device))
     print(f"[1/8] loading base model and {len(config.tasks)} task checkpoints")
     base_state_dict = load_checkpoint(config.base_model_path, device="cpu")
@@ -60,7 +63,9 @@ def run_svd_hybrid_pipeline(config: SVDHybridConfig) -> Dict:
     # svdq_compress_gather_from_base) and the deltas are never materialised.  Clustering takes the task Gram the
     # compressor's first pass leaves behind; only masked parameters are not in it (the reference clusters on their
     # unmasked vectors), so a cluster-weighted run with masks still forms the task vectors.
-    from_checkpoints = not config.svd_eval_reconstruction and (config.svd_weighting != "cluster" or not has_masks)
+    # With ``eval_from_checkpoints`` the diagnostics need no task vectors either (svdq_diagnostics_from_base).
+    from_checkpoints = ((not config.svd_eval_reconstruction or eval_from_checkpoints)
+                        and (config.svd_weighting != "cluster" or not has_masks))
     if from_checkpoints:
         float_base = {k: v for k, v in base_state_dict.items() if isinstance(v, torch.Tensor) and v.is_floating_point()}
         task_vectors = {}
@@ -128,7 +133,12 @@ def run_svd_hybrid_pipeline(config: SVDHybridConfig) -> Dict:
 
     if config.svd_eval_reconstruction:
         print("[8/8] diagnostics")
-        diagnostics = compute_all_diagnostics(task_vectors, compressed_all, bases, combined_masks, config, device=device)
+        if from_checkpoints:      # task_vectors holds the fine-tuned weights
+            diagnostics = compute_all_diagnostics_from_checkpoints(float_base, task_vectors, compressed_all, bases,
+                                                                   combined_masks, config, device=device)
+        else:
+            diagnostics = compute_all_diagnostics(task_vectors, compressed_all, bases, combined_masks, config,
+                                                  device=device)
         diagnostics["task_weights"] = weights
         if cluster_assignments:
             diagnostics["cluster_assignments"] = cluster_assignments
@@ -191,6 +201,8 @@ def parse_args(argv=None):
     p.add_argument("--eval-reconstruction", action="store_true", default=True, help="Evaluate reconstruction error")
     p.add_argument("--no-eval-reconstruction", action="store_false", dest="eval_reconstruction",
                    help="Skip reconstruction evaluation")
+    p.add_argument("--eval-from-checkpoints", action="store_true",
+                   help="Evaluate reconstruction against finetuned - base formed on the GPU (no task vectors in memory)")
     p.add_argument("--output-dir", type=str, default="./svd_hybrid_output", help="Output directory for merged model")
     p.add_argument("--artifact-dir", type=str, default="./artifacts", help="Directory for artifact storage")
     p.add_argument("--device", type=str, default="cuda", help="Device to use")
@@ -230,7 +242,7 @@ def main(argv=None):
         svd_cluster_k=args.cluster_k, svd_store_artifacts=args.store_artifacts,
         svd_eval_reconstruction=args.eval_reconstruction, output_dir=args.output_dir, artifact_dir=args.artifact_dir,
         device=args.device)
-    return run_svd_hybrid_pipeline(config)
+    return run_svd_hybrid_pipeline(config, eval_from_checkpoints=args.eval_from_checkpoints)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,8 @@
 //                        the MASKED regions, written at their source positions (+ base) in the same pass.
 //   k_diag / k_diag_finish  compute_parameter_diagnostics' inner loop (diagnostics.py:186-215) for all N tasks of a
 //                        parameter in one pass over U and the N deltas: N error tuples per parameter; walk mode =
-//                        masked regions, apply_mask_to_tensor (mask_loader.py:651-679) inside the pass.
+//                        masked regions, apply_mask_to_tensor (mask_loader.py:651-679) inside the pass; minus-base mode =
+//                        fine-tuned and base tensors in, compute_task_vector (task_vector_loader.py:103-141) in registers.
 //
 // Per-row arithmetic is that of k_reconstruct / k_recon_error (svdq_elem.hip): fp32 fma chains from 0 over the columns
 // in order, hi + lo, + mean, * scale -- so a parameter's merged rows are the same bits as the per-parameter route's
@@ -679,7 +680,12 @@ template <bool B> struct DiagBool { static constexpr bool value = B; };
 #define SVDQ_DIAG_ATTR
 #endif
 // TIN: element type of the task tensors (svdq_input.h), widened to fp32 by the loads; float for the walk.
-template <int NTP, int RPL_, int SETS, bool FULL, bool U16, bool WALK, typename TIN = float>
+// FB: minus-base mode (svdq_diagnostics_from_base).  The task tensors are FINE-TUNED weights and base_ptrs [P] names
+// the base tensors, of the same element type: a block's base row rides in the prefetch registers beside the task rows
+// (same lane -> row map, same widening) and x = finetuned - base, one fp32 subtraction, is formed where the registers
+// are consumed, so the next block's loads stay in flight during the compute phase.  A compile-time flag: the existing
+// instantiations keep their registers (the 17..32-task variants have none to spare).
+template <int NTP, int RPL_, int SETS, bool FULL, bool U16, bool WALK, typename TIN = float, bool FB = false>
 __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__restrict__ params, const SvdqUnit *__restrict__ units,
                                              const float *const *__restrict__ ptrs,
                                              const uint8_t *const *__restrict__ mask_ptrs,
@@ -687,7 +693,8 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                                              int NT, const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
                                              const uint8_t *__restrict__ basis, const float *__restrict__ meanbuf,
                                              int add_mean, const float *__restrict__ ctask /* [P][N][N] */,
-                                             DiagPart *__restrict__ part /* [n_units][N] */) {
+                                             DiagPart *__restrict__ part /* [n_units][N] */,
+                                             const float *const *__restrict__ base_ptrs /* [P], FB only */) {
     using T = typename UElem<U16>::type;
     using G = DiagGeom<NTP, RPL_, SETS>;
     static_assert(SETS == 1 || (RPL_ == 4 && NTP * SETS <= 16), "packed row sets: 16 / SETS tasks each, 256-row blocks");
@@ -759,6 +766,8 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
         gin<TIN> *dp[NTP];
 #pragma unroll
         for (int t = 0; t < NTP; ++t) dp[t] = (gin<TIN> *)ptrs[(size_t)p * n + (t < n ? t : 0)];
+        gin<TIN> *bp = nullptr;
+        if constexpr (FB) bp = (gin<TIN> *)base_ptrs[p];
         int64_t src = cpos, src_hi = cend;      // plain: source rows = compacted rows
         int inv = 0;
         if constexpr (WALK) {
@@ -768,7 +777,7 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
             inv = rg.inv;
         }
         // ---- the loads of one block into registers
-        float xpf[NTP][RPL] = {}, mpf[RPL] = {};
+        float xpf[NTP][RPL] = {}, mpf[RPL] = {}, bpf[RPL] = {};
         unsigned mkpf[RPL] = {};
         f32x4 ureg[SV];
         auto prefetch = [&](int64_t s0, int64_t c0) {
@@ -777,6 +786,10 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                 if (s0 + RB <= src_hi) {
 #pragma unroll
                     for (int e = 0; e < RPL; ++e) mkpf[e] = (unsigned)gmask[r0 + 64 * e];
+                    if constexpr (FB) {
+#pragma unroll
+                        for (int e = 0; e < RPL; ++e) bpf[e] = in_load1<TIN>(bp + (r0 + 64 * e));
+                    }
 #pragma unroll
                     for (int t = 0; t < NTP; ++t)
                         if (t < n) {      // wave-uniform
@@ -789,6 +802,7 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                     for (int e = 0; e < RPL; ++e) {
                         in[e] = r0 + 64 * e < src_hi;
                         mkpf[e] = in[e] ? (unsigned)gmask[r0 + 64 * e] : 0x100u;
+                        if constexpr (FB) bpf[e] = in[e] ? in_load1<TIN>(bp + (r0 + 64 * e)) : 0.f;
                     }
 #pragma unroll
                     for (int t = 0; t < NTP; ++t)
@@ -800,6 +814,17 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
             } else {                   // lane l owns rows s0 + RPL l .. + RPL - 1: one vector load per task
                 const int64_t r0 = s0 + RPL * lane;
                 if (s0 + RB <= src_hi) {
+                    if constexpr (FB) {
+                        if constexpr (RPL == 4) {
+                            const f32x4 v = in_load4<TIN>(bp + r0);
+                            bpf[0] = v.x, bpf[1] = v.y, bpf[2] = v.z, bpf[3] = v.w;
+                        } else if constexpr (RPL == 2) {
+                            const f32x2 v = in_load2<TIN>(bp + r0);
+                            bpf[0] = v.x, bpf[1] = v.y;
+                        } else {
+                            bpf[0] = in_load1<TIN>(bp + r0);
+                        }
+                    }
 #pragma unroll
                     for (int t = 0; t < NTP; ++t)
                         if (t < n) {
@@ -814,6 +839,10 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
                             }
                         }
                 } else {
+                    if constexpr (FB) {
+#pragma unroll
+                        for (int e = 0; e < RPL; ++e) bpf[e] = (r0 + e < src_hi) ? in_load1<TIN>(bp + (r0 + e)) : 0.f;
+                    }
 #pragma unroll
                     for (int t = 0; t < NTP; ++t)
                         if (t < n) {
@@ -864,19 +893,24 @@ __global__ __launch_bounds__(64) SVDQ_DIAG_ATTR void k_diag(const SvdqParam *__r
 #pragma unroll
                 for (int e = 0; e < RPL; ++e) X[NTP * XSD + 64 * e + lane] = mpf[e];
             }
+            // FB: finetuned - base where the prefetched registers are consumed (rows past the end: 0 - 0)
+            auto xv = [&](int t, int e) -> float {
+                if constexpr (FB) return __fsub_rn(xpf[t][e], bpf[e]);
+                else return xpf[t][e];
+            };
 #pragma unroll
             for (int t = 0; t < NTP; ++t) {      // strips past the plan's tasks hold don't-cares (their C is zero)
                 if constexpr (WALK) {
 #pragma unroll
-                    for (int e = 0; e < RPL; ++e) X[t * XSD + slot[e]] = xpf[t][e];
+                    for (int e = 0; e < RPL; ++e) X[t * XSD + slot[e]] = xv(t, e);
                 } else if constexpr (RPL == 4) {
-                    f32x4 v = {xpf[t][0], xpf[t][1], xpf[t][2], xpf[t][3]};
+                    f32x4 v = {xv(t, 0), xv(t, 1), xv(t, 2), xv(t, 3)};
                     *reinterpret_cast<f32x4 *>(X + t * XSD + 4 * lane) = v;
                 } else if constexpr (RPL == 2) {
-                    f32x2 v = {xpf[t][0], xpf[t][1]};
+                    f32x2 v = {xv(t, 0), xv(t, 1)};
                     *reinterpret_cast<f32x2 *>(X + t * XSD + 2 * lane) = v;
                 } else {
-                    X[t * XSD + lane] = xpf[t][0];
+                    X[t * XSD + lane] = xv(t, 0);
                 }
             }
             lds_fence();
@@ -1305,9 +1339,11 @@ extern "C" int64_t svdq_diagnostics_work_bytes(const svdq_plan *pl) {
 #ifndef SVDQ_DIAG_RPL_MID
 #define SVDQ_DIAG_RPL_MID 2      // rows per lane and block of the 9..24-task variants (A/B builds)
 #endif
-static int run_diagnostics(const char *who, const svdq_plan *pl, const void *delta_ptrs, const void *mask_ptrs,
-                           const int64_t *unit_start, const int64_t *rows_dev, const void *small, const void *basis,
-                           const float *mean, int32_t add_mean, double *out, void *work, void *stream) {
+// base_ptrs: NULL, or the [P] base tensors of the minus-base mode (delta_ptrs then names the fine-tuned tensors)
+static int run_diagnostics(const char *who, const svdq_plan *pl, const void *delta_ptrs, const void *base_ptrs,
+                           const void *mask_ptrs, const int64_t *unit_start, const int64_t *rows_dev, const void *small,
+                           const void *basis, const float *mean, int32_t add_mean, double *out, void *work,
+                           void *stream) {
     if (!pl || !delta_ptrs || !small || !basis || !out || !work) {
         svdq_set_error("%s: bad argument", who);
         return SVDQ_EINVAL;
@@ -1324,6 +1360,7 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
     auto bs = reinterpret_cast<const uint8_t *>(basis);
     auto pp = reinterpret_cast<const float *const *>(delta_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
+    auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     // variants by padded task count (the prefetch registers and the X strips are sized by it), each also for plans with
     // exactly that many tasks (FULL); the walk over the masks (WALK) reads fp32 tensors only, which
     // svdq_diagnostics_masked has checked
@@ -1345,10 +1382,13 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
                         constexpr bool WALK = walk_c;
                         if constexpr (WALK && !CAN_WALK) return false;
                         else {
-                            hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK, TIN>), dim3(pl->n_units), dim3(64),
-                                               lds, st, pl->d_params, pl->d_units, pp, mp, unit_start, rows_dev, (int)n, sv.k,
-                                               sv.r, bs, mean, add_mean, ctask, part);
-                            return true;
+                            return svdq_dispatch_bool(bp != nullptr, [&](auto fb_c) {
+                                constexpr bool FB = fb_c;
+                                hipLaunchKernelGGL((k_diag<NTP, RPL, SETS, FULL, F16, WALK, TIN, FB>), dim3(pl->n_units),
+                                                   dim3(64), lds, st, pl->d_params, pl->d_units, pp, mp, unit_start,
+                                                   rows_dev, (int)n, sv.k, sv.r, bs, mean, add_mean, ctask, part, bp);
+                                return true;
+                            });
                         }
                     });
                 });
@@ -1363,8 +1403,20 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
 extern "C" int svdq_diagnostics(const svdq_plan *pl, const void *delta_ptrs, const int64_t *rows_dev, const void *small,
                                 const void *basis, const float *mean, int32_t add_mean, double *out, void *work,
                                 void *stream) {
-    return run_diagnostics("svdq_diagnostics", pl, delta_ptrs, nullptr, nullptr, rows_dev, small, basis, mean, add_mean,
-                           out, work, stream);
+    return run_diagnostics("svdq_diagnostics", pl, delta_ptrs, nullptr, nullptr, nullptr, rows_dev, small, basis, mean,
+                           add_mean, out, work, stream);
+}
+
+// ---- the same straight from checkpoints (include/svdq.h): k_diag's minus-base mode
+extern "C" int svdq_diagnostics_from_base(const svdq_plan *pl, const void *finetuned_ptrs, const void *base_ptrs,
+                                          const int64_t *rows_dev, const void *small, const void *basis,
+                                          const float *mean, int32_t add_mean, double *out, void *work, void *stream) {
+    if (!base_ptrs) {
+        svdq_set_error("svdq_diagnostics_from_base: base_ptrs is required");
+        return SVDQ_EINVAL;
+    }
+    return run_diagnostics("svdq_diagnostics_from_base", pl, finetuned_ptrs, base_ptrs, nullptr, nullptr, rows_dev, small,
+                           basis, mean, add_mean, out, work, stream);
 }
 
 extern "C" int svdq_diagnostics_masked(const svdq_plan *pl, const void *delta_ptrs, const void *mask_ptrs,
@@ -1377,6 +1429,26 @@ extern "C" int svdq_diagnostics_masked(const svdq_plan *pl, const void *delta_pt
     }
     if (pl)
         if (int rc = svdq_require_f32_input(pl, "svdq_diagnostics_masked")) return rc;
-    return run_diagnostics("svdq_diagnostics_masked", pl, delta_ptrs, mask_ptrs, unit_start, rows_dev, small, basis, mean,
+    return run_diagnostics("svdq_diagnostics_masked", pl, delta_ptrs, nullptr, mask_ptrs, unit_start, rows_dev, small,
+                           basis, mean, add_mean, out, work, stream);
+}
+
+extern "C" int svdq_diagnostics_masked_from_base(const svdq_plan *pl, const void *finetuned_ptrs, const void *base_ptrs,
+                                                 const void *mask_ptrs, const int64_t *unit_start,
+                                                 const int64_t *rows_dev, const void *small, const void *basis,
+                                                 const float *mean, int32_t add_mean, double *out, void *work,
+                                                 void *stream) {
+    const char *who = "svdq_diagnostics_masked_from_base";
+    if (!base_ptrs) {
+        svdq_set_error("%s: base_ptrs is required", who);
+        return SVDQ_EINVAL;
+    }
+    if (!mask_ptrs || !unit_start || !rows_dev) {
+        svdq_set_error("%s: mask_ptrs, unit_start and rows_dev are required", who);
+        return SVDQ_EINVAL;
+    }
+    if (pl)
+        if (int rc = svdq_require_f32_input(pl, who)) return rc;
+    return run_diagnostics(who, pl, finetuned_ptrs, base_ptrs, mask_ptrs, unit_start, rows_dev, small, basis, mean,
                            add_mean, out, work, stream);
 }

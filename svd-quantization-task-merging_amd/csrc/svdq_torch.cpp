@@ -30,10 +30,12 @@
 //       Tensor[] base) -> Tensor[]                             svdq_merge_masked: full-size tensors, mask scatter fused
 //   diagnostics(Tensor[] deltas, Tensor[] masks, Tensor small, Tensor basis, Tensor mean, int n_tasks, <settings>,
 //       bool add_mean) -> Tensor                               float64 [P, n_tasks, 6]; masks empty = unmasked
+//   diagnostics_from_base(Tensor[] finetuned, Tensor[] base, Tensor small, Tensor basis, Tensor mean, int n_tasks,
+//       <settings>, bool add_mean) -> Tensor                   the same from checkpoints (svdq_diagnostics_from_base)
 //   ingest(Tensor base, Tensor[] finetuned) -> Tensor[]
 //   task_gram(Tensor[] deltas, int n_tasks) -> Tensor
 //   plan_cache_size() -> int                                  plans kept by compress (for tests)
-// compress, compress_gather, compress_from_base, diagnostics (unmasked) and task_gram read fp16 / bf16 task tensors as
+// compress, compress_gather, compress_from_base, diagnostics (unmasked), diagnostics_from_base and task_gram read fp16 / bf16 task tensors as
 // they are when every task tensor (and every base tensor) has that one dtype (svdq_plan_set_input_type: the outputs are
 // byte-identical to those of the same call on the tensors converted to fp32); any other mix is converted to fp32 first.
 #include <ATen/ATen.h>
@@ -702,6 +704,46 @@ at::Tensor diagnostics(at::TensorList deltas, at::TensorList masks, const at::Te
     return out;
 }
 
+// svdq_diagnostics_from_base: the unmasked diagnostics against finetuned - base, formed inside the pass (no task vectors)
+at::Tensor diagnostics_from_base(at::TensorList finetuned, at::TensorList base, const at::Tensor &small,
+                                 const at::Tensor &basis, const at::Tensor &mean, int64_t n_tasks, double energy,
+                                 int64_t max_rank, bool center, bool fp16, int64_t bits, int64_t stages, bool add_mean) {
+    const int32_t in_type = input_type_of(finetuned, base);
+    std::vector<at::Tensor> vecs = prep_list(finetuned, n_tasks, "diagnostics_from_base", in_type);
+    const c10::Device dev = vecs[0].device();
+    c10::DeviceGuard guard(dev);
+    void *stream = stream_of(dev);
+    std::vector<int64_t> rows = rows_of(vecs, n_tasks);
+    const int64_t P = (int64_t)rows.size();
+    TORCH_CHECK_VALUE((int64_t)base.size() == P, "diagnostics_from_base: one base tensor per parameter");
+    std::vector<at::Tensor> bs;
+    for (int64_t p = 0; p < P; ++p) {
+        TORCH_CHECK_VALUE(base[p].device() == dev, "diagnostics_from_base: all tensors must live on one device");
+        TORCH_CHECK_VALUE(base[p].numel() == rows[p], "parameter ", p, ": base and fine-tuned tensors differ in size");
+        bs.push_back(prep_in(base[p], in_type));
+    }
+    TORCH_CHECK_VALUE(small.device() == dev && basis.device() == dev,
+                      "diagnostics_from_base: all tensors must live on one device");
+    PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
+    std::lock_guard<std::mutex> lock(g_cache_mu);
+    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    check_artifacts("diagnostics_from_base", small, basis, mean, plan->sizes, center, dev);
+    at::Tensor table = table_of(vecs, dev), btab = table_of(bs, dev);
+    at::Tensor out = at::empty({P, n_tasks, 6}, at::TensorOptions().dtype(at::kDouble).device(dev));
+    at::Tensor work = bytes_on(dev, svdq_diagnostics_work_bytes(plan->h));
+    const float *mn = (center && mean.numel() > 0) ? mean.data_ptr<float>() : nullptr;
+    svdq_small_layout L{};
+    svdq_plan_small_layout(plan->h, &L);
+    const int rc = svdq_diagnostics_from_base(plan->h, table.data_ptr(), btab.data_ptr(),
+                                              reinterpret_cast<const int64_t *>(small.data_ptr<uint8_t>() + L.rows_off),
+                                              small.data_ptr(), basis.data_ptr(), mn, add_mean ? 1 : 0,
+                                              out.data_ptr<double>(), work.data_ptr(), stream);
+    sync(dev);      // the pointer tables die with this scope
+    release_plan(std::move(key), std::move(plan));
+    check(rc, "svdq_diagnostics_from_base");
+    return out;
+}
+
 int64_t plan_cache_size() {
     std::lock_guard<std::mutex> lock(g_cache_mu);
     return (int64_t)g_cache.size();
@@ -890,6 +932,8 @@ TORCH_LIBRARY(svdq, m) {
           "bool center, bool fp16, int bits, int stages, Tensor weights, Tensor[] base) -> Tensor[]");
     m.def("diagnostics(Tensor[] deltas, Tensor[] masks, Tensor small, Tensor basis, Tensor mean, int n_tasks, float energy, "
           "int max_rank, bool center, bool fp16, int bits, int stages, bool add_mean) -> Tensor");
+    m.def("diagnostics_from_base(Tensor[] finetuned, Tensor[] base, Tensor small, Tensor basis, Tensor mean, int n_tasks, "
+          "float energy, int max_rank, bool center, bool fp16, int bits, int stages, bool add_mean) -> Tensor");
     m.def("ingest(Tensor base, Tensor[] finetuned) -> Tensor[]");
     m.def("task_gram(Tensor[] deltas, int n_tasks) -> Tensor");
     m.def("plan_cache_size() -> int", plan_cache_size);
@@ -912,6 +956,7 @@ TORCH_LIBRARY_IMPL(svdq, CUDA, m) {
     m.impl("merge", merge);
     m.impl("merge_masked", merge_masked);
     m.impl("diagnostics", diagnostics);
+    m.impl("diagnostics_from_base", diagnostics_from_base);
     m.impl("ingest", ingest);
     m.impl("task_gram", task_gram);
 }

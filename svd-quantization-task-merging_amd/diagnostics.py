@@ -156,7 +156,7 @@ def _batched_errors(task_vectors, compressed_all, bases, masks) -> Dict[str, Dic
         plans.setdefault(id(batch), (batch, []))[1].append((name, i, meta))
     out = {}
     for batch, items in plans.values():
-        plan, small = batch.plan, batch.small
+        plan = batch.plan
         with torch.cuda.device(plan.device):
             if batch.mode == "plain":
                 res = plan.diagnostics(batch.table, batch.rows_dev)
@@ -164,56 +164,69 @@ def _batched_errors(task_vectors, compressed_all, bases, masks) -> Dict[str, Dic
                 res = plan.diagnostics_masked(batch.table, batch.mask_table, batch.unit_start, batch.rows_dev)
             res = res.cpu().numpy()      # [P, N, 6]
         for name, i, meta in items:
-            tasks_i = batch.task_names[i]
-            pos = {t: j for j, t in enumerate(tasks_i)}
-            first = next(iter(task_vectors.keys()))
-            diag = {"param_name": name, "original_shape": None, "masked_size": 0, "unmasked_size": 0,
-                    "reconstruction_errors": {}, "compression_ratios": {}}
-            if name in task_vectors[first]:
-                diag["original_shape"] = list(task_vectors[first][name].shape)
-            k, r, rows = int(small.k[i]), int(small.r[i]), int(small.rows[i])
-            if batch.mode == "plain":
-                diag["masked_size"] = np.prod(diag["original_shape"])
-            else:      # mask.sum() / (~mask).sum() (diagnostics.py:168-169): the counts the run kept on the device
-                diag["masked_size"] = rows
-                diag["unmasked_size"] = int(plan.rows[i]) - rows
-            diag["basis"] = {"k": k, "D": rows, "N": plan.N, "energy_retained": float(small.energy[i])}
-            nl, bits, stages = r - k, plan.bits_of(i), plan.S
-            ratio = (nl * 4) / max(nl * bits / 8 * stages + 8 * stages, 1)      # estimate_compression_ratio, rtvq.py:142-161
-            errs = []
-            for task in task_vectors.keys():
-                if name not in task_vectors[task] or task not in pos or task not in meta["have"]:
-                    continue
-                m = {key: float(v) for key, v in zip(_KEYS, res[i, pos[task]])}
-                errs.append(m["relative_error"])
-                diag["reconstruction_errors"][task] = m
-                diag["compression_ratios"][task] = ratio
-            if errs:
-                diag["mean_relative_error"] = float(np.mean(errs))
-                diag["std_relative_error"] = float(np.std(errs))
-                diag["max_relative_error"] = float(np.max(errs))
-                diag["min_relative_error"] = float(np.min(errs))
-            out[name] = diag
+            out[name] = _plan_entry_diagnostics(batch, i, meta, name, task_vectors, res[i], batch.mode != "plain")
     return out
+
+
+def _plan_entry_diagnostics(batch, i, meta, name, task_vectors, res_i, masked: bool) -> Dict:
+    """compute_parameter_diagnostics' dictionary of plan entry ``i`` from its rows ``res_i`` [N, 6] of a plan-level
+    diagnostics call.  ``task_vectors``: {task: {name: tensor}}, read for names and shapes only (task deltas or
+    fine-tuned weights: the shapes are the same)."""
+    plan, small = batch.plan, batch.small
+    pos = {t: j for j, t in enumerate(batch.task_names[i])}
+    first = next(iter(task_vectors.keys()))
+    diag = {"param_name": name, "original_shape": None, "masked_size": 0, "unmasked_size": 0,
+            "reconstruction_errors": {}, "compression_ratios": {}}
+    if name in task_vectors[first]:
+        diag["original_shape"] = list(task_vectors[first][name].shape)
+    k, r, rows = int(small.k[i]), int(small.r[i]), int(small.rows[i])
+    if not masked:
+        diag["masked_size"] = np.prod(diag["original_shape"])
+    else:      # mask.sum() / (~mask).sum() (diagnostics.py:168-169): the counts the run kept on the device
+        diag["masked_size"] = rows
+        diag["unmasked_size"] = int(plan.rows[i]) - rows
+    diag["basis"] = {"k": k, "D": rows, "N": plan.N, "energy_retained": float(small.energy[i])}
+    nl, bits, stages = r - k, plan.bits_of(i), plan.S
+    ratio = (nl * 4) / max(nl * bits / 8 * stages + 8 * stages, 1)      # estimate_compression_ratio, rtvq.py:142-161
+    errs = []
+    for task in task_vectors.keys():
+        if name not in task_vectors[task] or task not in pos or task not in meta["have"]:
+            continue
+        m = {key: float(v) for key, v in zip(_KEYS, res_i[pos[task]])}
+        errs.append(m["relative_error"])
+        diag["reconstruction_errors"][task] = m
+        diag["compression_ratios"][task] = ratio
+    if errs:
+        diag["mean_relative_error"] = float(np.mean(errs))
+        diag["std_relative_error"] = float(np.std(errs))
+        diag["max_relative_error"] = float(np.max(errs))
+        diag["min_relative_error"] = float(np.min(errs))
+    return diag
 
 
 def compute_all_diagnostics(task_vectors: Dict[str, Dict[str, torch.Tensor]], compressed_all: Dict[str, Dict],
                             bases: Dict[str, Dict], masks: Dict[str, torch.Tensor], config, device: str = "cpu") -> Dict:
     """Reference diagnostics.py:234-321."""
     quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
-    out = {"config": {"svd_energy_threshold": config.svd_energy_threshold, "svd_max_rank": config.svd_max_rank,
-                      "svd_low_bits": config.svd_low_bits, "svd_rtvq_stages": config.svd_rtvq_stages,
-                      "svd_mask_strategy": config.svd_mask_strategy, "svd_weighting": config.svd_weighting},
-           "per_parameter": {}, "summary": {}}
+    per_parameter = {}
     pre = _batched_errors(task_vectors, compressed_all, bases, masks)
     for name in sorted(bases.keys()):
         if name not in compressed_all:
             continue
         if name in pre:
-            out["per_parameter"][name] = pre[name]
+            per_parameter[name] = pre[name]
             continue
-        out["per_parameter"][name] = compute_parameter_diagnostics(name, task_vectors, compressed_all[name],
-                                                                   bases[name], masks.get(name), quantizer, device)
+        per_parameter[name] = compute_parameter_diagnostics(name, task_vectors, compressed_all[name],
+                                                            bases[name], masks.get(name), quantizer, device)
+    return _all_diagnostics(per_parameter, config)
+
+
+def _all_diagnostics(per_parameter: Dict[str, Dict], config) -> Dict:
+    """The frame of compute_all_diagnostics' result (reference diagnostics.py:234-321) around its per-parameter part."""
+    out = {"config": {"svd_energy_threshold": config.svd_energy_threshold, "svd_max_rank": config.svd_max_rank,
+                      "svd_low_bits": config.svd_low_bits, "svd_rtvq_stages": config.svd_rtvq_stages,
+                      "svd_mask_strategy": config.svd_mask_strategy, "svd_weighting": config.svd_weighting},
+           "per_parameter": per_parameter, "summary": {}}
     ranks, energies, mean_errs, ratios = [], [], [], []
     for d in out["per_parameter"].values():
         if "basis" in d:
@@ -232,6 +245,151 @@ def compute_all_diagnostics(task_vectors: Dict[str, Dict[str, torch.Tensor]], co
         "average_compression_ratio": float(np.mean(ratios)) if ratios else 0,
     }
     return out
+
+
+def checkpoint_tables(names, task_names, base_state_dict, finetuned):
+    """The tensors behind the pointer tables of a plan-level diagnostics call from checkpoints
+    (svdq_diagnostics_from_base), in the plan's parameter and task order: ``names[p]`` is the parameter of plan entry
+    p, ``task_names[p]`` its tasks in plan order.  Returns ``(ft, base)``: ``ft`` [P * N] parameter-major --
+    ``ft[p * N + j] = finetuned[task_names[p][j]][names[p]]``, or None where that task lacks the parameter (the pair is
+    skipped: its slot is measured against nothing) -- and ``base`` [P].  A fine-tuned tensor whose shape is not its base
+    tensor's is a ValueError, as is a parameter without a base tensor.  Host only: reads names and shapes."""
+    ft, base = [], []
+    for name, tasks in zip(names, task_names):
+        if name not in base_state_dict:
+            raise ValueError(f"parameter {name!r}: no base tensor")
+        b = base_state_dict[name]
+        base.append(b)
+        for t in tasks:
+            f = finetuned.get(t, {}).get(name)
+            if f is not None and f.shape != b.shape:
+                raise ValueError(f"parameter {name!r}, task {t!r}: fine-tuned shape {tuple(f.shape)} vs base "
+                                 f"{tuple(b.shape)}")
+            ft.append(f)
+    return ft, base
+
+
+def _exact_for(plan_dtype: torch.dtype, tensors) -> bool:
+    """Can a plan whose input dtype is ``plan_dtype`` read ``tensors`` exactly?  As they are, or (an fp32 plan) widened
+    from fp16 / bf16; never narrowed."""
+    ok = (torch.float32, torch.float16, torch.bfloat16) if plan_dtype is torch.float32 else (plan_dtype,)
+    return all(t.dtype in ok for t in tensors if t is not None)
+
+
+def _checkpoint_errors(base_state_dict, finetuned, compressed_all, bases, masks) -> Dict[str, Dict]:
+    """compute_parameter_diagnostics' dictionaries, measured against ``finetuned - base`` formed inside the pass, for
+    every parameter whose artifacts live in a plan -- a fused run's (from deltas or from base) or an adopted one
+    (``adopt_artifacts``; masked parameters with ``masks=``): per plan one svdq_diagnostics_from_base over its unmasked
+    entries and one svdq_diagnostics_masked_from_base over its masked ones (rows_dev = 0 keeps a call away from the
+    other kind and from the noise entries, which have no diagnostics).  The tables are built from the caller's tensors;
+    a device copy the run kept of the very tensor the caller passes (``BatchResult.sources``) is reused instead of a
+    second upload.  Parameters a plan-level call cannot take are left to the caller's per-parameter route."""
+    from .driver import adopted_mask_walk
+    from .merge import _batched_entry, _mask_identity
+    from .pipeline import prepare_input
+    by_batch = {}
+    for name in bases.keys():
+        if name not in compressed_all or name not in base_state_dict:
+            continue
+        got = _batched_entry(name, compressed_all, bases)
+        if got is None:
+            continue
+        batch, i, meta = got
+        if getattr(batch, "mode", None) not in ("plain", "walk", "gather"):
+            continue
+        by_batch.setdefault(id(batch), (batch, []))[1].append((name, i, meta))
+    out = {}
+    for batch, items in by_batch.values():
+        plan = batch.plan
+        dev, idt, N = plan.device, plan.input_dtype, plan.N
+        adopted = bool(getattr(batch, "adopted", False))
+        walk = adopted_mask_walk(batch, masks) if adopted else None
+        kept = getattr(batch, "sources", None) or {}
+        plain, masked = [], []      # (name, i, meta, ft [N], base)
+        for name, i, meta in items:
+            ft, (b,) = checkpoint_tables([name], [batch.task_names[i]], base_state_dict, finetuned)
+            if not _exact_for(idt, ft + [b]):
+                continue
+            mask = masks.get(name)
+            if batch.mode == "plain" and (mask is None or not adopted):
+                if mask is not None or b.numel() != plan.rows[i] or int(batch.small.rows[i]) != plan.rows[i]:
+                    continue
+                plain.append((name, i, meta, ft, b))
+                continue
+            # masked: fp32 tensors only, the mask of the tensor's shape, and the mask the unit starts were made for
+            if idt is not torch.float32 or mask is None or mask.shape != b.shape or b.numel() != plan.rows[i]:
+                continue
+            if adopted:
+                if walk is None or i not in walk[2]:
+                    continue
+            elif batch.unit_start is None or getattr(batch, "mask_ident", {}).get(name) != _mask_identity(mask):
+                continue
+            masked.append((name, i, meta, ft, b))
+        with torch.cuda.device(dev):
+            for group, is_masked in ((plain, False), (masked, True)):
+                if not group:
+                    continue
+                hold = []
+
+                def addr(t):
+                    v = kept.get(id(t))
+                    v = v[1] if v is not None and v[0] is t else prepare_input(t, dev, idt)
+                    hold.append(v)
+                    return v.data_ptr()
+
+                ftab, btab, rows = [0] * (plan.P * N), [0] * plan.P, [0] * plan.P
+                for name, i, meta, ft, b in group:
+                    btab[i] = addr(b)
+                    # a task that lacks the parameter: its slot reads the base tensor (a zero delta nobody looks at)
+                    ftab[i * N:(i + 1) * N] = [addr(f) if f is not None else btab[i] for f in ft]
+                    rows[i] = int(batch.small.rows[i])
+                ftab, btab, rows = (torch.tensor(x, dtype=torch.int64).to(dev) for x in (ftab, btab, rows))
+                if not is_masked:
+                    res = plan.diagnostics_from_base(ftab, btab, rows)
+                elif adopted:
+                    res = plan.diagnostics_masked_from_base(ftab, btab, walk[0], walk[1], rows)
+                else:
+                    res = plan.diagnostics_masked_from_base(ftab, btab, batch.mask_table, batch.unit_start, rows)
+                res = res.cpu().numpy()      # [P, N, 6]; synchronises: the tables and copies may go
+                del hold
+                for name, i, meta, ft, b in group:
+                    out[name] = _plan_entry_diagnostics(batch, i, meta, name, finetuned, res[i], is_masked)
+    return out
+
+
+def compute_all_diagnostics_from_checkpoints(base_state_dict: Dict[str, torch.Tensor],
+                                             finetuned: Dict[str, Dict[str, torch.Tensor]], compressed_all: Dict[str, Dict],
+                                             bases: Dict[str, Dict], masks: Dict[str, torch.Tensor], config,
+                                             device: str = "cpu") -> Dict:
+    """``compute_all_diagnostics`` without task vectors: the same dictionary, measured against ``finetuned - base`` of
+    the checkpoints the caller passes (reference compute_task_vector, task_vector_loader.py:103-141, followed by
+    diagnostics.py:186-215; bit for bit the numbers of the fp32 deltas ``ft.float() - base.float()``).  Works on the
+    dictionaries of a fused run (from deltas or from checkpoints) and on adopted ones (``adopt_artifacts``; pass it the
+    ``masks`` the masked parameters are to be measured with).  Tensors are uploaded, or widened from fp16 / bf16 for an
+    fp32 plan, never narrowed.  What a plan-level call cannot take -- masked parameters of a half plan, a mask other
+    than the run's, dtypes the plan cannot read exactly, artifacts no plan holds -- goes through
+    ``compute_parameter_diagnostics`` on that one parameter's fp32 deltas, formed on the device."""
+    from .pipeline import resolve_device
+    masks = masks or {}
+    quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
+    dev = resolve_device(device)
+    pre = _checkpoint_errors(base_state_dict, finetuned, compressed_all, bases, masks)
+    per_parameter = {}
+    for name in sorted(bases.keys()):
+        if name not in compressed_all:
+            continue
+        if name in pre:
+            per_parameter[name] = pre[name]
+            continue
+        tasks = [t for t in finetuned if name in finetuned[t]]
+        ft, (b,) = checkpoint_tables([name], [tasks], base_state_dict, finetuned)
+        bf = b.to(dev).float()
+        deltas = {t: {} for t in finetuned}
+        for t, f in zip(tasks, ft):
+            deltas[t][name] = f.to(dev).float() - bf
+        per_parameter[name] = compute_parameter_diagnostics(name, deltas, compressed_all[name], bases[name],
+                                                            masks.get(name), quantizer, device)
+    return _all_diagnostics(per_parameter, config)
 
 
 def compute_compression_statistics(task_vectors: Dict[str, Dict[str, torch.Tensor]], compressed_all: Dict[str, Dict],

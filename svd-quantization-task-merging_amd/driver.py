@@ -91,7 +91,7 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                 # with the by-product a plan's Gram columns must mean the same tasks for all its parameters
                 groups.setdefault((tuple(present) if task_gram else len(present), "plain", idt), []).append(
                     {"name": name, "region": "masked", "tasks": present, "vectors": vs, "count": None,
-                     "upper": vs[0].numel(), "min": 0,
+                     "upper": vs[0].numel(), "min": 0, "src": deltas,
                      "base": prepare_input(base_state[name], dev, idt) if base_state is not None else None})
         # Masked parameters never get compacted copies of their deltas.  One count + scan per group (mask.sum() stays
         # on the device and becomes rows_dev); then, per region, one of two ways to reach the selected rows:
@@ -127,7 +127,7 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
 
                 idt, vs, bvec = inputs(walk_sig)
                 e = {"name": name, "region": "masked", "tasks": present, "vectors": vs, "count": ct[q:q + 1],
-                     "upper": vs[0].numel(), "min": min_size, "base": bvec}
+                     "upper": vs[0].numel(), "min": min_size, "base": bvec, "src": deltas}
                 e.update(ms=ms, q=q, inv=False, mask_ident=ident)
                 if not walk_sig:
                     e["index"] = it_[q]
@@ -135,7 +135,7 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
                 if include_noise:
                     idt, vs, bvec = inputs(walk_noise)
                     e = {"name": name, "region": "noise", "tasks": present, "vectors": vs, "count": cf[q:q + 1],
-                         "upper": vs[0].numel(), "min": 1, "gate": ct[q:q + 1], "base": bvec}
+                         "upper": vs[0].numel(), "min": 1, "gate": ct[q:q + 1], "base": bvec, "src": deltas}
                     e.update(ms=ms, q=q, inv=True, mask_ident=ident)
                     if not walk_noise:
                         e["index"] = if_[q]
@@ -221,6 +221,13 @@ def build_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], combined_masks
             batch.mask_table, batch.unit_start = mtab, us
             batch.mask_ident = {e["name"]: e["mask_ident"] for e in entries if "mask_ident" in e}
             batch.from_base = base_state is not None
+            # a from-base batch keeps its base table beside the fine-tuned one, and which of the caller's tensors each
+            # device tensor was prepared from: the diagnostics from checkpoints (svdq_diagnostics_from_base) read them again
+            batch.base_table = btab
+            batch.sources = None
+            if base_state is not None:
+                batch.sources = {id(s): (s, v) for e in entries
+                                 for s, v in zip(e["src"] + [base_state[e["name"]]], e["vectors"] + [e["base"]])}
             # the by-product: Gram of this plan's tensors, its task order, the parameters it covers
             batch.task_gram = ({"gram": gram, "tasks": list(entries[0]["tasks"]), "names": [e["name"] for e in entries]}
                                if want_gram else None)
@@ -723,6 +730,7 @@ def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], con
         batch.mode, batch.table, batch.rows_dev = "plain", None, None
         batch.mask_table, batch.unit_start, batch.mask_ident = None, None, {}
         batch.from_base, batch.task_gram, batch.adopted = False, None, True
+        batch.base_table, batch.sources = None, None
         plan._keep = None
         for i, e in enumerate(entries):
             where[(e["name"], e["region"])] = (batch, i)

@@ -609,6 +609,32 @@ class CompressPlan:
                   "svdq_diagnostics")
         return out
 
+    def diagnostics_from_base(self, ft_table, base_table, rows_dev: Optional[torch.Tensor] = None,
+                              add_mean: bool = False) -> torch.Tensor:
+        """``diagnostics`` straight from checkpoints (svdq_diagnostics_from_base): ``ft_table`` [P*N] names the
+        fine-tuned tensors, ``base_table`` [P] the base model's, all in the plan's input dtype; finetuned - base is
+        formed inside the pass.  Bit for bit ``diagnostics`` on fp32 tensors holding ``ft.float() - base.float()``."""
+        out = torch.empty((self.P, self.N, 6), dtype=torch.float64, device=self.device)
+        work = torch.empty(int(self.lib.svdq_diagnostics_work_bytes(self._h)), dtype=torch.uint8, device=self.device)
+        nat.check(self.lib.svdq_diagnostics_from_base(self._h, _ptr(ft_table), _ptr(base_table), _ptr(rows_dev),
+                                                      _ptr(self.small), _ptr(self.basis), _ptr(self.mean),
+                                                      int(bool(add_mean)), _ptr(out), _ptr(work), _stream_ptr()),
+                  "svdq_diagnostics_from_base")
+        return out
+
+    def diagnostics_masked_from_base(self, ft_table, base_table, mask_table: torch.Tensor, unit_start: torch.Tensor,
+                                     rows_dev: torch.Tensor, add_mean: bool = False) -> torch.Tensor:
+        """``diagnostics_masked`` straight from checkpoints (svdq_diagnostics_masked_from_base): the tables name the
+        FULL fp32 fine-tuned and base tensors; the selection and the subtraction both happen inside the pass."""
+        out = torch.empty((self.P, self.N, 6), dtype=torch.float64, device=self.device)
+        work = torch.empty(int(self.lib.svdq_diagnostics_work_bytes(self._h)), dtype=torch.uint8, device=self.device)
+        nat.check(self.lib.svdq_diagnostics_masked_from_base(self._h, _ptr(ft_table), _ptr(base_table), _ptr(mask_table),
+                                                             _ptr(unit_start), _ptr(rows_dev), _ptr(self.small),
+                                                             _ptr(self.basis), _ptr(self.mean), int(bool(add_mean)),
+                                                             _ptr(out), _ptr(work), _stream_ptr()),
+                  "svdq_diagnostics_masked_from_base")
+        return out
+
     def tune_placement(self, table, rows_dev=None, candidates: int = 6, reps: int = 2,
                        max_spacer_bytes: int = 32 << 30) -> List[float]:
         """Put the output buffers where pass 2 runs fastest.
