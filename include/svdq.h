@@ -651,6 +651,45 @@ int svdq_plan_import(const svdq_plan *plan, const void *u_high_ptrs_dev /*[P]*/,
                      const void *mean_ptrs_dev /*[P], NULL when center == 0*/, const void *small_dev, void *basis_dev,
                      float *mean_dev, void *stream);
 
+/* ---- project NEW task tensors onto the basis a plan already holds (the one statement of the contract; the sources point
+ *      here).  The reference's Step 5 on its own: compress_all_parameters (compress.py:173-207) -> compress_parameter ->
+ *      compress_single_task -> project_to_basis (compress.py:6-56) with bases that were not made in this process -- loaded
+ *      from disk, adopted, a caller's own U.  A new fine-tuned model is projected onto the stored bases, its coefficients
+ *      are quantized, and it joins the store; no other task's checkpoint is read and no basis is recomputed.  Pass 2 of the
+ *      compressor without pass 1: the basis, mean, k, r and rows in the plan's buffers are ONLY READ (they may come from
+ *      any compress route or from svdq_plan_import), and the coefficient epilogue is the fused route's own code.
+ *   task_ptrs_dev   [P*N], parameter-major: the tensor of task slot t of parameter p; a NULL entry = the slot is absent:
+ *                   nothing of it is read and its fields in small_dev stay exactly as they were.  Element type: the plan's
+ *                   input type (fp32 16-byte aligned, fp16 / bf16 8-byte aligned).
+ *   base_ptrs_dev   NULL, or [P] base tensors of the same element type: the task tensors are then FINE-TUNED weights and
+ *                   x[d] = finetuned[d] - base[d], one fp32 subtraction (compute_task_vector, task_vector_loader.py:103-141).
+ *   index_ptrs_dev  NULL, or [P] int32 index lists (the ascending positions svdq_maskset_indices writes): row d of
+ *                   parameter p is element index[p][d] of the full-size task (and base) tensors.  The mask walk is not
+ *                   offered here.
+ *   rows_dev        NULL (the plan's rows) or int64 [P]: rows of each parameter's basis, <= the plan's rows; 0 = nothing of
+ *                   p is read or written.
+ *   arithmetic      for every present slot: c[i] = sum_d float(U[d][i]) * xc[d] for i < r[p], columns < k[p] from U_high, the
+ *                   rest from U_low; xc[d] = x[d] - mean[d] on a centred plan (one fp32 subtraction), x[d] otherwise.  Sums
+ *                   are fp32 inside one block of at most 256 rows (the matrix pipe's chain over the block's rows) and fp64
+ *                   across blocks and work units, in a fixed order without atomics: the same bits in every run.  Then
+ *                   compress_single_task's tail: coef = the fp32 coefficients, c_high = coef[:k] as fp16, and codes, scale,
+ *                   zero_point, residual_norm = RTVQQuantizer(bits[p], stages).quantize(coef[k:r]) bit for bit
+ *                   (svdq_plan_set_low_bits is respected).
+ *   launches        two: one streaming launch over the plan's own work units -- a block of basis, mean and base rows is
+ *                   read once, and the rows of every present task once; one fp64 partial per unit goes to work_dev -- and
+ *                   the fixed-order finish with the quantizer.
+ *   never written   sigma, k, r, energy, rows, status, the basis and the mean; the fields of absent slots.
+ *   errors          NULL plan, task_ptrs_dev, basis_dev, small_dev or work_dev, or a NULL mean_dev on a centred plan:
+ *                   SVDQ_EINVAL before anything is launched.  (On an uncentred plan mean_dev is ignored.)
+ *   work_dev        svdq_plan_project_work_bytes bytes (one N x N fp64 matrix per work unit).
+ *   Allocates nothing, copies nothing to the host, synchronises nothing: capturable like every other entry point.  Any
+ *   N <= SVDQ_MAX_TASKS, fp16 or fp32 basis. */
+int64_t svdq_plan_project_work_bytes(const svdq_plan *plan);
+int svdq_plan_project(const svdq_plan *plan, const void *task_ptrs_dev /*[P*N]; NULL entry = slot absent*/,
+                      const void *base_ptrs_dev /*NULL or [P]*/, const void *index_ptrs_dev /*NULL or [P]*/,
+                      const int64_t *rows_dev, const void *basis_dev, const float *mean_dev, void *small_dev,
+                      void *work_dev, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

@@ -2,6 +2,10 @@
 Task-vector compression with the reference's call signatures and return layouts
 (reference src/svd_hybrid/compress.py:6-207).
 
+``project_all_parameters`` is the batched form of the second route below: stored bases go into plans
+(``driver.adopt_bases``) and ONE ``svdq_plan_project`` per plan projects and quantizes every new task.  It is a name of its
+own because its last bits differ from ``svdq_project``'s grid-stride sums.
+
 Two routes produce identical artifact dicts:
   * bases that came out of ``driver.run_basis_and_compress`` / ``driver.build_bases`` carry the
     coefficients the fused pass 2 already computed; ``compress_all_parameters`` just assembles them;
@@ -149,3 +153,153 @@ def compress_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], ma
         if gc_was_on:
             gc.enable()
     return out
+
+
+def project_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], masks: Optional[Dict[str, torch.Tensor]],
+                           bases: Dict[str, Dict], config, device: str = "cuda",
+                           base_state_dict: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Dict]:
+    """``compress_all_parameters`` for NEW tasks against bases that already exist -- loaded from disk, adopted, a
+    caller's own U -- in one ``svdq_plan_project`` per plan instead of a selection, a projection launch pair, a
+    device-to-host copy and a quantizer call per (parameter, region, task).  Returns exactly the dictionary layout
+    ``compress_all_parameters`` returns: {param: {task: {"masked": {...}, "unmasked": ... | None}}}, CPU tensors.
+
+    ``task_vectors``: {task: {param: tensor}}, up to 32 tasks; with ``base_state_dict`` they hold FINE-TUNED weights and
+    finetuned - base is formed inside the launch (no task vectors in memory).  Tensors that are all fp16 or all bf16
+    (base included) are read as they are.  A masked parameter (``masks[name]`` of the tensor's shape) is read through
+    index lists built once per parameter (svdq_maskset_indices); its noise region, when ``config.svd_include_noise``,
+    through the inverted list against ``bases[name]["noise"]``.  A selected count that differs from the stored D raises a
+    ``ValueError`` naming the parameter.  What ``adopt_bases`` declines -- and a parameter whose mask selects fewer than
+    ``svd_min_mask_size`` elements -- goes through ``compress_parameter``, unchanged (there ``task_vectors`` must hold
+    task vectors: with ``base_state_dict`` the difference is formed first, for those parameters only)."""
+    import gc
+    from . import mask_loader as ml
+    from .driver import adopt_bases
+    from .pipeline import native_input_dtype, prepare_input, task_artifact
+    masks = masks or {}
+    tasks = list(task_vectors.keys())
+    if not tasks:
+        return {}
+    if len(tasks) > nat.MAX_TASKS:
+        raise ValueError(f"project_all_parameters takes at most {nat.MAX_TASKS} tasks per call, got {len(tasks)}")
+    dev = resolve_device(device)
+    include_noise = bool(config.svd_include_noise)
+
+    def usable_mask(name):
+        """The mask as compress_parameter applies it: only when its shape is the tensors' shape."""
+        m = masks.get(name)
+        if m is None:
+            return None
+        shapes = {tuple(tv[name].shape) for tv in task_vectors.values() if name in tv}
+        return m if shapes == {tuple(m.shape)} else None
+
+    names = [n for n in sorted(bases.keys()) if any(n in tv for tv in task_vectors.values())]
+    mask_of = {n: usable_mask(n) for n in names}
+    # masks that select fewer than min_mask_size elements empty the masked region (compress.py:143-147): per parameter
+    small_mask = {n for n, m in mask_of.items() if m is not None and int(m.sum()) < config.svd_min_mask_size}
+    batched_bases = {n: bases[n] for n in names if n not in small_mask}
+    covered = [t[n] for t in task_vectors.values() for n in batched_bases if n in t]
+    if base_state_dict is not None:
+        missing = [n for n in names if n not in base_state_dict]
+        if missing:
+            raise ValueError(f"base_state_dict lacks parameter {missing[0]!r}")
+        covered += [base_state_dict[n] for n in batched_bases]
+    in_dtype = native_input_dtype(covered)
+    batches, declined = adopt_bases(batched_bases, config, len(tasks), device=dev, input_dtype=in_dtype)
+
+    out: Dict[str, Dict] = {}
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.device(dev):
+            for batch in batches:
+                plan = batch.plan
+                P, N = plan.P, plan.N
+                stored = [int(r) for r in batch.small.rows]
+                # index lists, once per masked parameter of the plan
+                mnames = []
+                for name, _ in batch.entries:
+                    if mask_of[name] is not None and name not in mnames:
+                        mnames.append(name)
+                idx_true = idx_false = {}
+                ms = None
+                if mnames:
+                    ms = ml.MaskSet([int(mask_of[n].numel()) for n in mnames], dev)
+                    it, if_, ct, cf = ms.indices([mask_of[n] for n in mnames], include_noise)
+                    counts = torch.stack([ct, cf if cf is not None else torch.zeros_like(ct)]).cpu().tolist()
+                    idx_true = {n: (it[q], counts[0][q]) for q, n in enumerate(mnames)}
+                    idx_false = {n: (if_[q], counts[1][q]) for q, n in enumerate(mnames)} if include_noise else {}
+                keep, tab, btab, itab, active = [], [0] * (P * N), [0] * P, [0] * P, [False] * P
+                for i, (name, region) in enumerate(batch.entries):
+                    if region == "noise" and not include_noise:
+                        continue      # compress_parameter hands no noise basis on: "unmasked" stays None
+                    m = mask_of[name]
+                    if region == "noise" and m is None:
+                        continue      # no mask, no noise region (compress.py:150-152)
+                    numel = None
+                    for t, task in enumerate(tasks):
+                        x = task_vectors[task].get(name)
+                        if x is None:
+                            continue
+                        v = prepare_input(x, dev, in_dtype)
+                        numel = v.numel()
+                        keep.append(v)
+                        tab[i * N + t] = v.data_ptr()
+                    if m is not None:
+                        lst, count = (idx_false if region == "noise" else idx_true)[name]
+                        keep.append(lst)
+                        itab[i] = lst.data_ptr()
+                    else:
+                        count = numel
+                    if count != stored[i]:
+                        raise ValueError(f"parameter {name!r} [{region}]: {count} selected elements, the stored basis "
+                                         f"has D = {stored[i]}")
+                    if base_state_dict is not None:
+                        b = prepare_input(base_state_dict[name], dev, in_dtype)
+                        if b.numel() != numel:
+                            raise ValueError(f"parameter {name!r}: the base tensor has {b.numel()} elements, the "
+                                             f"task tensors {numel}")
+                        keep.append(b)
+                        btab[i] = b.data_ptr()
+                    active[i] = True
+                has_idx = any(itab)
+                if has_idx:
+                    # a plan mixes masked and unmasked entries: an unmasked one reads through the identity list
+                    for i, (name, region) in enumerate(batch.entries):
+                        if active[i] and not itab[i]:
+                            ident = torch.arange(stored[i], dtype=torch.int32, device=dev)
+                            keep.append(ident)
+                            itab[i] = ident.data_ptr()
+                rows_dev = torch.tensor([stored[i] if active[i] else 0 for i in range(P)], dtype=torch.int64).to(dev)
+                table = torch.tensor(tab, dtype=torch.int64).to(dev)
+                base_table = torch.tensor(btab, dtype=torch.int64).to(dev) if base_state_dict is not None else None
+                index_table = torch.tensor(itab, dtype=torch.int64).to(dev) if has_idx else None
+                sm = plan.project_tasks(table, base_table=base_table, index_table=index_table, rows_dev=rows_dev)
+                del keep, ms
+                for i, (name, region) in enumerate(batch.entries):
+                    art_key = "masked" if region == "masked" else "unmasked"
+                    per_task = out.setdefault(name, {})
+                    for t, task in enumerate(tasks):
+                        if name not in task_vectors[task]:
+                            continue
+                        art = per_task.setdefault(task, {"masked": None, "unmasked": None})
+                        if active[i]:
+                            art[art_key] = task_artifact(plan, sm, i, t)
+        # the per-parameter route for whatever did not go into a plan
+        rest = [n for n in names if n not in out]
+        if rest:
+            quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
+            for name in rest:
+                tv = task_vectors
+                if base_state_dict is not None:
+                    b = base_state_dict[name]
+                    tv = {t: {name: (v[name].to(dev).float() - b.to(dev).float())} for t, v in task_vectors.items()
+                          if name in v}
+                comp = compress_parameter(name, tv, masks.get(name), bases[name], quantizer,
+                                          include_noise=include_noise, min_mask_size=config.svd_min_mask_size,
+                                          device=device)
+                if comp is not None:
+                    out[name] = comp
+    finally:
+        if gc_was_on:
+            gc.enable()
+    return {n: out[n] for n in sorted(out)}

@@ -1,0 +1,368 @@
+// svdq_plan_project.hip -- svdq_plan_project: the projections of NEW task tensors onto the basis a plan already holds
+// (contract: include/svdq.h).  Pass 2 of the compressor without pass 1: the basis, mean, k and r in the plan's buffers
+// are only read -- they may come from any compress route or from svdq_plan_import -- and the coefficient epilogue is the
+// fused route's own (svdq_coeff.h).  Replaces the per-(parameter, region, task) loop of compress_all_parameters
+// (compress.py:173-207) -> compress_parameter (:114-170) -> compress_single_task (:24-56) -> project_to_basis (:6-21).
+//
+// Two launches.
+//   k_plan_project         one wavefront per work unit of the plan.  A block of RB rows (256 up to 16 task slots, 128
+//                          above): the block's U_high / U_low rows are staged row-major in LDS (svdq_merge_stream.h's
+//                          staging), the rows of every PRESENT task slot are loaded once, x = finetuned - base and
+//                          xc = x - mean are formed in registers (one fp32 subtraction each) and written to per-task
+//                          LDS strips X[t][row].  The r x M products of a row go to the matrix pipe:
+//                          v_mfma_f32_16x16x4f32 with A[i][kk] = U[row kk][column i], B[kk][j] = xc[task j][row kk];
+//                          the contraction runs over the block's rows, four per instruction, so a block's sum is one
+//                          fp32 accumulation chain of RB / 4 steps per (column, task) and the result tile holds
+//                          c[task][column] directly.  After each block the tile is added to fp64 accumulators; a unit
+//                          leaves one fp64 partial matrix [task][column] in work_dev.
+//   k_plan_project_finish  per parameter: the unit partials summed in a fixed order (reduce_partials), then
+//                          coeff_store_quantize for the present slots.
+// No atomics: the same bits in every run.  Compiled with -ffp-contract=off (the quantizer's roundings).
+
+#include "svdq_coeff.h"
+#include "svdq_dispatch.h"
+#include "svdq_input.h"
+#include "svdq_merge_stream.h"
+
+typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(1))) int32_t pp_gint;
+
+__device__ __forceinline__ float pp_lds_u(const uint8_t *base, int byte_off, __half) {
+    return __half2float(*reinterpret_cast<const __half *>(base + byte_off));
+}
+__device__ __forceinline__ float pp_lds_u(const uint8_t *base, int byte_off, float) {
+    return *reinterpret_cast<const float *>(base + byte_off);
+}
+
+// k and r as every consumer reads them, held to what the slab has room for (svdq_plan_import's rule)
+__device__ __forceinline__ void pp_ranks(const int32_t *k_in, const int32_t *r_in, int p, int64_t rows, int n, int &k,
+                                         int &r) {
+    const int64_t rmax = rows < n ? rows : n;
+    int64_t rr = r_in[p], kk = k_in[p];
+    rr = rr < 0 ? 0 : (rr > rmax ? rmax : rr);
+    kk = kk < 0 ? 0 : (kk > rr ? rr : kk);
+    k = (int)kk;
+    r = (int)rr;
+}
+
+__host__ __device__ constexpr int pp_xs(int rb) { return rb + 4; }      // strip stride (floats)
+
+// NTP: the task slots the instantiation has registers for (8, 16 or 32 >= N): the prefetch registers of a block are
+// NTP x RPL task values and the block's basis rows, and with them sized to the plan the kernel runs at three to four
+// waves per SIMD up to 8 slots -- one wave per SIMD leaves the pass at a quarter of the read rate.
+// TL = 16-slot tiles of the task (and column) dimension: 1 for N <= 16, 2 above.  GATHER: rows through int32 index lists.
+// FB: the task tensors are fine-tuned weights, base_ptrs names the base tensors.
+template <bool U16, typename TIN, int NTP, bool GATHER, bool FB>
+__global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict__ params,
+                                                     const SvdqUnit *__restrict__ units,
+                                                     const void *const *__restrict__ ptrs,
+                                                     const void *const *__restrict__ base_ptrs,
+                                                     const int32_t *const *__restrict__ idx_ptrs,
+                                                     const int64_t *__restrict__ rows_dev, int NT,
+                                                     const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
+                                                     const uint8_t *__restrict__ basis, const float *__restrict__ meanbuf,
+                                                     double *__restrict__ part /* [n_units][NT * NT] */) {
+    using T = typename UElem<U16>::type;
+    constexpr int ES = U16 ? 2 : 4;
+    constexpr int TL = NTP > 16 ? 2 : 1;
+    constexpr int RPL = TL == 1 ? 4 : 2, RB = 64 * RPL, XS = pp_xs(RB);
+    constexpr int SV = (RB * NTP * ES / 16 + 2 + 63) / 64;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
+    const int lane = threadIdx.x, n = NT, u = blockIdx.x;
+    const int g = lane >> 4, col = lane & 15;
+    uint8_t *Ubuf = lds_raw;
+    float *X = reinterpret_cast<float *>(lds_raw + stream_ubytes(RB, n, ES));      // [n][XS]
+    const SvdqUnit ud = units[u];
+    const int p = ud.param;
+    const SvdqParam pd = params[p];
+    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
+    if (D > pd.rows) D = pd.rows;
+    int64_t cpos = ud.row0;
+    int64_t cend = ud.row0 + ud.nrows;
+    if (cend > D) cend = D;
+    double accd[TL][TL][4];
+#pragma unroll
+    for (int ti = 0; ti < TL; ++ti)
+#pragma unroll
+        for (int tt = 0; tt < TL; ++tt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) accd[ti][tt][v] = 0.0;
+    int k = 0, r = 0;
+    if (cpos < cend) pp_ranks(k_in, r_in, p, D, n, k, r);
+    if (cpos < cend && r > 0) {      // wave-uniform
+        const int nl = r - k;
+        const uint8_t *gUh = basis + pd.slab_off;
+        const uint8_t *gUl = gUh + svdq_align_up(D * (int64_t)k * ES, 256);
+        mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
+        gin<TIN> *dp[NTP];
+#pragma unroll
+        for (int t = 0; t < NTP; ++t) dp[t] = t < n ? (gin<TIN> *)ptrs[(size_t)p * n + t] : nullptr;
+        gin<TIN> *bp = nullptr;
+        if constexpr (FB) bp = (gin<TIN> *)base_ptrs[p];
+        pp_gint *gidx = nullptr;
+        if constexpr (GATHER) gidx = (pp_gint *)idx_ptrs[p];
+
+        // ---- the loads of one block into registers; lane l owns rows c0 + RPL l .. + RPL - 1
+        float xpf[NTP][RPL] = {}, mpf[RPL] = {}, bpf[RPL] = {};
+        f32x4 ureg[SV];
+        auto prefetch = [&](int64_t c0) {
+            const int64_t r0 = c0 + RPL * lane;
+            const int nr = block_rows<RB>(c0, cend);
+            if constexpr (GATHER) {
+                int64_t src[RPL];
+                bool in[RPL];
+#pragma unroll
+                for (int e = 0; e < RPL; ++e) {
+                    in[e] = r0 + e < cend;
+                    src[e] = in[e] ? (int64_t)gidx[r0 + e] : 0;
+                }
+                if constexpr (FB) {
+#pragma unroll
+                    for (int e = 0; e < RPL; ++e) bpf[e] = in[e] ? in_load1<TIN>(bp + src[e]) : 0.f;
+                }
+#pragma unroll
+                for (int t = 0; t < NTP; ++t)
+                    if (dp[t]) {      // wave-uniform
+#pragma unroll
+                        for (int e = 0; e < RPL; ++e) xpf[t][e] = in[e] ? in_load1<TIN>(dp[t] + src[e]) : 0.f;
+                    }
+            } else if (nr == RB) {
+                if constexpr (FB) {
+                    if constexpr (RPL == 4) {
+                        const f32x4 v = in_load4<TIN>(bp + r0);
+                        bpf[0] = v.x, bpf[1] = v.y, bpf[2] = v.z, bpf[3] = v.w;
+                    } else {
+                        const svdq_f32x2 v = in_load2<TIN>(bp + r0);
+                        bpf[0] = v.x, bpf[1] = v.y;
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < NTP; ++t)
+                    if (dp[t]) {
+                        if constexpr (RPL == 4) {
+                            const f32x4 v = in_load4<TIN>(dp[t] + r0);
+                            xpf[t][0] = v.x, xpf[t][1] = v.y, xpf[t][2] = v.z, xpf[t][3] = v.w;
+                        } else {
+                            const svdq_f32x2 v = in_load2<TIN>(dp[t] + r0);
+                            xpf[t][0] = v.x, xpf[t][1] = v.y;
+                        }
+                    }
+            } else {
+                if constexpr (FB) {
+#pragma unroll
+                    for (int e = 0; e < RPL; ++e) bpf[e] = (r0 + e < cend) ? in_load1<TIN>(bp + (r0 + e)) : 0.f;
+                }
+#pragma unroll
+                for (int t = 0; t < NTP; ++t)
+                    if (dp[t]) {
+#pragma unroll
+                        for (int e = 0; e < RPL; ++e) xpf[t][e] = (r0 + e < cend) ? in_load1<TIN>(dp[t] + (r0 + e)) : 0.f;
+                    }
+            }
+            if (gmean) {
+#pragma unroll
+                for (int e = 0; e < RPL; ++e) mpf[e] = (r0 + e < cend) ? gmean[r0 + e] : 0.f;
+            }
+            ustage_fetch(ureg, ustage_plan<ES>(c0, nr, k, nl), gUh, gUl, lane);
+        };
+
+        // ---- where the lane's A operand (basis column i = col + 16 ti, row 4 g of a 16-row step) sits in the staged image.
+        // A column past r reads column 0 of a part that exists: a finite staged value whose result row is dropped.
+        const int ntile_i = (r + 15) >> 4;
+        auto compute = [&](const UStage &cur, int count, auto masked_c) {
+            constexpr bool MASKED = decltype(masked_c)::value;
+            int ua[TL], urow[TL];
+#pragma unroll
+            for (int ti = 0; ti < TL; ++ti) {
+                int i = col + 16 * ti;
+                if (i >= r) i = 0;
+                const bool hi = i < k;
+                const int w = hi ? k : nl;
+                urow[ti] = w * ES;
+                ua[ti] = (hi ? cur.offh * ES : 16 * cur.nvh + cur.offl * ES) + (4 * g * w + (hi ? i : i - k)) * ES;
+            }
+            int xo[TL];
+#pragma unroll
+            for (int tt = 0; tt < TL; ++tt) {
+                const int j = col + 16 * tt;
+                xo[tt] = (j < n ? j : 0) * XS + 4 * g;
+            }
+            f32x4 acc[TL][TL];
+#pragma unroll
+            for (int ti = 0; ti < TL; ++ti)
+#pragma unroll
+                for (int tt = 0; tt < TL; ++tt) acc[ti][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int nsteps = (count + 15) >> 4;
+            // two steps in flight: unrolled further (a full block's count is a constant) the LDS reads of all sixteen steps
+            // are hoisted and hold 100 more vector registers, which costs the kernel half of its waves
+#pragma unroll 2
+            for (int s = 0; s < nsteps; ++s) {
+                f32x4 xb[TL];
+#pragma unroll
+                for (int tt = 0; tt < TL; ++tt) xb[tt] = *reinterpret_cast<const f32x4 *>(X + xo[tt] + 16 * s);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    float a[TL];
+#pragma unroll
+                    for (int ti = 0; ti < TL; ++ti) {
+                        a[ti] = 0.f;
+                        if (ti < ntile_i) {      // wave-uniform
+                            a[ti] = pp_lds_u(Ubuf, ua[ti] + (16 * s + v) * urow[ti], T{});
+                            // rows past the block's count were never staged: whatever sits there must not reach the
+                            // matrix pipe (their x is an exact zero, but NaN * 0 is NaN)
+                            if constexpr (MASKED) a[ti] = (16 * s + 4 * g + v < count) ? a[ti] : 0.f;
+                        }
+                    }
+#pragma unroll
+                    for (int ti = 0; ti < TL; ++ti)
+                        if (ti < ntile_i) {
+#pragma unroll
+                            for (int tt = 0; tt < TL; ++tt)
+                                acc[ti][tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ti], xb[tt][v], acc[ti][tt], 0, 0, 0);
+                        }
+                }
+            }
+#pragma unroll
+            for (int ti = 0; ti < TL; ++ti)
+#pragma unroll
+                for (int tt = 0; tt < TL; ++tt)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) accd[ti][tt][v] += (double)acc[ti][tt][v];
+        };
+
+        prefetch(cpos);
+        while (true) {
+            const int nr = block_rows<RB>(cpos, cend);
+            const UStage cur = ustage_plan<ES>(cpos, nr, k, nl);
+            ustage_commit(Ubuf, ureg, cur, lane);
+            // xc = (finetuned - base) - mean, each a single fp32 subtraction; rows past the block's end are 0 - 0 - 0
+#pragma unroll
+            for (int t = 0; t < NTP; ++t)
+                if (dp[t]) {
+                    float xc[RPL];
+#pragma unroll
+                    for (int e = 0; e < RPL; ++e) {
+                        float x = xpf[t][e];
+                        if constexpr (FB) x = __fsub_rn(x, bpf[e]);
+                        if (gmean) x = __fsub_rn(x, mpf[e]);
+                        xc[e] = x;
+                    }
+                    if constexpr (RPL == 4) {
+                        *reinterpret_cast<f32x4 *>(X + t * XS + 4 * lane) = f32x4{xc[0], xc[1], xc[2], xc[3]};
+                    } else {
+                        *reinterpret_cast<pp_f32x2 *>(X + t * XS + 2 * lane) = pp_f32x2{xc[0], xc[1]};
+                    }
+                }
+            lds_fence();
+            const bool more = cpos + RB < cend;
+            if (more) prefetch(cpos + RB);
+            if (nr == RB) compute(cur, nr, std::false_type{});
+            else compute(cur, nr, std::true_type{});
+            if (!more) break;
+            cpos += RB;
+            lds_fence();      // the strips and the basis rows are rewritten next
+        }
+    }
+    // the unit's partial [task][column]: result register v of tile (ti, tt) is column 16 ti + 4 g + v of task 16 tt + col.
+    // Columns past r and absent slots leave as zeros, so work_dev is the same bytes in every run.
+    double *dst = part + (size_t)u * n * n;
+#pragma unroll
+    for (int tt = 0; tt < TL; ++tt) {
+        const int t = col + 16 * tt;
+        if (t >= n) continue;
+        const bool present = ptrs[(size_t)p * n + t] != nullptr;
+#pragma unroll
+        for (int ti = 0; ti < TL; ++ti)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int i = 16 * ti + 4 * g + v;
+                if (i < n) dst[(size_t)t * n + i] = (present && i < r) ? accd[ti][tt][v] : 0.0;
+            }
+    }
+}
+
+__global__ __launch_bounds__(EIG_THREADS) void k_plan_project_finish(
+    const SvdqParam *__restrict__ params, const void *const *__restrict__ ptrs, const int64_t *__restrict__ rows_dev,
+    int NT, int bits, int stages, const int32_t *__restrict__ bits_tab, const double *__restrict__ part,
+    const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in, float *__restrict__ coef_out,
+    uint16_t *__restrict__ chigh_out, uint8_t *__restrict__ codes_out, float *__restrict__ scale_out,
+    float *__restrict__ zp_out, float *__restrict__ rnorm_out) {
+    __shared__ double red[4 * 1024];
+    __shared__ double C[1024];
+    __shared__ float res[32 * LDN];
+    const int p = blockIdx.x, n = NT;
+    const SvdqParam pd = params[p];
+    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
+    if (D > pd.rows) D = pd.rows;
+    if (D <= 0) return;      // workgroup-uniform: nothing of p is written
+    if (bits_tab) bits = bits_tab[p];
+    reduce_partials(part, pd.unit_begin, pd.unit_begin + pd.unit_count, n * n, red, C);
+    int k, r;
+    pp_ranks(k_in, r_in, p, D, n, k, r);
+    coeff_store_quantize(p, n, k, r, bits, stages, C, nullptr, ptrs + (size_t)p * n, res, coef_out, chigh_out, codes_out,
+                         scale_out, zp_out, rnorm_out);
+}
+
+extern "C" int64_t svdq_plan_project_work_bytes(const svdq_plan *pl) {
+    if (!pl) return 0;
+    return svdq_align_up((int64_t)pl->n_units * pl->n_tasks * pl->n_tasks * 8, 256);
+}
+
+extern "C" int svdq_plan_project(const svdq_plan *pl, const void *task_ptrs, const void *base_ptrs, const void *index_ptrs,
+                                 const int64_t *rows_dev, const void *basis, const float *mean, void *small, void *work,
+                                 void *stream) {
+    if (!pl || !task_ptrs || !basis || !small || !work) {
+        svdq_set_error("svdq_plan_project: the plan, task_ptrs, basis, small and work are required");
+        return SVDQ_EINVAL;
+    }
+    if (pl->cfg.center && !mean) {
+        svdq_set_error("svdq_plan_project: mean is required on a centred plan");
+        return SVDQ_EINVAL;
+    }
+    if (((uintptr_t)task_ptrs | (uintptr_t)base_ptrs | (uintptr_t)index_ptrs | (uintptr_t)rows_dev | (uintptr_t)work) & 7) {
+        svdq_set_error("svdq_plan_project: pointer tables, rows and work must be 8-byte aligned");
+        return SVDQ_EINVAL;
+    }
+    if (((uintptr_t)small | (uintptr_t)basis | (uintptr_t)mean) & 15) {
+        svdq_set_error("svdq_plan_project: small, basis and mean must be 16-byte aligned");
+        return SVDQ_EINVAL;
+    }
+    const svdq_small_layout &L = pl->small;
+    uint8_t *sm = reinterpret_cast<uint8_t *>(small);
+    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    auto tp = reinterpret_cast<const void *const *>(task_ptrs), bp = reinterpret_cast<const void *const *>(base_ptrs);
+    auto ip = reinterpret_cast<const int32_t *const *>(index_ptrs);
+    auto bs = reinterpret_cast<const uint8_t *>(basis);
+    const float *mn = pl->cfg.center ? mean : nullptr;      // an uncentred plan subtracts nothing
+    double *part = reinterpret_cast<double *>(work);
+    hipStream_t st = (hipStream_t)stream;
+    const int n = pl->n_tasks;
+    const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
+        using TIN = typename decltype(tin_c)::type;
+        return svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
+            constexpr bool U16 = f16_c;
+            return svdq_dispatch_int<8, 16, 32>(n <= 8 ? 8 : (n <= 16 ? 16 : 32), [&](auto ntp_c) {
+                constexpr int NTP = ntp_c;
+                return svdq_dispatch_bool(index_ptrs != nullptr, [&](auto gather_c) {
+                    constexpr bool GATHER = gather_c;
+                    return svdq_dispatch_bool(base_ptrs != nullptr, [&](auto fb_c) {
+                        constexpr bool FB = fb_c;
+                        constexpr int RB = NTP <= 16 ? 256 : 128, ES = U16 ? 2 : 4;
+                        const size_t lds = (size_t)stream_ubytes(RB, n, ES) + (size_t)n * pp_xs(RB) * 4;
+                        hipLaunchKernelGGL((k_plan_project<U16, TIN, NTP, GATHER, FB>), dim3(pl->n_units), dim3(64), lds, st,
+                                           pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, kk, rr, bs, mn, part);
+                        return true;
+                    });
+                });
+            });
+        });
+    });
+    if (!ok) return svdq_launch_status(false, "k_plan_project");
+    if (hipGetLastError() != hipSuccess) return SVDQ_EHIP;
+    hipLaunchKernelGGL(k_plan_project_finish, dim3(pl->n_params), dim3(EIG_THREADS), 0, st, pl->d_params, tp, rows_dev, n,
+                       pl->cfg.low_bits, pl->cfg.rtvq_stages, pl->d_bits, part, kk, rr,
+                       reinterpret_cast<float *>(sm + L.coef_off), reinterpret_cast<uint16_t *>(sm + L.chigh_off),
+                       sm + L.codes_off, reinterpret_cast<float *>(sm + L.scale_off),
+                       reinterpret_cast<float *>(sm + L.zp_off), reinterpret_cast<float *>(sm + L.rnorm_off));
+    return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
+}

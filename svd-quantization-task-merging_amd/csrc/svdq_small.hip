@@ -10,33 +10,7 @@
 
 #include "svdq_common.h"
 #include "svdq_dispatch.h"
-#include "svdq_eig.h"
-#include <hip/hip_fp16.h>
-
-#define EIG_THREADS 256
-
-// Sum partial matrices [slot][nn] over slots [s0, s1) into out[nn] (LDS), fixed order:
-// wave w takes slots s0+w, s0+w+4, ... ; the four wave sums are then added 0+1+2+3.
-__device__ void reduce_partials(const double *__restrict__ part, int s0, int s1, int nn, double *red /*[4][1024]*/,
-                                double *out /*[nn]*/) {
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    for (int e = l; e < nn; e += 64) {
-        double a[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a[u] = 0.0;
-        int s = s0 + w;
-        for (; s + 28 < s1; s += 32) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a[u] += part[(size_t)(s + 4 * u) * nn + e];
-        }
-        for (; s < s1; s += 4) a[0] += part[(size_t)s * nn + e];
-        red[w * 1024 + e] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    }
-    __syncthreads();
-    for (int e = tid; e < nn; e += EIG_THREADS)
-        out[e] = (red[e] + red[1024 + e]) + (red[2048 + e] + red[3072 + e]);
-    __syncthreads();
-}
+#include "svdq_coeff.h"
 
 // First-level reduction, spread over the chip: chunk c of parameter p sums its share of the unit slots into
 // part2[(p*SVDQ_RC + c)][nn]; k_eig / k_coeff then only add SVDQ_RC partials per parameter.  Keeps the whole reduction
@@ -251,9 +225,6 @@ __global__ __launch_bounds__(THREADS) void k_eig(const SvdqParam *__restrict__ p
 }
 
 // ------------------------------------------------------------------------------------ epilogue
-__device__ __forceinline__ float f_min_nan(float a, float b) { return (a != a) ? a : ((b != b) ? b : (b < a ? b : a)); }
-__device__ __forceinline__ float f_max_nan(float a, float b) { return (a != a) ? a : ((b != b) ? b : (b > a ? b : a)); }
-
 __global__ __launch_bounds__(EIG_THREADS) void k_coeff(const SvdqParam *__restrict__ params, int NT, int pack,
                                                        int bits, int stages, const double *__restrict__ cpart,
                                                        const double *__restrict__ c0_in,
@@ -274,63 +245,8 @@ __global__ __launch_bounds__(EIG_THREADS) void k_coeff(const SvdqParam *__restri
     (void)pd;
     reduce_partials(cpart, p * SVDQ_RC, (p + 1) * SVDQ_RC, n * n, red, C);  // level-2 partials of k_reduce
 
-    const int k = k_in[p], r = r_in[p];
-    const int nl = r - k;
-    // c[t][i] fp32, c_high fp16 (round-to-nearest-even), zero padding past the valid prefix
-    for (int e = tid; e < n * n; e += EIG_THREADS) {
-        const int t = e / n, i = e % n;
-        const float cv = (float)(c0_in[(size_t)p * n * n + e] + C[e]);
-        coef_out[(size_t)p * n * n + e] = cv;
-        chigh_out[(size_t)p * n * n + e] = (i < k) ? __half_as_ushort(__float2half_rn(cv)) : (uint16_t)0;
-        if (i >= k && i < r) res[t * LDN + (i - k)] = cv;
-    }
-    __syncthreads();
-
-    if (tid < n) {
-        const int t = tid;
-        float *x = res + t * LDN;
-        const float qmax = (float)((1 << bits) - 1);
-        const size_t sbase = ((size_t)p * n + t) * stages;
-        for (int s = 0; s < stages; ++s) {
-            uint8_t *cdst = codes_out + (sbase + s) * n;
-            if (nl <= 0) {
-                for (int j = 0; j < n; ++j) cdst[j] = 0;
-                scale_out[sbase + s] = 0.f;
-                zp_out[sbase + s] = 0.f;
-                rnorm_out[sbase + s] = 0.f;
-                continue;
-            }
-            double ss = 0.0;
-            float mn = x[0], mx = x[0];
-            for (int j = 0; j < nl; ++j) {
-                ss += (double)x[j] * (double)x[j];
-                mn = f_min_nan(mn, x[j]);
-                mx = f_max_nan(mx, x[j]);
-            }
-            // rtvq.py:17-18: python-int / Tensor == Tensor.reciprocal() * int -> two roundings
-            const float range = __fsub_rn(mx, mn);
-            const float recip = __fdiv_rn(1.0f, range);
-            const float scale = __fmul_rn(recip, qmax);
-            const float zp = __fmul_rn(-1.0f, rintf(__fmul_rn(scale, mn)));
-            for (int j = 0; j < nl; ++j) {
-                float vq = rintf(__fadd_rn(__fmul_rn(scale, x[j]), zp));
-                uint8_t q;
-                if (vq != vq) {
-                    q = 0;
-                } else {
-                    vq = vq < 0.f ? 0.f : (vq > qmax ? qmax : vq);
-                    q = (uint8_t)vq;
-                }
-                cdst[j] = q;
-                const float deq = __fdiv_rn(__fsub_rn((float)q, zp), scale);
-                x[j] = __fsub_rn(x[j], deq);
-            }
-            for (int j = nl; j < n; ++j) cdst[j] = 0;
-            scale_out[sbase + s] = scale;
-            zp_out[sbase + s] = zp;
-            rnorm_out[sbase + s] = (float)sqrt(ss);
-        }
-    }
+    coeff_store_quantize(p, n, k_in[p], r_in[p], bits, stages, C, c0_in, nullptr, res, coef_out, chigh_out, codes_out,
+                         scale_out, zp_out, rnorm_out);
 }
 
 // ------------------------------------------------------------------------------------ launchers

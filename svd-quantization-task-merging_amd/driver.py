@@ -362,16 +362,10 @@ def run_basis_and_compress_from_checkpoints(base_state: Dict[str, torch.Tensor],
 _REGIONS = (("masked", "masked"), ("noise", "unmasked"))      # (key in a basis file, key in a task's artifact)
 
 
-def _adoptable(basis, artifacts) -> Optional[str]:
-    """Why the stored artifacts of ONE region of one parameter cannot be adopted into a plan (``adopt_artifacts``), or
-    None when they can.  ``basis``: the region's basis dictionary (U_high, U_low, k, mean, ...); ``artifacts``: the
-    region's artifact {c_high_fp16, c_low_quant} of every task that holds it, in plan order.  Reads shapes, dtypes and
-    scalars only -- no tensor data, no GPU."""
-    n = len(artifacts)
-    if n < 1:
-        return "no task holds the region"
-    if n > nat.MAX_TASKS:
-        return f"more than {nat.MAX_TASKS} tasks"
+def _basis_adoptable(basis, n: Optional[int] = None) -> Optional[str]:
+    """Why the stored BASIS of one region cannot go into a plan, or None when it can -- the basis half of ``_adoptable``,
+    and all of it for ``adopt_bases``.  ``n``: the tasks that hold the region (k + n_low may not exceed it), or None when
+    the plan's task count is still free (then the library's limit bounds k + n_low).  Shapes, dtypes and scalars only."""
     if not isinstance(basis, dict):
         return "the basis is not a dictionary"
     uh, ul, k = basis.get("U_high"), basis.get("U_low"), basis.get("k")
@@ -388,13 +382,34 @@ def _adoptable(basis, artifacts) -> Optional[str]:
         return "U_high.shape[1] != k"
     n_low = int(ul.shape[1])
     r = k + n_low
-    if r > min(D, n):
+    if n is None:
+        if r > min(D, nat.MAX_TASKS):
+            return f"k + n_low exceeds min(D, {nat.MAX_TASKS})"
+    elif r > min(D, n):
         return "k + n_low exceeds min(D, tasks that hold the region)"
     mean, sv = basis.get("mean"), basis.get("singular_values")
     if mean is not None and not (isinstance(mean, torch.Tensor) and mean.dtype is torch.float32 and mean.numel() == D):
         return "mean is not an fp32 tensor of D elements"
     if not (isinstance(sv, torch.Tensor) and sv.dim() == 1 and sv.is_floating_point()):
         return "singular_values is not a vector"
+    return None
+
+
+def _adoptable(basis, artifacts) -> Optional[str]:
+    """Why the stored artifacts of ONE region of one parameter cannot be adopted into a plan (``adopt_artifacts``), or
+    None when they can.  ``basis``: the region's basis dictionary (U_high, U_low, k, mean, ...); ``artifacts``: the
+    region's artifact {c_high_fp16, c_low_quant} of every task that holds it, in plan order.  Reads shapes, dtypes and
+    scalars only -- no tensor data, no GPU."""
+    n = len(artifacts)
+    if n < 1:
+        return "no task holds the region"
+    if n > nat.MAX_TASKS:
+        return f"more than {nat.MAX_TASKS} tasks"
+    why = _basis_adoptable(basis, n)
+    if why is not None:
+        return why
+    k, n_low = basis["k"], int(basis["U_low"].shape[1])
+    r = k + n_low
     bits = stages = None
     for a in artifacts:
         if not isinstance(a, dict):
@@ -430,16 +445,19 @@ def _adoptable(basis, artifacts) -> Optional[str]:
 
 
 def _adoption_groups(bases, compressed_all):
-    """The GPU-free half of ``adopt_artifacts``: which (parameter, region) pairs go into which plan.  Returns
+    """The GPU-free half of ``adopt_artifacts`` -- and, with ``compressed_all`` None, of ``adopt_bases``: the bases alone
+    are grouped, by (basis dtype, mean is None), entries without tasks or artifacts and ``bits`` None --: which
+    (parameter, region) pairs go into which plan.  Returns
     ``(groups, declined)``: groups = {(tasks present, num_stages, basis dtype, mean is None): [entry]} with entry =
     {name, region, art_key, basis, tasks, artifacts, bits}, in the dictionaries' order; declined = {name: reason}.  A
     parameter is adopted with ALL its regions or not at all (the batched consumers take both regions of a parameter
     from plans, or neither); a task that lacks a region is simply not among that entry's tasks, as in ``build_bases``."""
     groups: Dict[Tuple, List[dict]] = {}
     declined: Dict[str, str] = {}
+    basis_only = compressed_all is None
     for name, b in bases.items():
-        per_task = compressed_all.get(name)
-        if not isinstance(b, dict) or not isinstance(per_task, dict):
+        per_task = None if basis_only else compressed_all.get(name)
+        if not isinstance(b, dict) or not (basis_only or isinstance(per_task, dict)):
             declined[name] = "no basis / coefficient dictionaries"
             continue
         if isinstance(per_task, LazyArtifacts) and per_task._batch is not None:
@@ -452,6 +470,18 @@ def _adoption_groups(bases, compressed_all):
         for region, art_key in _REGIONS:
             rb = b.get(region)
             if rb is None:
+                continue
+            if basis_only:
+                try:
+                    why = _basis_adoptable(rb)
+                except Exception as exc:
+                    why = f"malformed ({type(exc).__name__})"
+                if why is not None:
+                    why = f"[{region}] {why}"
+                    break
+                found.append(((rb["U_high"].dtype, rb.get("mean") is None),
+                              {"name": name, "region": region, "art_key": art_key, "basis": rb, "tasks": [],
+                               "artifacts": [], "bits": None}))
                 continue
             present = [(t, a[art_key]) for t, a in per_task.items() if isinstance(a, dict) and a.get(art_key) is not None]
             try:
@@ -670,6 +700,100 @@ def adopted_mask_walk(batch, masks):
     return result
 
 
+def _adopt_plan(entries, N: int, S: int, udt, no_mean: bool, config, dev, masks, packed, bits, views=None,
+                input_dtype=torch.float32):
+    """One adopted plan -- shared by ``adopt_artifacts`` and ``adopt_bases``: a workspace-less ``CompressPlan`` over the
+    entries' rows, its small buffer packed from ``packed`` (``pack_small`` entries) and the entries' U_high / U_low /
+    mean copied into its packed buffers by ONE launch (svdq_plan_import).  Returns the ``BatchResult`` (mode "plain", no
+    table, nothing kept), or None when the library has no plan for the set (SVDQ_EINVAL): those parameters stay as they
+    came."""
+    P = len(entries)
+    try:
+        plan = CompressPlan([_planned_rows(e, masks) for e in entries], N,
+                            energy_threshold=config.svd_energy_threshold, max_rank=config.svd_max_rank,
+                            center=not no_mean, fp16=udt is torch.float16, low_bits=list(bits),
+                            rtvq_stages=S, device=dev, workspace=False, input_dtype=input_dtype)
+    except ValueError:
+        return None
+    small_host = pack_small(plan.layout, P, N, S, packed)
+    # the sources of the one copy launch; device copies of CPU tensors live until the end of this call only
+    uh = [_device_source(e["basis"]["U_high"], dev, udt) for e in entries]
+    ul = [_device_source(e["basis"]["U_low"], dev, udt) for e in entries]
+    mn = None if no_mean else [_device_source(e["basis"]["mean"].reshape(-1), dev, torch.float32) for e in entries]
+    plan.import_artifacts(uh, ul, mn, small_host)
+    del uh, ul, mn
+    small = small_views(small_host, plan.layout, P, N, S)
+    if views is not None:
+        small._host_views = views
+    batch = BatchResult(plan, small, [(e["name"], e["region"]) for e in entries], [e["tasks"] for e in entries])
+    batch.keep = None
+    batch.mode, batch.table, batch.rows_dev = "plain", None, None
+    batch.mask_table, batch.unit_start, batch.mask_ident = None, None, {}
+    batch.from_base, batch.task_gram, batch.adopted = False, None, True
+    batch.base_table, batch.sources = None, None
+    plan._keep = None
+    return batch
+
+
+def _bases_plan_specs(bases, n_slots: int):
+    """The GPU-free half of ``adopt_bases``: ``(specs, declined)`` with one spec per plan, {udt, no_mean, N, entries} --
+    the groups of ``_adoption_groups`` over the bases alone, each with N = max(n_slots, the largest stored r of the
+    group), so that r <= N holds for every entry and every plan has room for ``n_slots`` task slots."""
+    n_slots = int(n_slots)
+    if not 1 <= n_slots <= nat.MAX_TASKS:
+        raise ValueError(f"n_slots must be in [1, {nat.MAX_TASKS}], got {n_slots}")
+    groups, declined = _adoption_groups(bases, None)
+    specs = []
+    for (udt, no_mean), entries in groups.items():
+        r_max = max(int(e["basis"]["k"]) + int(e["basis"]["U_low"].shape[1]) for e in entries)
+        specs.append({"udt": udt, "no_mean": no_mean, "N": max(n_slots, r_max), "entries": entries})
+    return specs, declined
+
+
+def adopt_bases(bases: Dict[str, Dict], config, n_slots: int, device="cuda",
+                masks: Optional[Dict[str, torch.Tensor]] = None, input_dtype=torch.float32):
+    """Adoption of BASES only: stored bases -- loaded from disk, a caller's own U -- go into plans that have room for
+    ``n_slots`` new tasks, ready for ``CompressPlan.project_tasks`` (svdq_plan_project).  The groups and plans are
+    ``adopt_artifacts``' (same code), without the task count in the key: one plan per (basis dtype, mean is None) with
+    N = max(n_slots, the largest stored r in the group) task slots, num_stages and the code widths from ``config``
+    (``svd_low_bits_by_param`` respected).  U_high / U_low / mean / sigma / k / r / energy are imported, the coefficient
+    fields are zero.  ``masks``: as for ``adopt_artifacts``; ``input_dtype``: the dtype the plans read task tensors in.
+    Returns ``(batches, declined)``: the ``BatchResult`` of every plan (``entries`` = [(name, region)], in the
+    dictionaries' order) and {name: reason} for what a plan cannot express -- those parameters stay with the
+    per-parameter route.  Adoption never raises on data."""
+    import numpy as np
+    dev = resolve_device(device)
+    specs, declined = _bases_plan_specs(bases, n_slots)
+    S = int(config.svd_rtvq_stages)
+    by_param = getattr(config, "svd_low_bits_by_param", None)
+    batches = []
+    for spec in specs:
+        entries, N = spec["entries"], spec["N"]
+        sig = _host_arrays([e["basis"]["singular_values"] for e in entries])
+        packed, bits = [], []
+        for e, sv in zip(entries, sig):
+            b = e["basis"]
+            k, n_low = int(b["k"]), int(b["U_low"].shape[1])
+            r = k + n_low
+            sigma = np.zeros(r, dtype=np.float32)
+            sv = np.asarray(sv, dtype=np.float32).reshape(-1)
+            sigma[:min(sv.size, r)] = sv[:r]
+            packed.append({"rows": int(b["U_high"].shape[0]), "k": k, "r": r, "energy": b.get("energy_retained", 0.0),
+                           "sigma": sigma, "c_high": np.zeros((N, k), dtype=np.float16),
+                           "codes": np.zeros((N, S, n_low), dtype=np.uint8),
+                           "scale": np.zeros((N, S), dtype=np.float32), "zero_point": np.zeros((N, S), dtype=np.float32),
+                           "residual_norm": np.zeros((N, S), dtype=np.float32)})
+            bits.append(int(by_param(e["name"])) if by_param is not None else int(config.svd_low_bits))
+        batch = _adopt_plan(entries, N, S, spec["udt"], spec["no_mean"], config, dev, masks, packed, bits,
+                            input_dtype=input_dtype)
+        if batch is None:
+            for e in entries:
+                declined.setdefault(e["name"], "the library has no plan for this set")
+            continue
+        batches.append(batch)
+    return batches, declined
+
+
 def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], config, device="cuda",
                     masks: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[Dict[str, Dict], Dict[str, Dict]]:
     """Put artifacts that did NOT come out of a fused run in this process -- the reference-layout dictionaries
@@ -707,31 +831,11 @@ def adopt_artifacts(bases: Dict[str, Dict], compressed_all: Dict[str, Dict], con
     new_comp = dict(compressed_all)
     where: Dict[Tuple[str, str], Tuple[BatchResult, int]] = {}
     for (n_tasks, stages, udt, no_mean), entries in groups.items():
-        P, N, S = len(entries), n_tasks, stages
-        try:
-            plan = CompressPlan([_planned_rows(e, masks) for e in entries], N,
-                                energy_threshold=config.svd_energy_threshold, max_rank=config.svd_max_rank,
-                                center=not no_mean, fp16=udt is torch.float16, low_bits=[e["bits"] for e in entries],
-                                rtvq_stages=S, device=dev, workspace=False)
-        except ValueError:      # a set the library has no plan for (SVDQ_EINVAL): these parameters stay as they came
+        batch = _adopt_plan(entries, n_tasks, stages, udt, no_mean, config, dev, masks,
+                            _gather_small(entries, n_tasks, stages), [e["bits"] for e in entries],
+                            views=_AdoptedViews([e["artifacts"] for e in entries]))
+        if batch is None:
             continue
-        packed = _gather_small(entries, N, S)
-        small_host = pack_small(plan.layout, P, N, S, packed)
-        # the sources of the one copy launch; device copies of CPU tensors live until the end of this iteration only
-        uh = [_device_source(e["basis"]["U_high"], dev, udt) for e in entries]
-        ul = [_device_source(e["basis"]["U_low"], dev, udt) for e in entries]
-        mn = None if no_mean else [_device_source(e["basis"]["mean"].reshape(-1), dev, torch.float32) for e in entries]
-        plan.import_artifacts(uh, ul, mn, small_host)
-        del uh, ul, mn
-        small = small_views(small_host, plan.layout, P, N, S)
-        small._host_views = _AdoptedViews([e["artifacts"] for e in entries])
-        batch = BatchResult(plan, small, [(e["name"], e["region"]) for e in entries], [e["tasks"] for e in entries])
-        batch.keep = None
-        batch.mode, batch.table, batch.rows_dev = "plain", None, None
-        batch.mask_table, batch.unit_start, batch.mask_ident = None, None, {}
-        batch.from_base, batch.task_gram, batch.adopted = False, None, True
-        batch.base_table, batch.sources = None, None
-        plan._keep = None
         for i, e in enumerate(entries):
             where[(e["name"], e["region"])] = (batch, i)
     for (name, region), (batch, i) in where.items():

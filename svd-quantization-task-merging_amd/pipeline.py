@@ -460,6 +460,41 @@ class CompressPlan:
                       "svdq_plan_import")
         self._typed = None
 
+    # ---- new tasks onto the basis the plan holds (svdq_plan_project.hip)
+    def project_tasks(self, table: torch.Tensor, base_table: Optional[torch.Tensor] = None,
+                      index_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None,
+                      fetch: bool = True) -> Optional[SmallArtifacts]:
+        """Project task tensors onto the basis this plan already holds -- from a compress run or from
+        ``import_artifacts`` -- and quantize their coefficients, in two launches (svdq_plan_project).  ``table``: int64
+        device tensor [P * N] (parameter-major) of task tensors in the plan's input dtype, 0 = the slot is absent and
+        its fields of the small buffer stay as they are.  ``base_table``: int64 [P] base tensors -- the task tensors are
+        then fine-tuned weights.  ``index_table``: int64 [P] int32 index lists (MaskSet.indices) -- the tables then name
+        full-size tensors.  ``rows_dev``: int64 [P] rows per parameter.  The basis, mean, sigma, k, r, energy and rows
+        of the plan are only read.  Returns the small views (one device-to-host copy, which synchronises);
+        ``fetch=False`` enqueues only and returns None."""
+        who = "svdq_plan_project"
+        if self.basis is None:
+            raise ValueError(f"{who}: a gram_only plan has no basis to project onto")
+        for what, t, need in (("table", table, self.P * self.N), ("base_table", base_table, self.P),
+                              ("index_table", index_table, self.P), ("rows_dev", rows_dev, self.P)):
+            if t is None:
+                if what == "table":
+                    raise ValueError(f"{who}: the task pointer table is required")
+                continue
+            if t.dtype is not torch.int64 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{who}: {what} must be a contiguous int64 tensor on {self.device}")
+            if t.numel() != need:
+                raise ValueError(f"{who}: {what} needs {need} entries, got {t.numel()}")
+        work = getattr(self, "_project_work", None)
+        need = int(self.lib.svdq_plan_project_work_bytes(self._h))
+        if work is None or work.numel() < need:
+            work = self._project_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.svdq_plan_project(self._h, _ptr(table), _ptr(base_table), _ptr(index_table), _ptr(rows_dev),
+                                                 _ptr(self.basis), _ptr(self.mean), _ptr(self.small), _ptr(work),
+                                                 _stream_ptr()), who)
+            return self.fetch_small() if fetch else None
+
     # ---- consumers of the artifacts, batched over the plan (svdq_merge.hip)
     def new_merged_outputs(self):
         """One packed fp32 buffer for the merged rows of every parameter (64-float aligned slices), its offsets and its

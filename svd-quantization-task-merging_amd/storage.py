@@ -261,6 +261,75 @@ def reconstruct_tasks_from_artifacts_masked(artifact_dir: str, base_state_dict, 
     return out
 
 
+def _stored_tasks(compressed: Dict[str, Dict], diagnostics: Dict[str, Any]) -> list:
+    """The task names a store holds, in the order of its weights, then of first appearance in the coefficient files."""
+    tasks = list((diagnostics.get("task_weights") or {}).keys())
+    for per_task in compressed.values():
+        for t in per_task:
+            if t not in tasks:
+                tasks.append(t)
+    return tasks
+
+
+def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[str, Any],
+                           masks: Optional[Dict[str, torch.Tensor]] = None, output_dir: str = None,
+                           weights: Optional[Dict[str, float]] = None, device: str = "cuda") -> Dict[str, Any]:
+    """Add NEW fine-tuned models to a stored artifact set: each is projected onto the bases already stored, its
+    coefficients are quantized and it joins the per-parameter coefficient dictionaries -- compress_all_parameters
+    (reference compress.py:173-207) for the new tasks alone.  The other tasks' checkpoints are not needed and no basis is
+    recomputed.  load_all_artifacts -> compress.project_all_parameters (one svdq_plan_project per plan, finetuned - base
+    formed inside the launch: no task vectors are materialised) -> the existing writers.
+
+    ``base_state_dict`` / the values of ``finetuned`` ({task: checkpoint}): state dicts or paths of them.  ``masks``:
+    the combined masks the store was compressed with ({parameter: mask}; masks are not stored, reload.py:204-205).
+    ``weights``: {task: weight} over ALL tasks, old and new, for ``diagnostics["task_weights"]``; None = uniform over all.
+    ``output_dir``: None or the artifact directory itself = in place, and then only the coefficient files and
+    diagnostics.json are rewritten; any other directory receives the whole store.
+    A task name the store already holds, or more than 32 tasks in total, is a ``ValueError`` before anything is read
+    from the checkpoints.  Returns {"tasks", "added", "compressed" (the new tasks' artifacts), "output_dir"}."""
+    from . import _native as nat
+    from .compress import project_all_parameters
+    art = load_all_artifacts(artifact_dir, device="cpu")
+    config, diagnostics, bases, compressed = art["config"], art["diagnostics"], art["bases"], art["compressed"]
+    old = _stored_tasks(compressed, diagnostics)
+    new = list(finetuned.keys())
+    if not new:
+        raise ValueError("no checkpoint to add")
+    for t in new:
+        if t in old:
+            raise ValueError(f"task {t!r} is already in the artifacts, which hold {old}")
+    if len(old) + len(new) > nat.MAX_TASKS:
+        raise ValueError(f"{len(old)} stored + {len(new)} new tasks: at most {nat.MAX_TASKS} tasks in total")
+    tasks = old + new
+    if weights is not None:
+        lacking = [t for t in tasks if t not in weights]
+        if lacking:
+            raise ValueError(f"weights lack task {lacking[0]!r}: they must cover all {len(tasks)} tasks")
+        task_weights = {t: float(weights[t]) for t in tasks}
+    else:
+        task_weights = {t: 1.0 / len(tasks) for t in tasks}
+    base = _load_base(base_state_dict, device)
+    models = {}
+    for t, ckpt in finetuned.items():
+        sd = _load_base(ckpt, device)
+        models[t] = {n: sd[n] for n in bases if n in sd and n in base}
+    added = project_all_parameters(models, masks or {}, bases, config, device=device,
+                                   base_state_dict={n: base[n] for n in bases if n in base})
+    touched = {}
+    for name, per_task in added.items():
+        merged = dict(compressed.get(name, {}))
+        merged.update(per_task)
+        compressed[name] = touched[name] = merged
+    diagnostics["task_weights"] = task_weights
+    out = output_dir or artifact_dir
+    if os.path.realpath(out) == os.path.realpath(artifact_dir):
+        save_compressed_coefficients(touched, out)
+        save_diagnostics(diagnostics, out)
+    else:
+        save_all_artifacts(bases, compressed, diagnostics, config, out)
+    return {"tasks": tasks, "added": new, "compressed": added, "output_dir": out}
+
+
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
     """Reference reload.py:60-139: a pre-saved merged_state_dict.pt in the artifact directory wins; otherwise the
     merged model is rebuilt from bases + coefficients + the base model named in the stored config."""
