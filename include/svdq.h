@@ -690,6 +690,84 @@ int svdq_plan_project(const svdq_plan *plan, const void *task_ptrs_dev /*[P*N]; 
                       const int64_t *rows_dev, const void *basis_dev, const float *mean_dev, void *small_dev,
                       void *work_dev, void *stream);
 
+/* ---- extend the basis a plan holds by what NEW tasks add outside its span (the one statement of the contract; the
+ *      sources point here).  No reference counterpart: the reference never adds a task to a store.  svdq_plan_project
+ *      projects a new task onto the stored columns and drops what lies outside their span -- for a new fine-tuned model
+ *      against r <= 32 stored directions that is nearly all of it.  These two entry points grow the stored U_high by the
+ *      orthonormal directions of the new tasks' residuals, without any other task's checkpoint and without touching a
+ *      stored column.  Call order per plan: svdq_plan_project (leaves the fp32 coefficients coef in small_dev) ->
+ *      svdq_plan_residual_gram -> the host reads the m values (ONE small device-to-host copy of the extension buffer, to
+ *      allocate the outputs) -> svdq_plan_extend_basis.  The two entry points themselves allocate nothing, copy nothing
+ *      to the host and synchronise nothing.
+ *   inputs          task_ptrs_dev, base_ptrs_dev, index_ptrs_dev, rows_dev, basis_dev, mean_dev: exactly as for
+ *                   svdq_plan_project, and the same tensors.  small_dev is ONLY READ: k, r and coef[p][t][0..r), the fp32
+ *                   coefficients svdq_plan_project has just left there (not the rounded or quantized ones).
+ *   n_new           the new tasks sit in task slots [0, n_new), 1 <= n_new <= SVDQ_MAX_NEW_TASKS (8) and n_new <= N; a NULL
+ *                   entry of task_ptrs_dev = the slot is absent for that parameter.  Slots >= n_new are never read.
+ *   per entry p     with U = [U_high | U_low] [D, r] as stored, xc_j = x_j - mean (formed exactly as svdq_plan_project forms
+ *                   it) and c_j = coef[p][j]:
+ *     residual      e_j[d] = fma(-u[d][r-1], c_j[r-1], ... fma(-u[d][0], c_j[0], xc_j[d])), u = float(U[d][i]): one fp32 fma
+ *                   chain in column order, U_high columns then U_low.  ONE device function serves both passes: the same
+ *                   bits.  By construction xc_j = U c_j + e_j whether or not the rounded U is orthonormal.
+ *     Gram          H = E^T E [n_new, n_new], n_j = |xc_j|^2 (and |e_j|^2 = H[j][j]).  fp32 inside one block of at most
+ *                   256 rows (the matrix pipe's chain, v_mfma_f32_16x16x4f32; n_j: an fma chain over the lane's rows, then
+ *                   the 64 lane sums in lane order), fp64 across blocks and work units in a fixed order, no atomics: the
+ *                   same bits in every run.  H is NOT formed from Xc^T Xc - 2 C^T C + ...: that cancels exactly when a task
+ *                   lies almost in the span, the case the threshold has to judge.
+ *     eigen stage   H = W L W^T in fp64 (the Jacobi of the compressor's eigen stage) over the PRESENT slots, lambda
+ *                   descending, each eigenvector's sign fixed so that its largest-magnitude component is positive.
+ *                   Direction i is kept iff lambda_i > min_residual^2 * max_j n_j and i < min(present slots, D - r);
+ *                   m = the number kept.  Z = W[:, :m] L^-1/2 [slot][column] and d_j = (L^1/2 W^T)[:m, j], task j's
+ *                   coefficients on the new columns, both fp32 (absent slots: zeros).
+ *     min_residual  relative to the largest |xc_j|.  Default 2^-12: the worst-case fp32 noise of the residual relative to
+ *                   |xc| is about (r + 2) 2^-24 sqrt(r) <= 1.2e-5 at r = 32, 16 x or more below the threshold, and the
+ *                   threshold is far below what a 4-bit c_low resolves.  Must be finite and >= 0.
+ *   non-finite data a NaN or +-Inf among the rows of a present slot makes that slot's n_j NaN or +Inf (a sum of squares; so does
+ *                   finite data whose squares overflow fp32).  The eigen stage then decomposes nothing: m = 0, lambda, Z
+ *                   and d are zeros, the entry is not extended, and n_j in ext_dev is the flag -- every healthy n_j is finite.
+ *                   CompressPlan.residual_gram raises NonFiniteInput on it, as the compress route does on a NaN energy.
+ *   ext_dev         svdq_plan_extend_layout bytes, 16-byte aligned; every field of every parameter is written by
+ *                   svdq_plan_residual_gram (rows = 0: zeros), so the buffer is the same bytes in every run.
+ *   work_dev        svdq_plan_residual_gram_work_bytes bytes: per work unit one fp64 [8][8] partial of H and [8] of n.
+ *   svdq_plan_extend_basis   the same walk again: e recomputed by the same device function, q[d][c] = sum_j e_j[d] Z[j][c]
+ *                   as an fp32 fma chain from 0 over j in slot order, and row d of out_ptrs_dev[p] -- the caller's U_high'
+ *                   [D, k + m] row-major in the basis element type -- = the k stored U_high elements of the row, copied bit
+ *                   for bit, then the m new ones rounded to the element type (fp16: round to nearest even).  m is read from
+ *                   ext_dev ON THE DEVICE.  A parameter with m = 0, rows = 0 or a NULL out_ptrs_dev[p] is not written at
+ *                   all, and nothing is written past D (k + m) elements.  out tensors: 16-byte aligned (caller's contract).
+ *   the extended entry   U_high' = [U_high | Q], U_low unchanged, k' = k + m.  Old tasks: c_high' = [c_high, 0 ... 0]
+ *                   (fp16 holds their zeros exactly; an affine RTVQ code has no exact zero -- hence the high side), c_low
+ *                   untouched.  New tasks: c_high' = fp16([coef[:k], d_j]), c_low as svdq_plan_project quantized it.
+ *                   singular_values' = [sigma[:k], sqrt(lambda[:m]), sigma[k:]] -- no longer globally descending; its
+ *                   first k' entries are still the high columns.  This bookkeeping is the host's (compress.extend_bases).
+ *   launches        svdq_plan_residual_gram: the streaming launch over the plan's own work units (one wavefront each) and
+ *                   the eigen launch (one workgroup per parameter).  svdq_plan_extend_basis: one streaming launch.
+ *   errors          SVDQ_EINVAL before anything is launched: a NULL plan, task_ptrs_dev, basis_dev, small_dev, ext_dev,
+ *                   work_dev or out_ptrs_dev; a NULL mean_dev on a centred plan; tables, rows or work off 8 bytes; small,
+ *                   basis, mean or ext off 16; n_new outside [1, min(8, N)]; min_residual negative or not finite.
+ *   Any N <= SVDQ_MAX_TASKS plan slots (the 8-, 16- and 32-slot instantiations), fp16 or fp32 basis, every input form of
+ *   svdq_plan_project (from-base, index lists, fp16 / bf16 inputs). */
+#define SVDQ_MAX_NEW_TASKS 8
+typedef struct svdq_extend_layout {
+    int64_t m_off;          /* int32  [P]        new columns kept                                          */
+    int64_t lambda_off;     /* double [P][8]     eigenvalues of H over the present slots, descending       */
+    int64_t z_off;          /* float  [P][8][8]  Z[slot][column], first m columns valid                    */
+    int64_t d_off;          /* float  [P][8][8]  d[slot][column]: the slot's coefficients on the new columns */
+    int64_t xnorm_off;      /* double [P][8]     n_j = |xc_j|^2                                            */
+    int64_t enorm_off;      /* double [P][8]     |e_j|^2 = H[j][j]                                         */
+    int64_t total_bytes;
+} svdq_extend_layout;
+int64_t svdq_plan_residual_gram_work_bytes(const svdq_plan *plan);
+int svdq_plan_extend_layout(const svdq_plan *plan, svdq_extend_layout *out);
+int svdq_plan_residual_gram(const svdq_plan *plan, const void *task_ptrs_dev /*[P*N]; NULL entry = slot absent*/,
+                            const void *base_ptrs_dev /*NULL or [P]*/, const void *index_ptrs_dev /*NULL or [P]*/,
+                            const int64_t *rows_dev, const void *basis_dev, const float *mean_dev, const void *small_dev,
+                            int32_t n_new, float min_residual, void *ext_dev, void *work_dev, void *stream);
+int svdq_plan_extend_basis(const svdq_plan *plan, const void *task_ptrs_dev, const void *base_ptrs_dev,
+                           const void *index_ptrs_dev, const int64_t *rows_dev, const void *basis_dev,
+                           const float *mean_dev, const void *small_dev, int32_t n_new, const void *ext_dev,
+                           const void *out_ptrs_dev /*[P] U_high' [D, k + m]; NULL entry = not written*/, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

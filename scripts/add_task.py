@@ -2,7 +2,8 @@
 """Add new fine-tuned checkpoints to a stored artifact set: each is projected onto the bases already stored
 (project_to_basis compress.py:6-21 inside compress_all_parameters compress.py:173-207, for the new tasks alone), its
 coefficients are quantized and written beside the other tasks'.  The other tasks' checkpoints are not needed and no basis
-is recomputed; afterwards load_and_merge.py / reconstruct_tasks.py see one more task.
+is recomputed; afterwards load_and_merge.py / reconstruct_tasks.py see one more task.  --extend-basis also grows the
+stored bases by the directions the new tasks add outside their span (storage.add_tasks_to_artifacts).
 
 A store that was compressed through masks needs the mask directory the run had (--mask-dir): masks are not stored
 (reload.py:204-205)."""
@@ -26,6 +27,12 @@ def build_parser():
     ap.add_argument("--weights-json", default=None,
                     help="JSON file {task: weight} over ALL tasks, old and new (default: uniform)")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--extend-basis", action="store_true",
+                    help="also grow the stored bases by the directions the new tasks add outside their span "
+                         "(1 to 8 new tasks; without it a new task reconstructs little more than the stored mean)")
+    ap.add_argument("--min-residual", type=float, default=2.0 ** -12,
+                    help="with --extend-basis: keep a residual direction whose norm exceeds this share of the largest "
+                         "centred task norm (default 2^-12)")
     return ap
 
 
@@ -62,9 +69,13 @@ def main(argv=None):
         base = _load_base(args.base_model_path, args.device)
         masks = load_combined_masks(args.artifact_dir, base, args.mask_dir, None, args.device)
     res = add_tasks_to_artifacts(args.artifact_dir, base, checkpoints, masks=masks, output_dir=args.output_dir,
-                                 weights=weights, device=args.device)
+                                 weights=weights, device=args.device, extend_basis=args.extend_basis,
+                                 min_residual=args.min_residual)
     print(f"added {res['added']} -> {res['output_dir']}: {len(res['tasks'])} tasks, "
           f"{len(res['compressed'])} parameters projected")
+    if args.extend_basis:
+        print(f"new basis columns: {sum(res['columns'].values())} over {len(res['columns'])} entries; energy the stored "
+              f"columns captured: " + ", ".join(f"{t} {e:.4f}" for t, e in res["captured_energy"].items()))
     return 0
 
 

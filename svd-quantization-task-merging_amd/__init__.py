@@ -16,7 +16,7 @@ from .rtvq import (RTVQQuantizer, asymmetric_quantization, asymmetric_dequantiza
 from .basis import (construct_basis, construct_masked_basis, select_rank, compute_energy_spectrum, compute_svd,
                     stack_and_center, compute_energy_statistics)
 from .compress import (project_to_basis, compress_single_task, compress_masked_regions, compress_parameter,
-                       compress_all_parameters, project_all_parameters)
+                       compress_all_parameters, project_all_parameters, extend_bases)
 from .mask_loader import (combine_masks, compute_union_mask, compute_intersection_mask, compute_majority_mask,
                           apply_mask_to_tensor, get_unmasked_portion, reconstruct_from_masked, load_task_masks,
                           load_single_mask, load_tall_mask_file, state_dict_to_vector, vector_to_state_dict,

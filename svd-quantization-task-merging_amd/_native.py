@@ -39,6 +39,14 @@ class SvdqSmallLayout(Structure):
                                        "coef_off", "status_off", "total_bytes")]
 
 
+class SvdqExtendLayout(Structure):
+    _fields_ = [(n, c_int64) for n in ("m_off", "lambda_off", "z_off", "d_off", "xnorm_off", "enorm_off",
+                                       "total_bytes")]
+
+
+MAX_NEW_TASKS = 8      # SVDQ_MAX_NEW_TASKS: new tasks per svdq_plan_residual_gram / svdq_plan_extend_basis call
+
+
 # name -> (restype, argtypes); mirrors include/svdq.h one to one (tests check the export list)
 SIGNATURES = {
     "svdq_abi_version": (c_int32, []),
@@ -143,6 +151,12 @@ SIGNATURES = {
     "svdq_plan_project_work_bytes": (c_int64, [c_void_p]),
     "svdq_plan_project": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+    "svdq_plan_residual_gram_work_bytes": (c_int64, [c_void_p]),
+    "svdq_plan_extend_layout": (c_int32, [c_void_p, POINTER(SvdqExtendLayout)]),
+    "svdq_plan_residual_gram": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "svdq_plan_extend_basis": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int32, c_void_p, c_void_p, c_void_p]),
     "svdq_mask_expand": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "svdq_hbm_probe": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
 }

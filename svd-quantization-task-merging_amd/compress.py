@@ -155,34 +155,16 @@ def compress_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], ma
     return out
 
 
-def project_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], masks: Optional[Dict[str, torch.Tensor]],
-                           bases: Dict[str, Dict], config, device: str = "cuda",
-                           base_state_dict: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Dict]:
-    """``compress_all_parameters`` for NEW tasks against bases that already exist -- loaded from disk, adopted, a
-    caller's own U -- in one ``svdq_plan_project`` per plan instead of a selection, a projection launch pair, a
-    device-to-host copy and a quantizer call per (parameter, region, task).  Returns exactly the dictionary layout
-    ``compress_all_parameters`` returns: {param: {task: {"masked": {...}, "unmasked": ... | None}}}, CPU tensors.
-
-    ``task_vectors``: {task: {param: tensor}}, up to 32 tasks; with ``base_state_dict`` they hold FINE-TUNED weights and
-    finetuned - base is formed inside the launch (no task vectors in memory).  Tensors that are all fp16 or all bf16
-    (base included) are read as they are.  A masked parameter (``masks[name]`` of the tensor's shape) is read through
-    index lists built once per parameter (svdq_maskset_indices); its noise region, when ``config.svd_include_noise``,
-    through the inverted list against ``bases[name]["noise"]``.  A selected count that differs from the stored D raises a
-    ``ValueError`` naming the parameter.  What ``adopt_bases`` declines -- and a parameter whose mask selects fewer than
-    ``svd_min_mask_size`` elements -- goes through ``compress_parameter``, unchanged (there ``task_vectors`` must hold
-    task vectors: with ``base_state_dict`` the difference is formed first, for those parameters only)."""
-    import gc
-    from . import mask_loader as ml
+def _projection_setup(task_vectors, masks, bases, config, device, base_state_dict, who: str):
+    """What ``project_all_parameters`` and ``extend_bases`` decide before any plan runs: the task order, the parameters
+    the new tasks hold, which masks apply, the input dtype, and the adoption of the bases into plans."""
     from .driver import adopt_bases
-    from .pipeline import native_input_dtype, prepare_input, task_artifact
+    from .pipeline import native_input_dtype
     masks = masks or {}
     tasks = list(task_vectors.keys())
-    if not tasks:
-        return {}
     if len(tasks) > nat.MAX_TASKS:
-        raise ValueError(f"project_all_parameters takes at most {nat.MAX_TASKS} tasks per call, got {len(tasks)}")
+        raise ValueError(f"{who} takes at most {nat.MAX_TASKS} tasks per call, got {len(tasks)}")
     dev = resolve_device(device)
-    include_noise = bool(config.svd_include_noise)
 
     def usable_mask(name):
         """The mask as compress_parameter applies it: only when its shape is the tensors' shape."""
@@ -205,76 +187,137 @@ def project_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], mas
         covered += [base_state_dict[n] for n in batched_bases]
     in_dtype = native_input_dtype(covered)
     batches, declined = adopt_bases(batched_bases, config, len(tasks), device=dev, input_dtype=in_dtype)
+    return {"masks": masks, "tasks": tasks, "dev": dev, "names": names, "mask_of": mask_of, "small_mask": small_mask,
+            "in_dtype": in_dtype, "batches": batches, "declined": declined,
+            "include_noise": bool(config.svd_include_noise)}
+
+
+def _plan_tables(batch, setup, task_vectors, base_state_dict):
+    """The device tables of one adopted plan for ``CompressPlan.project_tasks`` (and the extension entry points, which
+    take the same ones): {"table", "base_table", "index_table", "rows_dev", "active", "keep"}.  ``active[i]``: entry i of
+    the plan is projected; ``keep``: the owners of the raw addresses in the tables."""
+    from . import mask_loader as ml
+    from .pipeline import prepare_input
+    tasks, dev, mask_of, in_dtype = setup["tasks"], setup["dev"], setup["mask_of"], setup["in_dtype"]
+    include_noise = setup["include_noise"]
+    plan = batch.plan
+    P, N = plan.P, plan.N
+    stored = [int(r) for r in batch.small.rows]
+    # index lists, once per masked parameter of the plan
+    mnames = []
+    for name, _ in batch.entries:
+        if mask_of[name] is not None and name not in mnames:
+            mnames.append(name)
+    idx_true = idx_false = {}
+    ms = None
+    if mnames:
+        ms = ml.MaskSet([int(mask_of[n].numel()) for n in mnames], dev)
+        it, if_, ct, cf = ms.indices([mask_of[n] for n in mnames], include_noise)
+        counts = torch.stack([ct, cf if cf is not None else torch.zeros_like(ct)]).cpu().tolist()
+        idx_true = {n: (it[q], counts[0][q]) for q, n in enumerate(mnames)}
+        idx_false = {n: (if_[q], counts[1][q]) for q, n in enumerate(mnames)} if include_noise else {}
+    keep, tab, btab, itab, active = [], [0] * (P * N), [0] * P, [0] * P, [False] * P
+    for i, (name, region) in enumerate(batch.entries):
+        if region == "noise" and not include_noise:
+            continue      # compress_parameter hands no noise basis on: "unmasked" stays None
+        m = mask_of[name]
+        if region == "noise" and m is None:
+            continue      # no mask, no noise region (compress.py:150-152)
+        numel = None
+        for t, task in enumerate(tasks):
+            x = task_vectors[task].get(name)
+            if x is None:
+                continue
+            v = prepare_input(x, dev, in_dtype)
+            numel = v.numel()
+            keep.append(v)
+            tab[i * N + t] = v.data_ptr()
+        if m is not None:
+            lst, count = (idx_false if region == "noise" else idx_true)[name]
+            keep.append(lst)
+            itab[i] = lst.data_ptr()
+        else:
+            count = numel
+        if count != stored[i]:
+            raise ValueError(f"parameter {name!r} [{region}]: {count} selected elements, the stored basis "
+                             f"has D = {stored[i]}")
+        if base_state_dict is not None:
+            b = prepare_input(base_state_dict[name], dev, in_dtype)
+            if b.numel() != numel:
+                raise ValueError(f"parameter {name!r}: the base tensor has {b.numel()} elements, the "
+                                 f"task tensors {numel}")
+            keep.append(b)
+            btab[i] = b.data_ptr()
+        active[i] = True
+    has_idx = any(itab)
+    if has_idx:
+        # a plan mixes masked and unmasked entries: an unmasked one reads through the identity list
+        for i, (name, region) in enumerate(batch.entries):
+            if active[i] and not itab[i]:
+                ident = torch.arange(stored[i], dtype=torch.int32, device=dev)
+                keep.append(ident)
+                itab[i] = ident.data_ptr()
+    rows_dev = torch.tensor([stored[i] if active[i] else 0 for i in range(P)], dtype=torch.int64).to(dev)
+    table = torch.tensor(tab, dtype=torch.int64).to(dev)
+    base_table = torch.tensor(btab, dtype=torch.int64).to(dev) if base_state_dict is not None else None
+    index_table = torch.tensor(itab, dtype=torch.int64).to(dev) if has_idx else None
+    keep.append(ms)
+    return {"table": table, "base_table": base_table, "index_table": index_table, "rows_dev": rows_dev,
+            "active": active, "keep": keep}
+
+
+def _per_parameter_rest(rest, out, task_vectors, setup, bases, config, device, base_state_dict):
+    """The per-parameter route (``compress_parameter``) for whatever did not go into a plan."""
+    dev, masks = setup["dev"], setup["masks"]
+    quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
+    for name in rest:
+        tv = task_vectors
+        if base_state_dict is not None:
+            b = base_state_dict[name]
+            tv = {t: {name: (v[name].to(dev).float() - b.to(dev).float())} for t, v in task_vectors.items()
+                  if name in v}
+        comp = compress_parameter(name, tv, masks.get(name), bases[name], quantizer,
+                                  include_noise=setup["include_noise"], min_mask_size=config.svd_min_mask_size,
+                                  device=device)
+        if comp is not None:
+            out[name] = comp
+
+
+def project_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], masks: Optional[Dict[str, torch.Tensor]],
+                           bases: Dict[str, Dict], config, device: str = "cuda",
+                           base_state_dict: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Dict]:
+    """``compress_all_parameters`` for NEW tasks against bases that already exist -- loaded from disk, adopted, a
+    caller's own U -- in one ``svdq_plan_project`` per plan instead of a selection, a projection launch pair, a
+    device-to-host copy and a quantizer call per (parameter, region, task).  Returns exactly the dictionary layout
+    ``compress_all_parameters`` returns: {param: {task: {"masked": {...}, "unmasked": ... | None}}}, CPU tensors.
+
+    ``task_vectors``: {task: {param: tensor}}, up to 32 tasks; with ``base_state_dict`` they hold FINE-TUNED weights and
+    finetuned - base is formed inside the launch (no task vectors in memory).  Tensors that are all fp16 or all bf16
+    (base included) are read as they are.  A masked parameter (``masks[name]`` of the tensor's shape) is read through
+    index lists built once per parameter (svdq_maskset_indices); its noise region, when ``config.svd_include_noise``,
+    through the inverted list against ``bases[name]["noise"]``.  A selected count that differs from the stored D raises a
+    ``ValueError`` naming the parameter.  What ``adopt_bases`` declines -- and a parameter whose mask selects fewer than
+    ``svd_min_mask_size`` elements -- goes through ``compress_parameter``, unchanged (there ``task_vectors`` must hold
+    task vectors: with ``base_state_dict`` the difference is formed first, for those parameters only)."""
+    import gc
+    from .pipeline import task_artifact
+    if not task_vectors:
+        return {}
+    setup = _projection_setup(task_vectors, masks, bases, config, device, base_state_dict, "project_all_parameters")
+    tasks, dev = setup["tasks"], setup["dev"]
 
     out: Dict[str, Dict] = {}
     gc_was_on = gc.isenabled()
     gc.disable()
     try:
         with torch.cuda.device(dev):
-            for batch in batches:
+            for batch in setup["batches"]:
                 plan = batch.plan
-                P, N = plan.P, plan.N
-                stored = [int(r) for r in batch.small.rows]
-                # index lists, once per masked parameter of the plan
-                mnames = []
-                for name, _ in batch.entries:
-                    if mask_of[name] is not None and name not in mnames:
-                        mnames.append(name)
-                idx_true = idx_false = {}
-                ms = None
-                if mnames:
-                    ms = ml.MaskSet([int(mask_of[n].numel()) for n in mnames], dev)
-                    it, if_, ct, cf = ms.indices([mask_of[n] for n in mnames], include_noise)
-                    counts = torch.stack([ct, cf if cf is not None else torch.zeros_like(ct)]).cpu().tolist()
-                    idx_true = {n: (it[q], counts[0][q]) for q, n in enumerate(mnames)}
-                    idx_false = {n: (if_[q], counts[1][q]) for q, n in enumerate(mnames)} if include_noise else {}
-                keep, tab, btab, itab, active = [], [0] * (P * N), [0] * P, [0] * P, [False] * P
-                for i, (name, region) in enumerate(batch.entries):
-                    if region == "noise" and not include_noise:
-                        continue      # compress_parameter hands no noise basis on: "unmasked" stays None
-                    m = mask_of[name]
-                    if region == "noise" and m is None:
-                        continue      # no mask, no noise region (compress.py:150-152)
-                    numel = None
-                    for t, task in enumerate(tasks):
-                        x = task_vectors[task].get(name)
-                        if x is None:
-                            continue
-                        v = prepare_input(x, dev, in_dtype)
-                        numel = v.numel()
-                        keep.append(v)
-                        tab[i * N + t] = v.data_ptr()
-                    if m is not None:
-                        lst, count = (idx_false if region == "noise" else idx_true)[name]
-                        keep.append(lst)
-                        itab[i] = lst.data_ptr()
-                    else:
-                        count = numel
-                    if count != stored[i]:
-                        raise ValueError(f"parameter {name!r} [{region}]: {count} selected elements, the stored basis "
-                                         f"has D = {stored[i]}")
-                    if base_state_dict is not None:
-                        b = prepare_input(base_state_dict[name], dev, in_dtype)
-                        if b.numel() != numel:
-                            raise ValueError(f"parameter {name!r}: the base tensor has {b.numel()} elements, the "
-                                             f"task tensors {numel}")
-                        keep.append(b)
-                        btab[i] = b.data_ptr()
-                    active[i] = True
-                has_idx = any(itab)
-                if has_idx:
-                    # a plan mixes masked and unmasked entries: an unmasked one reads through the identity list
-                    for i, (name, region) in enumerate(batch.entries):
-                        if active[i] and not itab[i]:
-                            ident = torch.arange(stored[i], dtype=torch.int32, device=dev)
-                            keep.append(ident)
-                            itab[i] = ident.data_ptr()
-                rows_dev = torch.tensor([stored[i] if active[i] else 0 for i in range(P)], dtype=torch.int64).to(dev)
-                table = torch.tensor(tab, dtype=torch.int64).to(dev)
-                base_table = torch.tensor(btab, dtype=torch.int64).to(dev) if base_state_dict is not None else None
-                index_table = torch.tensor(itab, dtype=torch.int64).to(dev) if has_idx else None
-                sm = plan.project_tasks(table, base_table=base_table, index_table=index_table, rows_dev=rows_dev)
-                del keep, ms
+                tb = _plan_tables(batch, setup, task_vectors, base_state_dict)
+                active = tb["active"]
+                sm = plan.project_tasks(tb["table"], base_table=tb["base_table"], index_table=tb["index_table"],
+                                        rows_dev=tb["rows_dev"])
+                del tb
                 for i, (name, region) in enumerate(batch.entries):
                     art_key = "masked" if region == "masked" else "unmasked"
                     per_task = out.setdefault(name, {})
@@ -285,21 +328,161 @@ def project_all_parameters(task_vectors: Dict[str, Dict[str, torch.Tensor]], mas
                         if active[i]:
                             art[art_key] = task_artifact(plan, sm, i, t)
         # the per-parameter route for whatever did not go into a plan
-        rest = [n for n in names if n not in out]
+        rest = [n for n in setup["names"] if n not in out]
         if rest:
-            quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
-            for name in rest:
-                tv = task_vectors
-                if base_state_dict is not None:
-                    b = base_state_dict[name]
-                    tv = {t: {name: (v[name].to(dev).float() - b.to(dev).float())} for t, v in task_vectors.items()
-                          if name in v}
-                comp = compress_parameter(name, tv, masks.get(name), bases[name], quantizer,
-                                          include_noise=include_noise, min_mask_size=config.svd_min_mask_size,
-                                          device=device)
-                if comp is not None:
-                    out[name] = comp
+            _per_parameter_rest(rest, out, task_vectors, setup, bases, config, device, base_state_dict)
     finally:
         if gc_was_on:
             gc.enable()
     return {n: out[n] for n in sorted(out)}
+
+
+# ---- the stored bases grown by what the new tasks add outside their span (include/svdq.h, svdq_plan_residual_gram)
+def _regions(basis):
+    """The (region key, artifact key, region basis) triples of one parameter's stored basis."""
+    return [(rk, ak, basis[rk]) for rk, ak in (("masked", "masked"), ("noise", "unmasked"))
+            if isinstance(basis, dict) and isinstance(basis.get(rk), dict)]
+
+
+def check_extension_room(bases: Dict[str, Dict], n_new: int, n_stored_tasks: Optional[int] = None) -> None:
+    """The ``ValueError``s of ``extend_bases``, from shapes and scalars alone (no GPU): at most ``MAX_NEW_TASKS`` new
+    tasks per call, and for every stored region k + n_new <= 32, r + n_new <= 32 and N + n_new <= 32 -- an extended
+    store must be adoptable again (a plan has at most 32 slots and r <= N)."""
+    if not 1 <= n_new <= nat.MAX_NEW_TASKS:
+        raise ValueError(f"extend_bases takes 1 to {nat.MAX_NEW_TASKS} new tasks per call, got {n_new}")
+    if n_stored_tasks is not None and n_stored_tasks + n_new > nat.MAX_TASKS:
+        raise ValueError(f"{n_stored_tasks} stored + {n_new} new tasks: at most {nat.MAX_TASKS} tasks in total")
+    for name in sorted(bases):
+        for rk, _, b in _regions(bases[name]):
+            k = int(b["k"])
+            r = k + (int(b["U_low"].shape[1]) if b["U_low"].dim() == 2 else 0)
+            if k + n_new > nat.MAX_TASKS:
+                raise ValueError(f"parameter {name!r} [{rk}]: k + new tasks = {k} + {n_new} > {nat.MAX_TASKS}")
+            if r + n_new > nat.MAX_TASKS:
+                raise ValueError(f"parameter {name!r} [{rk}]: r + new tasks = {r} + {n_new} > {nat.MAX_TASKS}")
+            n_old = b.get("N")
+            if n_old is not None and int(n_old) + n_new > nat.MAX_TASKS:
+                raise ValueError(f"parameter {name!r} [{rk}]: {int(n_old)} stored + {n_new} new tasks: at most "
+                                 f"{nat.MAX_TASKS} tasks in total")
+
+
+def extended_basis_entry(basis: Dict, u_high_ext: torch.Tensor, lam, n_added: int) -> Dict:
+    """One region's basis dictionary after m = len(lam) new columns: U_high' = ``u_high_ext`` [D, k + m] (the stored
+    columns first), k' = k + m, singular_values' = [sigma[:k], sqrt(lam), sigma[k:]] -- NOT globally descending any more;
+    its first k' entries are still the high columns --, energy_retained by the reference's formula on that vector
+    (compute_energy_spectrum, cum[k' - 1]; basis.py:116-156), N' = N + ``n_added``.  U_low and mean are the same
+    objects.  A pure function of its arguments (no GPU)."""
+    from .basis import compute_energy_spectrum
+    k = int(basis["k"])
+    lam_t = torch.as_tensor(lam, dtype=torch.float64).reshape(-1)
+    m = int(lam_t.numel())
+    if tuple(u_high_ext.shape) != (int(basis["U_high"].shape[0]), k + m):
+        raise ValueError(f"U_high' has shape {tuple(u_high_ext.shape)}, expected "
+                         f"{(int(basis['U_high'].shape[0]), k + m)}")
+    sv = torch.as_tensor(basis["singular_values"]).detach().cpu().float().reshape(-1)
+    sv2 = torch.cat([sv[:k], lam_t.clamp_min(0).sqrt().float(), sv[k:]])
+    out = dict(basis)
+    out["U_high"] = u_high_ext
+    out["k"] = k + m
+    out["singular_values"] = sv2
+    out["energy_retained"] = float(compute_energy_spectrum(sv2)[k + m - 1]) if k + m > 0 else 0.0
+    if "N" in basis:
+        out["N"] = int(basis["N"]) + int(n_added)
+    return out
+
+
+def pad_c_high(artifact: Optional[Dict], m: int) -> Optional[Dict]:
+    """An OLD task's region artifact against a basis that gained m high columns: c_high' = [c_high, 0 ... 0] (fp16 holds
+    the zeros exactly), c_low_quant the same object."""
+    if artifact is None or m <= 0:
+        return artifact
+    out = dict(artifact)
+    c = artifact["c_high_fp16"]
+    out["c_high_fp16"] = torch.cat([c.reshape(-1), torch.zeros(m, dtype=c.dtype, device=c.device)])
+    return out
+
+
+def extend_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], masks: Optional[Dict[str, torch.Tensor]],
+                 bases: Dict[str, Dict], config, device: str = "cuda",
+                 base_state_dict: Optional[Dict[str, torch.Tensor]] = None, min_residual: float = 2.0 ** -12) -> Dict:
+    """``project_all_parameters`` plus the directions the new tasks add OUTSIDE the span of the stored columns: per plan
+    project -> residual Gram + eigen stage -> read the m values -> write U_high' (include/svdq.h,
+    svdq_plan_residual_gram).  No other task's checkpoint is read and no stored column is recomputed.
+
+    Arguments as ``project_all_parameters``; 1 to 8 new tasks per call, and every stored region needs k + M <= 32,
+    r + M <= 32 and N + M <= 32 (``ValueError`` before anything runs).  ``min_residual``: a residual direction is kept
+    when its norm exceeds ``min_residual`` times the largest |xc_j| of the entry.  The default 2^-12 sits 16 x above the
+    worst-case fp32 noise of the residual, (r + 2) 2^-24 sqrt(r) <= 1.2e-5 |xc| at r = 32, and far below what a 4-bit
+    c_low resolves.
+
+    Returns {"bases": the bases in the reference layout -- entries with new columns replaced by
+    ``extended_basis_entry``'s dictionaries (CPU tensors), every other entry the object that came in --, "compressed":
+    the new tasks' artifacts, c_high' = fp16([coef[:k], d_j]) on extended entries, otherwise exactly
+    ``project_all_parameters``', "columns": {(param, region): m} for every entry that went through a plan,
+    "captured_energy": {task: 1 - sum |e|^2 / sum |xc|^2 over those entries} -- the share of the task's energy the STORED
+    columns capture, i.e. what the plain route keeps --, "skipped": the parameters that stayed on the per-parameter
+    route (what ``adopt_bases`` declines, masks under ``svd_min_mask_size``): projected as today, not extended}."""
+    import gc
+    from .pipeline import task_artifact
+    tasks = list(task_vectors.keys())
+    check_extension_room(bases, len(tasks))
+    setup = _projection_setup(task_vectors, masks, bases, config, device, base_state_dict, "extend_bases")
+    dev, M = setup["dev"], len(tasks)
+    out: Dict[str, Dict] = {}
+    new_bases = dict(bases)
+    columns: Dict = {}
+    e_sum = {t: 0.0 for t in tasks}
+    x_sum = {t: 0.0 for t in tasks}
+    gc_was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.device(dev):
+            for batch in setup["batches"]:
+                plan = batch.plan
+                tb = _plan_tables(batch, setup, task_vectors, base_state_dict)
+                active = tb["active"]
+                args = dict(base_table=tb["base_table"], index_table=tb["index_table"], rows_dev=tb["rows_dev"])
+                sm = plan.project_tasks(tb["table"], **args)
+                ext = plan.residual_gram(tb["table"], M, min_residual=min_residual, **args)
+                udt = torch.float16 if plan.fp16 else torch.float32
+                outs = [None] * plan.P
+                for i in range(plan.P):
+                    m = int(ext.m[i])
+                    if active[i] and m > 0:
+                        outs[i] = torch.empty((int(sm.rows[i]), int(sm.k[i]) + m), dtype=udt, device=dev)
+                if any(o is not None for o in outs):
+                    plan.extend_basis(tb["table"], M, outs, **args)
+                del tb
+                for i, (name, region) in enumerate(batch.entries):
+                    art_key = "masked" if region == "masked" else "unmasked"
+                    per_task = out.setdefault(name, {})
+                    m = int(ext.m[i]) if active[i] else 0
+                    present = [t for t, task in enumerate(tasks) if name in task_vectors[task]]
+                    if active[i]:
+                        columns[(name, region)] = m
+                    if m > 0:
+                        nb = dict(new_bases[name])
+                        nb[region] = extended_basis_entry(bases[name][region], outs[i].cpu(), ext.lam[i, :m], len(present))
+                        new_bases[name] = nb
+                    for t in present:
+                        task = tasks[t]
+                        art = per_task.setdefault(task, {"masked": None, "unmasked": None})
+                        if not active[i]:
+                            continue
+                        a = task_artifact(plan, sm, i, t)
+                        if m > 0:
+                            a = dict(a)
+                            d = torch.from_numpy(ext.d[i, t, :m].copy()).half()
+                            a["c_high_fp16"] = torch.cat([a["c_high_fp16"].reshape(-1), d])
+                        art[art_key] = a
+                        e_sum[task] += float(ext.enorm[i, t])
+                        x_sum[task] += float(ext.xnorm[i, t])
+        rest = [n for n in setup["names"] if n not in out]
+        if rest:
+            _per_parameter_rest(rest, out, task_vectors, setup, bases, config, device, base_state_dict)
+    finally:
+        if gc_was_on:
+            gc.enable()
+    captured = {t: (1.0 - e_sum[t] / x_sum[t]) if x_sum[t] > 0.0 else 1.0 for t in tasks}
+    return {"bases": new_bases, "compressed": {n: out[n] for n in sorted(out)}, "columns": columns,
+            "captured_energy": captured, "skipped": sorted(rest)}

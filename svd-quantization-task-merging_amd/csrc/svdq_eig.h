@@ -56,6 +56,13 @@ __device__ __forceinline__ void phase_sync() {
     }
 }
 
+// Parallel-order cyclic Jacobi in fp64 on the symmetric n x n matrix A (leading dimension NMAX + 1, LDS), V <- V J with
+// V = I on entry: on return the diagonal of A holds the eigenvalues (unsorted) and the columns of V the eigenvectors.
+// rowoff / rowdg: LDS scratch [n].  The THREADS threads of one workgroup call it together.  Shared by eig_param and the
+// basis-extension eigen stage (svdq_plan_extend.hip).  Defined below eig_param.
+template <int THREADS, int NMAX>
+__device__ __forceinline__ void jacobi_parallel(double *A, double *V, double *rowoff, double *rowdg, int n, int tid);
+
 // THREADS = 64 for n <= 8 (one wavefront: barriers cost nothing), 256 otherwise.
 // LDS scratch eig_param<THREADS, NMAX> needs (bytes), for the caller that provides it
 #define SVDQ_EIG_LDS_BYTES(NMAX) (((NMAX) * (NMAX) + 2 * (NMAX) * ((NMAX) + 1) + 7 * (NMAX)) * 8 + ((NMAX) + 1) * 4)
@@ -179,88 +186,7 @@ __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
     phase_sync<THREADS>();
 
     EIG_STAMP(2);
-    // Parallel-order cyclic Jacobi: a round-robin tournament pairs all indices into M = ceil(n/2)
-    // disjoint (p,q) per round (ne - 1 rounds per sweep); the M rotations of a round commute, so they
-    // are applied together: A <- A J (columns), then A <- J^T A (rows), V <- V J.
-    const int M = (n + 1) >> 1, ne = 2 * M;
-    // fixed work assignment: item e = (idx, m) -> thread e % THREADS; n*M <= 512, so <= 2 items/thread
-    // for THREADS = 256 and exactly <= 1 for THREADS = 64 (n <= 8).  No division inside the sweeps.
-    constexpr int ITEMS = (NMAX * ((NMAX + 1) / 2) + THREADS - 1) / THREADS;
-    int it_idx[ITEMS], it_m[ITEMS];
-#pragma unroll
-    for (int u = 0; u < ITEMS; ++u) {
-        const int e = tid + u * THREADS;
-        it_idx[u] = (e < n * M) ? e / M : -1;
-        it_m[u] = (e < n * M) ? e % M : 0;
-    }
-    for (int sweep = 0; sweep < 40 && n >= 2; ++sweep) {
-        if (tid < n) {
-            double off = 0.0;
-            for (int j = 0; j < n; ++j) {
-                const double a = A[tid * LDX + j];
-                off += (j != tid) ? a * a : 0.0;
-            }
-            rowoff[tid] = off;
-            rowdg[tid] = A[tid * LDX + tid] * A[tid * LDX + tid];
-        }
-        phase_sync<THREADS>();
-        double off = 0.0, dg = 0.0;  // every thread adds the n row sums in the same order: uniform decision
-        for (int j = 0; j < n; ++j) {
-            off += rowoff[j];
-            dg += rowdg[j];
-        }
-        if (off <= 1e-30 * dg || dg == 0.0) break;
-        for (int rd = 0; rd < ne - 1; ++rd) {
-            // every thread derives the rotation of ITS pair itself (same inputs -> same bits in all of
-            // the pair's threads) and keeps (c, s) in registers for the column and the row phase
-            int pp[ITEMS], qq[ITEMS];
-            double cs[ITEMS], sn[ITEMS];
-#pragma unroll
-            for (int u = 0; u < ITEMS; ++u) {
-                const int m = it_m[u];
-                int a2, b2;
-                if (m == 0) {
-                    a2 = ne - 1;
-                    b2 = rd;
-                } else {
-                    a2 = rd + m;
-                    if (a2 >= ne - 1) a2 -= ne - 1;
-                    b2 = rd - m;
-                    if (b2 < 0) b2 += ne - 1;
-                }
-                pp[u] = a2 < b2 ? a2 : b2;
-                qq[u] = a2 < b2 ? b2 : a2;
-                cs[u] = 1.0;
-                sn[u] = 0.0;
-                if (it_idx[u] >= 0 && qq[u] < n)
-                    jacobi_cs(A[pp[u] * LDX + pp[u]], A[qq[u] * LDX + qq[u]], A[pp[u] * LDX + qq[u]], cs[u], sn[u]);
-            }
-            phase_sync<THREADS>();  // everybody has read the 2x2 blocks before anybody rotates
-#pragma unroll
-            for (int u = 0; u < ITEMS; ++u) {  // columns of A and V: A <- A J, V <- V J
-                const int i = it_idx[u];
-                if (i >= 0 && qq[u] < n) {
-                    const double x = A[i * LDX + pp[u]], y = A[i * LDX + qq[u]];
-                    A[i * LDX + pp[u]] = cs[u] * x - sn[u] * y;
-                    A[i * LDX + qq[u]] = sn[u] * x + cs[u] * y;
-                    const double vx = V[i * LDX + pp[u]], vy = V[i * LDX + qq[u]];
-                    V[i * LDX + pp[u]] = cs[u] * vx - sn[u] * vy;
-                    V[i * LDX + qq[u]] = sn[u] * vx + cs[u] * vy;
-                }
-            }
-            phase_sync<THREADS>();
-#pragma unroll
-            for (int u = 0; u < ITEMS; ++u) {  // rows of A: A <- J^T A
-                const int j = it_idx[u];
-                if (j >= 0 && qq[u] < n) {
-                    const double x = A[pp[u] * LDX + j], y = A[qq[u] * LDX + j];
-                    A[pp[u] * LDX + j] = cs[u] * x - sn[u] * y;
-                    A[qq[u] * LDX + j] = sn[u] * x + cs[u] * y;
-                }
-            }
-            phase_sync<THREADS>();
-        }
-    }
+    jacobi_parallel<THREADS, NMAX>(A, V, rowoff, rowdg, n, tid);
     phase_sync<THREADS>();
     EIG_STAMP(3);
 
@@ -450,3 +376,90 @@ __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
     EIG_STAMP(8);
 }
 
+template <int THREADS, int NMAX>
+__device__ __forceinline__ void jacobi_parallel(double *A, double *V, double *rowoff, double *rowdg, int n, int tid) {
+#pragma clang fp contract(off)
+    constexpr int LDX = NMAX + 1;
+    // Parallel-order cyclic Jacobi: a round-robin tournament pairs all indices into M = ceil(n/2)
+    // disjoint (p,q) per round (ne - 1 rounds per sweep); the M rotations of a round commute, so they
+    // are applied together: A <- A J (columns), then A <- J^T A (rows), V <- V J.
+    const int M = (n + 1) >> 1, ne = 2 * M;
+    // fixed work assignment: item e = (idx, m) -> thread e % THREADS; n*M <= 512, so <= 2 items/thread
+    // for THREADS = 256 and exactly <= 1 for THREADS = 64 (n <= 8).  No division inside the sweeps.
+    constexpr int ITEMS = (NMAX * ((NMAX + 1) / 2) + THREADS - 1) / THREADS;
+    int it_idx[ITEMS], it_m[ITEMS];
+#pragma unroll
+    for (int u = 0; u < ITEMS; ++u) {
+        const int e = tid + u * THREADS;
+        it_idx[u] = (e < n * M) ? e / M : -1;
+        it_m[u] = (e < n * M) ? e % M : 0;
+    }
+    for (int sweep = 0; sweep < 40 && n >= 2; ++sweep) {
+        if (tid < n) {
+            double off = 0.0;
+            for (int j = 0; j < n; ++j) {
+                const double a = A[tid * LDX + j];
+                off += (j != tid) ? a * a : 0.0;
+            }
+            rowoff[tid] = off;
+            rowdg[tid] = A[tid * LDX + tid] * A[tid * LDX + tid];
+        }
+        phase_sync<THREADS>();
+        double off = 0.0, dg = 0.0;  // every thread adds the n row sums in the same order: uniform decision
+        for (int j = 0; j < n; ++j) {
+            off += rowoff[j];
+            dg += rowdg[j];
+        }
+        if (off <= 1e-30 * dg || dg == 0.0) break;
+        for (int rd = 0; rd < ne - 1; ++rd) {
+            // every thread derives the rotation of ITS pair itself (same inputs -> same bits in all of
+            // the pair's threads) and keeps (c, s) in registers for the column and the row phase
+            int pp[ITEMS], qq[ITEMS];
+            double cs[ITEMS], sn[ITEMS];
+#pragma unroll
+            for (int u = 0; u < ITEMS; ++u) {
+                const int m = it_m[u];
+                int a2, b2;
+                if (m == 0) {
+                    a2 = ne - 1;
+                    b2 = rd;
+                } else {
+                    a2 = rd + m;
+                    if (a2 >= ne - 1) a2 -= ne - 1;
+                    b2 = rd - m;
+                    if (b2 < 0) b2 += ne - 1;
+                }
+                pp[u] = a2 < b2 ? a2 : b2;
+                qq[u] = a2 < b2 ? b2 : a2;
+                cs[u] = 1.0;
+                sn[u] = 0.0;
+                if (it_idx[u] >= 0 && qq[u] < n)
+                    jacobi_cs(A[pp[u] * LDX + pp[u]], A[qq[u] * LDX + qq[u]], A[pp[u] * LDX + qq[u]], cs[u], sn[u]);
+            }
+            phase_sync<THREADS>();  // everybody has read the 2x2 blocks before anybody rotates
+#pragma unroll
+            for (int u = 0; u < ITEMS; ++u) {  // columns of A and V: A <- A J, V <- V J
+                const int i = it_idx[u];
+                if (i >= 0 && qq[u] < n) {
+                    const double x = A[i * LDX + pp[u]], y = A[i * LDX + qq[u]];
+                    A[i * LDX + pp[u]] = cs[u] * x - sn[u] * y;
+                    A[i * LDX + qq[u]] = sn[u] * x + cs[u] * y;
+                    const double vx = V[i * LDX + pp[u]], vy = V[i * LDX + qq[u]];
+                    V[i * LDX + pp[u]] = cs[u] * vx - sn[u] * vy;
+                    V[i * LDX + qq[u]] = sn[u] * vx + cs[u] * vy;
+                }
+            }
+            phase_sync<THREADS>();
+#pragma unroll
+            for (int u = 0; u < ITEMS; ++u) {  // rows of A: A <- J^T A
+                const int j = it_idx[u];
+                if (j >= 0 && qq[u] < n) {
+                    const double x = A[pp[u] * LDX + j], y = A[qq[u] * LDX + j];
+                    A[pp[u] * LDX + j] = cs[u] * x - sn[u] * y;
+                    A[qq[u] * LDX + j] = sn[u] * x + cs[u] * y;
+                }
+            }
+            phase_sync<THREADS>();
+        }
+    }
+}

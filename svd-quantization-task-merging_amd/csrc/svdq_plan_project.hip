@@ -23,9 +23,9 @@
 #include "svdq_dispatch.h"
 #include "svdq_input.h"
 #include "svdq_merge_stream.h"
+#include "svdq_plan_rows.h"
 
 typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(1))) int32_t pp_gint;
 
 __device__ __forceinline__ float pp_lds_u(const uint8_t *base, int byte_off, __half) {
     return __half2float(*reinterpret_cast<const __half *>(base + byte_off));
@@ -99,71 +99,15 @@ __global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict
         for (int t = 0; t < NTP; ++t) dp[t] = t < n ? (gin<TIN> *)ptrs[(size_t)p * n + t] : nullptr;
         gin<TIN> *bp = nullptr;
         if constexpr (FB) bp = (gin<TIN> *)base_ptrs[p];
-        pp_gint *gidx = nullptr;
-        if constexpr (GATHER) gidx = (pp_gint *)idx_ptrs[p];
+        plan_gint *gidx = nullptr;
+        if constexpr (GATHER) gidx = (plan_gint *)idx_ptrs[p];
 
         // ---- the loads of one block into registers; lane l owns rows c0 + RPL l .. + RPL - 1
         float xpf[NTP][RPL] = {}, mpf[RPL] = {}, bpf[RPL] = {};
         f32x4 ureg[SV];
         auto prefetch = [&](int64_t c0) {
-            const int64_t r0 = c0 + RPL * lane;
-            const int nr = block_rows<RB>(c0, cend);
-            if constexpr (GATHER) {
-                int64_t src[RPL];
-                bool in[RPL];
-#pragma unroll
-                for (int e = 0; e < RPL; ++e) {
-                    in[e] = r0 + e < cend;
-                    src[e] = in[e] ? (int64_t)gidx[r0 + e] : 0;
-                }
-                if constexpr (FB) {
-#pragma unroll
-                    for (int e = 0; e < RPL; ++e) bpf[e] = in[e] ? in_load1<TIN>(bp + src[e]) : 0.f;
-                }
-#pragma unroll
-                for (int t = 0; t < NTP; ++t)
-                    if (dp[t]) {      // wave-uniform
-#pragma unroll
-                        for (int e = 0; e < RPL; ++e) xpf[t][e] = in[e] ? in_load1<TIN>(dp[t] + src[e]) : 0.f;
-                    }
-            } else if (nr == RB) {
-                if constexpr (FB) {
-                    if constexpr (RPL == 4) {
-                        const f32x4 v = in_load4<TIN>(bp + r0);
-                        bpf[0] = v.x, bpf[1] = v.y, bpf[2] = v.z, bpf[3] = v.w;
-                    } else {
-                        const svdq_f32x2 v = in_load2<TIN>(bp + r0);
-                        bpf[0] = v.x, bpf[1] = v.y;
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < NTP; ++t)
-                    if (dp[t]) {
-                        if constexpr (RPL == 4) {
-                            const f32x4 v = in_load4<TIN>(dp[t] + r0);
-                            xpf[t][0] = v.x, xpf[t][1] = v.y, xpf[t][2] = v.z, xpf[t][3] = v.w;
-                        } else {
-                            const svdq_f32x2 v = in_load2<TIN>(dp[t] + r0);
-                            xpf[t][0] = v.x, xpf[t][1] = v.y;
-                        }
-                    }
-            } else {
-                if constexpr (FB) {
-#pragma unroll
-                    for (int e = 0; e < RPL; ++e) bpf[e] = (r0 + e < cend) ? in_load1<TIN>(bp + (r0 + e)) : 0.f;
-                }
-#pragma unroll
-                for (int t = 0; t < NTP; ++t)
-                    if (dp[t]) {
-#pragma unroll
-                        for (int e = 0; e < RPL; ++e) xpf[t][e] = (r0 + e < cend) ? in_load1<TIN>(dp[t] + (r0 + e)) : 0.f;
-                    }
-            }
-            if (gmean) {
-#pragma unroll
-                for (int e = 0; e < RPL; ++e) mpf[e] = (r0 + e < cend) ? gmean[r0 + e] : 0.f;
-            }
-            ustage_fetch(ureg, ustage_plan<ES>(c0, nr, k, nl), gUh, gUl, lane);
+            plan_rows_fetch<TIN, NTP, RPL, GATHER, FB>(xpf, mpf, bpf, dp, bp, gidx, gmean, c0, cend, lane);
+            ustage_fetch(ureg, ustage_plan<ES>(c0, block_rows<RB>(c0, cend), k, nl), gUh, gUl, lane);
         };
 
         // ---- where the lane's A operand (basis column i = col + 16 ti, row 4 g of a 16-row step) sits in the staged image.

@@ -158,6 +158,29 @@ def small_views(host: np.ndarray, L, P: int, N: int, S: int) -> SmallArtifacts:
         coef=view(L.coef_off, np.float32, (P, N, N)))
 
 
+@dataclass
+class ExtendArtifacts:
+    """Host copy of a plan's extension buffer (include/svdq.h, svdq_extend_layout), as typed numpy views."""
+    m: np.ndarray          # [P] i32       new columns kept
+    lam: np.ndarray        # [P, 8] f64    eigenvalues of the residual Gram over the present slots, descending
+    z: np.ndarray          # [P, 8, 8] f32 Z[slot][column]
+    d: np.ndarray          # [P, 8, 8] f32 d[slot][column]: the slot's coefficients on the new columns
+    xnorm: np.ndarray      # [P, 8] f64    |xc_j|^2
+    enorm: np.ndarray      # [P, 8] f64    |e_j|^2
+
+
+def extend_views(host: np.ndarray, L, P: int) -> ExtendArtifacts:
+    """The typed views of one extension buffer (``host``: its bytes as a uint8 array; ``L``: its layout).  No copy."""
+    def view(off, dtype, shape):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return host[off:off + n].view(dtype).reshape(shape)
+
+    M = nat.MAX_NEW_TASKS
+    return ExtendArtifacts(m=view(L.m_off, np.int32, (P,)), lam=view(L.lambda_off, np.float64, (P, M)),
+                           z=view(L.z_off, np.float32, (P, M, M)), d=view(L.d_off, np.float32, (P, M, M)),
+                           xnorm=view(L.xnorm_off, np.float64, (P, M)), enorm=view(L.enorm_off, np.float64, (P, M)))
+
+
 def pack_small(layout, P: int, N: int, S: int, entries: Sequence[Optional[Dict]]) -> np.ndarray:
     """The bytes of a plan's small-artifact buffer (include/svdq.h, svdq_small_layout) from per-parameter artifact
     values -- what ``CompressPlan.import_artifacts`` uploads.  A pure function of its arguments (``layout`` is any object
@@ -494,6 +517,90 @@ class CompressPlan:
                                                  _ptr(self.basis), _ptr(self.mean), _ptr(self.small), _ptr(work),
                                                  _stream_ptr()), who)
             return self.fetch_small() if fetch else None
+
+    # ---- the basis grown by what new tasks add outside its span (svdq_plan_extend.hip)
+    def _extend_args(self, who, table, base_table, index_table, rows_dev):
+        if self.basis is None:
+            raise ValueError(f"{who}: a gram_only plan has no basis to extend")
+        for what, t, need in (("table", table, self.P * self.N), ("base_table", base_table, self.P),
+                              ("index_table", index_table, self.P), ("rows_dev", rows_dev, self.P)):
+            if t is None:
+                if what == "table":
+                    raise ValueError(f"{who}: the task pointer table is required")
+                continue
+            if t.dtype is not torch.int64 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{who}: {what} must be a contiguous int64 tensor on {self.device}")
+            if t.numel() != need:
+                raise ValueError(f"{who}: {what} needs {need} entries, got {t.numel()}")
+
+    def extend_layout(self):
+        lay = getattr(self, "_extend_layout", None)
+        if lay is None:
+            lay = self._extend_layout = nat.SvdqExtendLayout()
+            nat.check(self.lib.svdq_plan_extend_layout(self._h, byref(lay)), "svdq_plan_extend_layout")
+        return lay
+
+    def residual_gram(self, table: torch.Tensor, n_new: int, base_table: Optional[torch.Tensor] = None,
+                      index_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None,
+                      min_residual: float = 2.0 ** -12, fetch: bool = True) -> Optional["ExtendArtifacts"]:
+        """After ``project_tasks`` on the same tables: the residuals of the new tasks in slots [0, ``n_new``) against the
+        basis this plan holds, their Gram matrix and its eigen stage (svdq_plan_residual_gram, two launches).  The small
+        buffer -- the fp32 coefficients ``project_tasks`` left there -- the basis and the mean are only read.  The
+        extension buffer stays on the device in ``self.extension``; returns its host views (the one small device-to-host
+        copy ``extend_basis`` needs to size its outputs; it synchronises) and raises ``NonFiniteInput`` when a new task's
+        |xc|^2 in that copy is not finite; ``fetch=False`` enqueues only."""
+        who = "svdq_plan_residual_gram"
+        self._extend_args(who, table, base_table, index_table, rows_dev)
+        lay = self.extend_layout()
+        ext = getattr(self, "extension", None)
+        if ext is None or ext.numel() != int(lay.total_bytes):
+            ext = self.extension = torch.zeros(int(lay.total_bytes), dtype=torch.uint8, device=self.device)
+        need = int(self.lib.svdq_plan_residual_gram_work_bytes(self._h))
+        work = getattr(self, "_extend_work", None)
+        if work is None or work.numel() < need:
+            work = self._extend_work = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.svdq_plan_residual_gram(self._h, _ptr(table), _ptr(base_table), _ptr(index_table),
+                                                       _ptr(rows_dev), _ptr(self.basis), _ptr(self.mean), _ptr(self.small),
+                                                       int(n_new), float(min_residual), _ptr(ext), _ptr(work),
+                                                       _stream_ptr()), who)
+            if not fetch:
+                return None
+            views = extend_views(ext.cpu().numpy(), lay, self.P)
+            bad = np.flatnonzero(~np.isfinite(views.xnorm).all(axis=1)).tolist()      # on the host copy: no second one
+            if bad:
+                raise NonFiniteInput(bad, f"{who}: input contained non-finite values (plan parameters {bad}: NaN or Inf "
+                                          "among the new tasks' centred deltas, or squares that overflow fp32)")
+            return views
+
+    def extend_basis(self, table: torch.Tensor, n_new: int, out: Sequence[Optional[torch.Tensor]],
+                     base_table: Optional[torch.Tensor] = None, index_table: Optional[torch.Tensor] = None,
+                     rows_dev: Optional[torch.Tensor] = None) -> None:
+        """After ``residual_gram`` on the same tables: write ``out[p]`` = U_high' [D, k + m] -- the stored U_high columns
+        bit for bit, then the m new orthonormal columns -- for every parameter whose ``out[p]`` is a tensor
+        (svdq_plan_extend_basis, one launch; m is read from ``self.extension`` on the device).  ``out[p]``: None (not
+        written) or a contiguous, 16-byte aligned tensor of the plan's basis dtype on its device with at least
+        D (k + m) elements.  Asynchronous on the current stream."""
+        who = "svdq_plan_extend_basis"
+        self._extend_args(who, table, base_table, index_table, rows_dev)
+        if getattr(self, "extension", None) is None:
+            raise ValueError(f"{who}: residual_gram has not run on this plan")
+        if len(out) != self.P:
+            raise ValueError(f"{who}: expected {self.P} output entries, got {len(out)}")
+        udt = torch.float16 if self.fp16 else torch.float32
+        ptrs = []
+        for p, t in enumerate(out):
+            if t is None:
+                ptrs.append(0)
+                continue
+            if t.dtype is not udt or t.device != self.device or not t.is_contiguous() or t.data_ptr() & 15:
+                raise ValueError(f"{who}: out[{p}] must be a contiguous, 16-byte aligned {udt} tensor on {self.device}")
+            ptrs.append(t.data_ptr())
+        with torch.cuda.device(self.device):
+            otab = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
+            nat.check(self.lib.svdq_plan_extend_basis(self._h, _ptr(table), _ptr(base_table), _ptr(index_table),
+                                                      _ptr(rows_dev), _ptr(self.basis), _ptr(self.mean), _ptr(self.small),
+                                                      int(n_new), _ptr(self.extension), _ptr(otab), _stream_ptr()), who)
 
     # ---- consumers of the artifacts, batched over the plan (svdq_merge.hip)
     def new_merged_outputs(self):

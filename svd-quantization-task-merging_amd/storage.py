@@ -273,7 +273,8 @@ def _stored_tasks(compressed: Dict[str, Dict], diagnostics: Dict[str, Any]) -> l
 
 def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[str, Any],
                            masks: Optional[Dict[str, torch.Tensor]] = None, output_dir: str = None,
-                           weights: Optional[Dict[str, float]] = None, device: str = "cuda") -> Dict[str, Any]:
+                           weights: Optional[Dict[str, float]] = None, device: str = "cuda",
+                           extend_basis: bool = False, min_residual: float = 2.0 ** -12) -> Dict[str, Any]:
     """Add NEW fine-tuned models to a stored artifact set: each is projected onto the bases already stored, its
     coefficients are quantized and it joins the per-parameter coefficient dictionaries -- compress_all_parameters
     (reference compress.py:173-207) for the new tasks alone.  The other tasks' checkpoints are not needed and no basis is
@@ -286,9 +287,17 @@ def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[s
     ``output_dir``: None or the artifact directory itself = in place, and then only the coefficient files and
     diagnostics.json are rewritten; any other directory receives the whole store.
     A task name the store already holds, or more than 32 tasks in total, is a ``ValueError`` before anything is read
-    from the checkpoints.  Returns {"tasks", "added", "compressed" (the new tasks' artifacts), "output_dir"}."""
+    from the checkpoints.  Returns {"tasks", "added", "compressed" (the new tasks' artifacts), "output_dir"}.
+
+    ``extend_basis=True`` (1 to 8 new tasks): the stored U_high of every batched entry also grows by the orthonormal
+    directions the new tasks add outside the span of the stored columns (``compress.extend_bases``; ``min_residual`` is
+    its threshold) -- without it a new task's artifact reconstructs little more than the stored mean, since r <= N
+    stored directions span next to nothing of a new delta.  The old tasks' ``c_high`` of extended entries are zero-padded
+    (their reconstructions do not move), the extended basis files are written as well, and ``captured_energy`` ({task:
+    share of its energy the stored columns captured}) and ``columns`` ({"param [region]": new columns}) go into
+    diagnostics.json and the return value.  ``False`` is the plain route, bit for bit."""
     from . import _native as nat
-    from .compress import project_all_parameters
+    from .compress import check_extension_room, extend_bases, pad_c_high, project_all_parameters
     art = load_all_artifacts(artifact_dir, device="cpu")
     config, diagnostics, bases, compressed = art["config"], art["diagnostics"], art["bases"], art["compressed"]
     old = _stored_tasks(compressed, diagnostics)
@@ -300,6 +309,8 @@ def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[s
             raise ValueError(f"task {t!r} is already in the artifacts, which hold {old}")
     if len(old) + len(new) > nat.MAX_TASKS:
         raise ValueError(f"{len(old)} stored + {len(new)} new tasks: at most {nat.MAX_TASKS} tasks in total")
+    if extend_basis:
+        check_extension_room(bases, len(new), len(old))
     tasks = old + new
     if weights is not None:
         lacking = [t for t in tasks if t not in weights]
@@ -313,21 +324,42 @@ def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[s
     for t, ckpt in finetuned.items():
         sd = _load_base(ckpt, device)
         models[t] = {n: sd[n] for n in bases if n in sd and n in base}
-    added = project_all_parameters(models, masks or {}, bases, config, device=device,
-                                   base_state_dict={n: base[n] for n in bases if n in base})
+    base_sd = {n: base[n] for n in bases if n in base}
+    extension, grown = None, {}
+    if extend_basis:
+        extension = extend_bases(models, masks or {}, bases, config, device=device, base_state_dict=base_sd,
+                                 min_residual=min_residual)
+        added = extension["compressed"]
+        for (name, region), m in extension["columns"].items():
+            if m <= 0:
+                continue
+            art_key = "masked" if region == "masked" else "unmasked"
+            grown[name] = bases[name] = extension["bases"][name]
+            compressed[name] = {t: {**a, art_key: pad_c_high(a.get(art_key), m)} if isinstance(a, dict) else a
+                                for t, a in compressed.get(name, {}).items()}
+    else:
+        added = project_all_parameters(models, masks or {}, bases, config, device=device, base_state_dict=base_sd)
     touched = {}
     for name, per_task in added.items():
         merged = dict(compressed.get(name, {}))
         merged.update(per_task)
         compressed[name] = touched[name] = merged
     diagnostics["task_weights"] = task_weights
+    result = {"tasks": tasks, "added": new, "compressed": added}
+    if extension is not None:
+        result["captured_energy"] = diagnostics["captured_energy"] = dict(extension["captured_energy"])
+        result["columns"] = diagnostics["columns"] = {f"{n} [{r}]": int(m) for (n, r), m in
+                                                      extension["columns"].items()}
     out = output_dir or artifact_dir
     if os.path.realpath(out) == os.path.realpath(artifact_dir):
+        for name, b in grown.items():
+            save_basis(b, name, out)
         save_compressed_coefficients(touched, out)
         save_diagnostics(diagnostics, out)
     else:
         save_all_artifacts(bases, compressed, diagnostics, config, out)
-    return {"tasks": tasks, "added": new, "compressed": added, "output_dir": out}
+    result["output_dir"] = out
+    return result
 
 
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
