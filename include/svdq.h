@@ -31,6 +31,7 @@ extern "C" {
 #define SVDQ_ABI_VERSION 1
 #define SVDQ_MAX_TASKS 32
 #define SVDQ_MAX_STAGES 8
+#define SVDQ_MAX_BOOL_MASKS 255 /* bool-byte masks one combine call votes on (the bit-packed routes: SVDQ_MAX_TASKS) */
 
 enum {
     SVDQ_OK = 0,
@@ -357,6 +358,10 @@ int svdq_project(const void *u_high_dev, const void *u_low_dev, int32_t u_fp16, 
  *      svdq_mask_combine writes the combined mask (0/1 bytes) and its popcount.  strategy: SVDQ_MASK_*; for
  *      SVDQ_MASK_MAJORITY bits 8.. may carry (votes needed + 1) for compute_majority_mask(threshold != 0.5)
  *      (mask_loader.py:456-485: vote_sum >= threshold * len(masks), compared in fp32); 0 there = threshold 0.5.
+ *      Every votes needed in 0..n_masks + 1 is accepted (0: every element passes, n_masks + 1: none does).
+ *      n_masks <= SVDQ_MAX_BOOL_MASKS (255) for svdq_mask_combine, svdq_maskset_combine, svdq_maskset_combine_indices
+ *      and svdq_maskset_combine_starts: the votes of an element are counted in one byte.  More is SVDQ_EINVAL before
+ *      anything is launched, and svdq_last_error() names the limit.  The svdq_mask_* and svdq_maskset_* entry points take mask pointers of any alignment.
  *      svdq_mask_compact: order-preserving compaction of n_src fp32 buffers under one mask
  *      (invert != 0 selects the False positions); count_dev receives the selected count.
  *      work_dev: svdq_mask_work_bytes(numel) bytes. */
@@ -406,7 +411,11 @@ int     svdq_maskset_combine_indices(const svdq_maskset *ms, const void *mask_pt
  * mask_loader.py:125-206: one numpy.packbits stream per task over the flattened state dict, first element = most
  * significant bit): stream_ptrs_dev [n_masks] device streams, stream_bytes_dev [n_masks] their lengths,
  * bit_offsets_dev [n_params] the bit position of each parameter's first element inside every stream.  Reads
- * n_masks / 8 bytes per element instead of n_masks; writes the combined bool masks, index lists and counts. */
+ * n_masks / 8 bytes per element instead of n_masks; writes the combined bool masks, index lists and counts.
+ * n_masks <= SVDQ_MAX_TASKS (32; the bool-byte routes above take SVDQ_MAX_BOOL_MASKS).  Every stream pointer is
+ * 16-byte aligned: the kernel fetches a stream in 16-byte chunks counted from its first byte.  No byte at or past
+ * stream_bytes_dev[m] is read, so a stream may end anywhere, also in the middle of a chunk.  The same holds for
+ * svdq_maskset_combine_packed_starts. */
 int     svdq_maskset_combine_packed_indices(const svdq_maskset *ms, const void *stream_ptrs_dev,
                                             const int64_t *stream_bytes_dev, const int64_t *bit_offsets_dev,
                                             int32_t n_masks, int32_t strategy, const void *out_ptrs_dev,

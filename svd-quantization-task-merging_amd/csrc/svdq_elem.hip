@@ -359,7 +359,14 @@ extern "C" int svdq_asym16_dequantize(const int16_t *codes, int64_t n, const flo
 
 // ---- tile helpers shared by the single-parameter and the batched mask kernels ------------------
 // torch.bool storage is one byte per element holding 0 or 1, so 8 mask bytes can be voted on at once:
-// byte lanes of a 64-bit word accumulate the per-element counts (n_masks <= 32 < 256, no carries).
+// byte lanes of a 64-bit word accumulate the per-element counts (n_masks <= SVDQ_MAX_BOOL_MASKS = 255: a lane holds
+// every count, nothing carries into its neighbour; the host entry points refuse more, bool_mask_count_ok).
+static bool bool_mask_count_ok(int n_masks, const char *who) {
+    if (n_masks <= SVDQ_MAX_BOOL_MASKS) return true;
+    svdq_set_error("%s: at most %d bool masks can be combined, got %d", who, SVDQ_MAX_BOOL_MASKS, n_masks);
+    return false;
+}
+
 __device__ __forceinline__ unsigned long long load_mask8(const uint8_t *p, int lim) {
     unsigned long long w = 0;
     if (lim == 8 && (reinterpret_cast<uintptr_t>(p) & 7) == 0) return *reinterpret_cast<const unsigned long long *>(p);
@@ -569,8 +576,10 @@ extern "C" int svdq_mask_combine(const void *mask_ptrs, int32_t n_masks, int64_t
         svdq_set_error("Empty mask list");  // mask_loader.py:425
         return SVDQ_EINVAL;
     }
+    if (!bool_mask_count_ok(n_masks, "svdq_mask_combine")) return SVDQ_EINVAL;
+    // bits 8.. = votes needed + 1, votes needed in 0..n_masks + 1 (n_masks + 1: no element can pass)
     if ((strategy & 0xff) > SVDQ_MASK_MAJORITY || strategy < 0 ||
-        ((strategy >> 8) != 0 && (strategy & 0xff) != SVDQ_MASK_MAJORITY) || (strategy >> 8) > SVDQ_MAX_TASKS + 2) {
+        ((strategy >> 8) != 0 && (strategy & 0xff) != SVDQ_MASK_MAJORITY) || (strategy >> 8) > n_masks + 2) {
         svdq_set_error("Unknown mask strategy: %d", strategy);  // mask_loader.py:611
         return SVDQ_EINVAL;
     }
@@ -972,6 +981,7 @@ extern "C" int svdq_maskset_combine(const svdq_maskset *ms, const void *mask_ptr
         svdq_set_error("Empty mask list");
         return SVDQ_EINVAL;
     }
+    if (!bool_mask_count_ok(n_masks, "svdq_maskset_combine")) return SVDQ_EINVAL;
     if (strategy < SVDQ_MASK_UNION || strategy > SVDQ_MASK_MAJORITY) {
         svdq_set_error("Unknown mask strategy: %d", strategy);
         return SVDQ_EINVAL;
@@ -1135,6 +1145,7 @@ extern "C" int svdq_maskset_combine_indices(const svdq_maskset *ms, const void *
         svdq_set_error(n_masks < 1 ? "Empty mask list" : "svdq_maskset_combine_indices: bad argument");
         return SVDQ_EINVAL;
     }
+    if (!bool_mask_count_ok(n_masks, "svdq_maskset_combine_indices")) return SVDQ_EINVAL;
     if (strategy < 0 || strategy > 2) {
         svdq_set_error("Unknown mask strategy: %d", strategy);
         return SVDQ_EINVAL;
@@ -1455,6 +1466,7 @@ extern "C" int svdq_maskset_combine_starts(const svdq_maskset *ms, const svdq_pl
         svdq_set_error(n_masks < 1 ? "Empty mask list" : "svdq_maskset_combine_starts: bad argument");
         return SVDQ_EINVAL;
     }
+    if (!bool_mask_count_ok(n_masks, "svdq_maskset_combine_starts")) return SVDQ_EINVAL;
     if (strategy < 0 || strategy > 2) {
         svdq_set_error("Unknown mask strategy: %d", strategy);
         return SVDQ_EINVAL;

@@ -22,6 +22,15 @@ def _as_mask_bytes(m: torch.Tensor, dev) -> torch.Tensor:
     return m.to(dev).contiguous().view(-1).view(torch.uint8)
 
 
+def _as_packed_stream(s: torch.Tensor, dev) -> torch.Tensor:
+    """A bit-packed mask stream on ``dev``: uint8, flat, contiguous, 16-byte aligned (the kernels fetch it in 16-byte
+    chunks counted from its first byte) -- cloned only when its storage is not, as prepare_vector does for fp32 inputs."""
+    v = s.to(dev).contiguous().view(-1).view(torch.uint8)
+    if v.data_ptr() % 16 != 0:
+        v = v.clone()
+    return v
+
+
 class MaskSet:
     """A ragged set of masked parameters processed together (svdq_maskset_*): one tile table, a handful of
     launches for all of them, per-parameter counts kept on the device."""
@@ -153,7 +162,7 @@ class MaskSet:
             raise ValueError(f"Unknown mask strategy: {strategy}")
         if not streams:
             raise ValueError("Empty mask list")
-        st = [s.to(self.device).contiguous().view(torch.uint8) for s in streams]
+        st = [_as_packed_stream(s, self.device) for s in streams]
         need = max((int(o) + n + 7) // 8 for o, n in zip(bit_offsets, self.numels))
         if any(s.numel() < need for s in st):
             raise ValueError("Shape mismatch: a packed mask stream is shorter than the parameters it should cover")
@@ -233,7 +242,7 @@ class MaskSet:
             raise ValueError(f"Unknown mask strategy: {strategy}")
         if not streams:
             raise ValueError("Empty mask list")
-        st = [s.to(self.device).contiguous().view(torch.uint8) for s in streams]
+        st = [_as_packed_stream(s, self.device) for s in streams]
         need = max((int(o) + n + 7) // 8 for o, n in zip(bit_offsets, self.numels))
         if any(s.numel() < need for s in st):
             raise ValueError("Shape mismatch: a packed mask stream is shorter than the parameters it should cover")
