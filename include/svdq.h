@@ -777,6 +777,44 @@ int svdq_plan_extend_basis(const svdq_plan *plan, const void *task_ptrs_dev, con
                            const float *mean_dev, const void *small_dev, int32_t n_new, const void *ext_dev,
                            const void *out_ptrs_dev /*[P] U_high' [D, k + m]; NULL entry = not written*/, void *stream);
 
+/* ---- the task Gram of a STORE: G[t][s] = <delta_t, delta_s> of the task vectors the stored artifacts reconstruct (the
+ *      one statement of the contract; the sources point here).  What the reference's cluster weighting looks at --
+ *      flatten_task_vectors (clustering.py:55-120) stacks the task vectors, cluster_tasks (clustering.py:198-245) clusters
+ *      the unit-normalised rows, and k-means / Ward only ever see their inner products -- computed from a plan's basis,
+ *      mean and small buffer alone: no fine-tuned checkpoint is read and no reconstructed model is written.
+ *   the identity    per parameter p, with A = [U_high | U_low | mean] [D, r + 1] and c'_t = [c_t ; 1] (c_t = the fp16
+ *                   c_high then the dequantized c_low of task slot t, exactly the values svdq_merge reconstructs from):
+ *                   delta_t = A c'_t, so G_p[t][s] = c'_t^T (A^T A) c'_s.  On an uncentred plan A = U and c'_t = c_t.
+ *                   U^T U is the real one, not I: stored columns are fp16 roundings, svdq_plan_extend_basis appends
+ *                   columns, and svdq_plan_import accepts any caller's U.  No scale (noise_shrink) is applied: the
+ *                   reference clusters raw task vectors.
+ *   inputs          rows_dev, small_dev, basis_dev, mean_dev: exactly as for svdq_plan_project -- k, r (held to the slab:
+ *                   r <= min(rows, N), k <= r) and, with rows_dev pointing at the small buffer's rows field, rows are read
+ *                   ON THE DEVICE.  All of them are ONLY READ.  rows[p] == 0: nothing of p is read, zeros are written.
+ *   arithmetic      A^T A: sums are fp32 inside one block of at most 256 rows (U^T U on the matrix pipe -- fp16 basis:
+ *                   v_mfma_f32_16x16x32_f16, whose fp16 x fp16 products are exact in fp32; fp32 basis: v_mfma_f32_16x16x4_f32;
+ *                   the mean column as fp32 fma chains over at most 4 rows per lane) and fp64 across blocks, lanes and work
+ *                   units, in a fixed order without atomics: the same bits in every run.  The coefficients are fp32 as the
+ *                   merge dequantizes them; C' (A^T A) C'^T is fp64, formed for t <= s and mirrored: exactly symmetric.
+ *   launches        two: one streaming launch over the plan's own work units (one wavefront each; a block of basis rows is
+ *                   staged once and is both operands of U^T U; one fp64 partial per unit goes to work_dev) and the
+ *                   fixed-order finish, one workgroup per parameter.  Reads 2 r + 4 bytes per row with an fp16 basis.
+ *   task_gram_dev   double [P][N][N], every entry written.  The per-parameter matrices are additive: the store's Gram is
+ *                   their sum, scattered by task name on the host (a plan's slot t may be another task in another entry).
+ *   basis_gram_dev  NULL, or double [P][33][33], every entry written: A^T A in rows / columns [0, r], row / column r = the
+ *                   mean (absent on an uncentred plan), zeros elsewhere.  max |U^T U - I| over its leading r x r block is
+ *                   the orthonormality of a stored or extended basis.
+ *   work_dev        svdq_plan_store_gram_work_bytes bytes: per work unit one fp64 [N][N] and one [N + 1].
+ *   errors          SVDQ_EINVAL before anything is launched: a NULL plan, small_dev, basis_dev, work_dev or task_gram_dev; a
+ *                   NULL mean_dev on a centred plan (on an uncentred plan it is ignored); rows, work or an output off 8
+ *                   bytes; small, basis or mean off 16.
+ *   Allocates nothing, copies nothing to the host, synchronises nothing: capturable like every other entry point.  Any
+ *   N <= SVDQ_MAX_TASKS, fp16 or fp32 basis, fused or adopted plans. */
+int64_t svdq_plan_store_gram_work_bytes(const svdq_plan *plan);
+int svdq_plan_store_gram(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                         const float *mean_dev, void *work_dev, double *task_gram_dev /*[P][N][N]*/,
+                         double *basis_gram_dev /*NULL or [P][33][33]*/, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

@@ -3,7 +3,9 @@
 (project_to_basis compress.py:6-21 inside compress_all_parameters compress.py:173-207, for the new tasks alone), its
 coefficients are quantized and written beside the other tasks'.  The other tasks' checkpoints are not needed and no basis
 is recomputed; afterwards load_and_merge.py / reconstruct_tasks.py see one more task.  --extend-basis also grows the
-stored bases by the directions the new tasks add outside their span (storage.add_tasks_to_artifacts).
+stored bases by the directions the new tasks add outside their span (storage.add_tasks_to_artifacts).  --weighting
+cluster then clusters ALL tasks, old and new, on the Gram of what the enlarged store reconstructs (cluster_tasks
+clustering.py:198-245 through storage.remerge_from_artifacts) and writes the cluster weights and labels into the store.
 
 A store that was compressed through masks needs the mask directory the run had (--mask-dir): masks are not stored
 (reload.py:204-205)."""
@@ -33,6 +35,12 @@ def build_parser():
     ap.add_argument("--min-residual", type=float, default=2.0 ** -12,
                     help="with --extend-basis: keep a residual direction whose norm exceeds this share of the largest "
                          "centred task norm (default 2^-12)")
+    ap.add_argument("--weighting", default=None, choices=["cluster"],
+                    help="after adding: cluster all tasks on what the store reconstructs and store the cluster weights "
+                         "(diagnostics.json task_weights / cluster_assignments, clusters.json); default: --weights-json "
+                         "or uniform, as before")
+    ap.add_argument("--cluster-k", type=int, default=None,
+                    help="with --weighting cluster: number of clusters (default: the stored configuration's)")
     return ap
 
 
@@ -76,6 +84,12 @@ def main(argv=None):
     if args.extend_basis:
         print(f"new basis columns: {sum(res['columns'].values())} over {len(res['columns'])} entries; energy the stored "
               f"columns captured: " + ", ".join(f"{t} {e:.4f}" for t, e in res["captured_energy"].items()))
+    if args.weighting == "cluster":
+        from svdq_amd.storage import remerge_from_artifacts
+        rem = remerge_from_artifacts(res["output_dir"], base, None, weighting="cluster", cluster_k=args.cluster_k,
+                                     device=args.device, update_store=True)
+        print("clusters: " + json.dumps(rem["cluster_assignments"]))
+        print("weights: " + json.dumps(rem["weights"]))
     return 0
 
 

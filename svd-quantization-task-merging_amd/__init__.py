@@ -28,7 +28,8 @@ from .weighting import (load_performance_metrics, compute_uniform_weights, compu
                         compute_cluster_weights, compute_weights, apply_weights_to_tensors, get_weight_statistics)
 from .clustering import (cluster_tasks, task_gram, cluster_from_gram, cluster_statistics_from_gram, flatten_task_vectors,
                          get_cluster_members, compute_cluster_statistics, merge_by_cluster, merge_cluster_results,
-                         compute_kmeans_clustering, compute_hierarchical_clustering)
+                         compute_kmeans_clustering, compute_hierarchical_clustering, assemble_task_gram,
+                         task_gram_from_artifacts, cluster_tasks_from_artifacts)
 from .diagnostics import (compute_reconstruction_error, compute_parameter_diagnostics, compute_all_diagnostics,
                           compute_all_diagnostics_from_checkpoints, compute_compression_statistics, print_detailed_compression_report,
                           print_diagnostics_summary, compute_coefficient_histograms)
@@ -36,7 +37,7 @@ from .storage import (save_basis, load_basis, save_compressed_coefficients, load
                       save_diagnostics, load_diagnostics, save_config, load_config, save_all_artifacts,
                       load_all_artifacts, save_merged_model, reconstruct_from_artifacts,
                       reload_merged_model_from_artifacts, reconstruct_tasks_from_artifacts,
-                      reconstruct_tasks_from_artifacts_masked, add_tasks_to_artifacts)
+                      reconstruct_tasks_from_artifacts_masked, add_tasks_to_artifacts, remerge_from_artifacts)
 from .task_vector_loader import (load_checkpoint, compute_task_vector, compute_task_vectors, load_task_vectors,
                                  get_parameter_names, organize_by_parameter, flatten_task_deltas,
                                  get_task_checkpoint_paths)

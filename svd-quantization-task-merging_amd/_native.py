@@ -157,6 +157,9 @@ SIGNATURES = {
                                           c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "svdq_plan_extend_basis": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_int32, c_void_p, c_void_p, c_void_p]),
+    "svdq_plan_store_gram_work_bytes": (c_int64, [c_void_p]),
+    "svdq_plan_store_gram": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
     "svdq_mask_expand": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "svdq_hbm_probe": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
 }

@@ -105,6 +105,118 @@ def task_gram(task_vectors: Dict[str, Dict[str, torch.Tensor]], device="cuda", *
     return out, tasks
 
 
+def assemble_task_gram(per_param: Dict[str, List[Tuple[np.ndarray, List[str]]]], tasks: List[str]) -> np.ndarray:
+    """The store's N x N Gram (rows / columns = ``tasks``) from per-parameter pieces {parameter: [(matrix, the tasks
+    its rows / columns stand for)]}: every matrix is added at its tasks' positions (``scatter_task_gram``), parameters in
+    sorted-name order, so the sum has one association whatever route produced the pieces.  A task that lacks a parameter
+    gets nothing from it (flatten_task_vectors' zeros).  A non-finite entry in a parameter's matrix is a ``ValueError``
+    that names the parameter: one NaN would otherwise spread over every label."""
+    G = np.zeros((len(tasks), len(tasks)), dtype=np.float64)
+    for name in sorted(per_param.keys()):
+        for gram, present in per_param[name]:
+            gram = np.asarray(gram, dtype=np.float64).reshape(len(present), len(present))
+            if not np.isfinite(gram).all():
+                raise ValueError(f"the task Gram of parameter {name!r} is not finite: its stored artifacts hold a NaN or "
+                                 f"Inf (basis, mean or coefficients)")
+            scatter_task_gram(G, gram, present, tasks)
+    return G
+
+
+def _artifact_tasks(per_task) -> List[str]:
+    meta = getattr(per_task, "_meta", None)      # a plan-backed entry names its tasks without being materialised
+    return list(meta["have"]) if meta else list(per_task.keys())
+
+
+def task_gram_from_artifacts(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict], device="cuda",
+                             basis_report: bool = False):
+    """``task_gram`` of a STORE: (G [N, N] fp64 on the host, the task names in sorted order) of the task vectors the
+    stored artifacts reconstruct, ``delta_t = U c_t + mean`` per parameter and region -- what the reference's cluster
+    weighting (flatten_task_vectors clustering.py:55-120, cluster_tasks :198-245) would see after
+    ``reconstruct_task_vectors`` for every task, without a checkpoint and without writing one reconstructed model.
+    Conventions as ``task_gram``: tasks sorted by name, parameters the union over tasks, a parameter a task lacks counts
+    as zeros.  No weight, no scale: ``svd_noise_shrink`` is NOT applied (the reference clusters raw task vectors).
+
+    Entries that ``merge._batched_entry`` accepts -- a fused run's dictionaries, ``adopt_artifacts``' output -- take ONE
+    ``svdq_plan_store_gram`` per distinct plan (``CompressPlan.store_gram``: a pass over the basis and the mean, 2 r + 4
+    bytes per row with an fp16 basis).  Signal and noise entries of a masked run both contribute: their rows are disjoint,
+    so the sum is the Gram of the full reconstructed vectors WHEN the run stored noise regions (svd_include_noise), and of
+    their signal part alone when it did not -- the store then holds nothing of the other rows.  Any other entry goes per
+    (parameter, region, task) through ``merge_parameter`` on that task alone with weight 1.0, and the matrix is formed
+    with torch in fp64.  The per-parameter matrices are added by task name in sorted parameter order
+    (``assemble_task_gram``); a non-finite one is a ``ValueError`` naming the parameter.
+
+    ``basis_report=True``: returns ``(G, tasks, report)`` with report = {"param [region]": max |U^T U - I|}, the
+    orthonormality of every stored (rounded, extended, caller-made) basis -- from the same pass."""
+    from .merge import _batched_entry, merge_parameter
+    from .rtvq import RTVQQuantizer
+    dev = resolve_device(device)
+    names = sorted(compressed_all.keys())
+    tasks = sorted({t for n in names for t in _artifact_tasks(compressed_all[n])})
+    jobs, rest = {}, []      # id(plan) -> (plan batch, {entry index: (name, region, meta)})
+    for name in names:
+        got = _batched_entry(name, compressed_all, bases)
+        if got is None:
+            rest.append(name)
+            continue
+        batch, i, meta = got
+        jobs.setdefault(id(batch.plan), (batch, {}))[1][i] = (name, "masked", meta)
+        if meta["noise"] is not None:
+            nb, j = meta["noise"]
+            jobs.setdefault(id(nb.plan), (nb, {}))[1][j] = (name, "noise", meta)
+    per_param: Dict[str, list] = {}
+    report: Dict[str, float] = {}
+    with torch.cuda.device(dev):
+        for batch, entries in jobs.values():
+            plan = batch.plan
+            out = plan.store_gram(basis_gram=basis_report)
+            G = (out[0] if basis_report else out).cpu().numpy()      # the one device-to-host copy of the plan
+            B = out[1].cpu().numpy() if basis_report else None
+            for i, (name, region, meta) in entries.items():
+                if int(batch.small.rows[i]) <= 0:
+                    continue
+                tasks_i = batch.task_names[i]
+                sel = [q for q, t in enumerate(tasks_i) if t in meta["have"]]
+                per_param.setdefault(name, []).append((G[i][np.ix_(sel, sel)], [tasks_i[q] for q in sel]))
+                if basis_report:
+                    r = int(batch.small.r[i])
+                    report[f"{name} [{region}]"] = float(np.abs(B[i][:r, :r] - np.eye(r)).max()) if r else 0.0
+        quantizer = RTVQQuantizer()      # only dequantizes: the payloads carry their own widths
+        for name in rest:
+            per_task, b = compressed_all[name], bases.get(name) or {}
+            for region, key in (("masked", "masked"), ("noise", "unmasked")):
+                rb = b.get(region)
+                if rb is None:
+                    continue
+                present = sorted(t for t, a in per_task.items() if isinstance(a, dict) and a.get(key) is not None)
+                if not present:
+                    continue
+                rows = int(rb["U_high"].shape[0] if rb["U_high"].dim() == 2 else rb["U_low"].shape[0])
+                # merge_parameter on one task with weight 1.0 is that task's own reconstruction; the region rides in the
+                # "masked" slot so that neither a mask nor noise_shrink comes into it
+                X = torch.stack([merge_parameter(name, {t: {"masked": per_task[t][key]}}, {"masked": rb}, {t: 1.0},
+                                                 quantizer, torch.Size([rows]), device=dev).double()
+                                 for t in present])
+                per_param.setdefault(name, []).append(((X @ X.T).cpu().numpy(), present))
+                if basis_report:
+                    U = torch.cat([u.to(dev).double() for u in (rb["U_high"], rb["U_low"]) if u.dim() == 2 and u.shape[1]],
+                                  dim=1) if rows else torch.zeros((0, 0), dtype=torch.float64, device=dev)
+                    r = int(U.shape[1])
+                    report[f"{name} [{region}]"] = float((U.T @ U - torch.eye(r, dtype=torch.float64, device=dev))
+                                                         .abs().max()) if r else 0.0
+    G = assemble_task_gram(per_param, tasks)
+    return (G, tasks, report) if basis_report else (G, tasks)
+
+
+def cluster_tasks_from_artifacts(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict], k: int,
+                                 method: str = "kmeans", device="cuda") -> Dict[str, int]:
+    """``cluster_tasks`` (clustering.py:198-245) for a store: the labels of the task vectors the stored artifacts
+    reconstruct, from ``task_gram_from_artifacts``."""
+    if method not in ("kmeans", "hierarchical"):
+        raise ValueError(f"Unknown clustering method: {method}")
+    G, tasks = task_gram_from_artifacts(compressed_all, bases, device=device)
+    return cluster_from_gram(G, tasks, k, method)
+
+
 def flatten_task_vectors(task_vectors: Dict[str, Dict[str, torch.Tensor]]) -> Tuple[np.ndarray, List[str]]:
     """Reference clustering.py:55-120: the [N, sum D] feature matrix (rows = tasks in sorted-name order, parameters in
     sorted-name order, zeros where a task lacks a parameter) and the task names.  Kept for API compatibility only:

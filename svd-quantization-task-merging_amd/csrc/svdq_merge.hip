@@ -46,22 +46,8 @@
 // exactly as the reference does on the host (merge.py:123-124); < 0 = the task is not in the set.
 // order   [P or 1][N]: task indices in the order the reference adds them (sorted task names, merge.py:89); NULL = 0..N-1.
 // cbar    [P][n_sets][N] out: columns 0..k-1 the averaged c_high, k..r-1 the averaged dequantized c_low, 0 beyond.
-// coefficient i (< r) of task t of parameter p as the reference holds it in fp32: column i < k the fp16 c_high, else the
-// dequantized c_low
-__device__ __forceinline__ float task_coeff(int p, int t, int i, int n, int k, int stages,
-                                            const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
-                                            const float *__restrict__ scale, const float *__restrict__ zp) {
-    if (i < k) return __half2float(__ushort_as_half(chigh[((size_t)p * n + t) * n + i]));
-    // zeros + sum over stages of (q - zero_point) / scale (rtvq.py:29-36, :85-103)
-    float c = 0.f;
-    const size_t sb = ((size_t)p * n + t) * stages;
-    for (int st = 0; st < stages; ++st) {
-        const float q = (float)codes[(sb + st) * n + (i - k)];
-        c = __fadd_rn(c, __fdiv_rn(__fsub_rn(q, zp[sb + st]), scale[sb + st]));
-    }
-    return c;
-}
-
+// task_coeff -- one task's coefficient as the reference holds it in fp32 -- is svdq_merge_stream.h's (svdq_store_gram.hip
+// reads the coefficients through the same lines).
 __global__ __launch_bounds__(64) void k_merge_coeff(int NT, int stages, int n_sets, int per_param,
                                                     const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
                                                     const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,

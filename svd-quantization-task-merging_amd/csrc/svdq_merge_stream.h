@@ -231,6 +231,22 @@ __device__ __forceinline__ WalkSel<RPL> walk_select(const unsigned (&mk)[RPL], i
 }
 
 // ------------------------------------------------------------------------------------ coefficients and fma chains
+// coefficient i (< r) of task t of parameter p as the reference holds it in fp32: column i < k the fp16 c_high, else the
+// dequantized c_low
+__device__ __forceinline__ float task_coeff(int p, int t, int i, int n, int k, int stages,
+                                            const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
+                                            const float *__restrict__ scale, const float *__restrict__ zp) {
+    if (i < k) return __half2float(__ushort_as_half(chigh[((size_t)p * n + t) * n + i]));
+    // zeros + sum over stages of (q - zero_point) / scale (rtvq.py:29-36, :85-103)
+    float c = 0.f;
+    const size_t sb = ((size_t)p * n + t) * stages;
+    for (int st = 0; st < stages; ++st) {
+        const float q = (float)codes[(sb + st) * n + (i - k)];
+        c = __fadd_rn(c, __fdiv_rn(__fsub_rn(q, zp[sb + st]), scale[sb + st]));
+    }
+    return c;
+}
+
 // the transposed coefficient image C[column][stride]: the coefficients of a column side by side, one per set or task;
 // slots past n_valid are 0.  cbar_p [n_valid][n]: the parameter's coefficient vectors.
 __device__ __forceinline__ void stage_coeffs(float *C, const float *__restrict__ cbar_p, int n, int n_valid, int stride,

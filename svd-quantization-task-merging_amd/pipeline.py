@@ -518,6 +518,34 @@ class CompressPlan:
                                                  _stream_ptr()), who)
             return self.fetch_small() if fetch else None
 
+    # ---- the task Gram of what the plan's stored artifacts reconstruct (svdq_store_gram.hip)
+    def store_gram(self, rows_dev: Optional[torch.Tensor] = None, basis_gram: bool = False):
+        """Per parameter, the N x N inner products of the task vectors the plan's artifacts reconstruct --
+        ``delta_t = U c_t + mean`` with the fp16 c_high and the dequantized c_low of the small buffer -- from ONE pass over
+        the basis and the mean (svdq_plan_store_gram: two launches, nothing reconstructed, no noise_shrink).  Returns a
+        float64 device tensor [P, N, N]; with ``basis_gram`` also [P, 33, 33]: ``A^T A`` of ``A = [U | mean]`` in rows /
+        columns [0, r] (row / column r = the mean; absent on an uncentred plan), zeros elsewhere.  ``rows_dev``: int64 [P]
+        rows per parameter; None = the rows field of the small buffer, read on the device.  Asynchronous on the current
+        stream; the work buffer is cached on the plan, the outputs are the caller's own."""
+        who = "svdq_plan_store_gram"
+        if self.basis is None:
+            raise ValueError(f"{who}: a gram_only plan holds no artifacts")
+        if rows_dev is None:
+            rows_dev = self.small[self.layout.rows_off:self.layout.rows_off + 8 * self.P].view(torch.int64)
+        elif (rows_dev.dtype is not torch.int64 or rows_dev.device != self.device or not rows_dev.is_contiguous()
+              or rows_dev.numel() != self.P):
+            raise ValueError(f"{who}: rows_dev must be a contiguous int64 tensor of {self.P} entries on {self.device}")
+        work = getattr(self, "_store_gram_work", None)
+        need = int(self.lib.svdq_plan_store_gram_work_bytes(self._h))
+        if work is None or work.numel() < need:
+            work = self._store_gram_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            G = torch.empty((self.P, self.N, self.N), dtype=torch.float64, device=self.device)
+            B = torch.empty((self.P, 33, 33), dtype=torch.float64, device=self.device) if basis_gram else None
+            nat.check(self.lib.svdq_plan_store_gram(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                    _ptr(self.mean), _ptr(work), _ptr(G), _ptr(B), _stream_ptr()), who)
+        return (G, B) if basis_gram else G
+
     # ---- the basis grown by what new tasks add outside its span (svdq_plan_extend.hip)
     def _extend_args(self, who, table, base_table, index_table, rows_dev):
         if self.basis is None:

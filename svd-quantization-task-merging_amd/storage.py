@@ -362,6 +362,77 @@ def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[s
     return result
 
 
+def remerge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None, weighting: Optional[str] = None,
+                           cluster_k: Optional[int] = None, performance_file: Optional[str] = None,
+                           temperature: Optional[float] = None, device: str = "cuda", update_store: bool = False
+                           ) -> Dict[str, Any]:
+    """Merge a stored artifact set again under another weighting -- the reference's Steps 6 and 7 (compute_weights
+    weighting.py:266-329, cluster_tasks clustering.py:198-245, merge_all_parameters / merge_with_clustering merge.py:304-626)
+    on a store, without the fine-tuned checkpoints.  load_all_artifacts -> adopt_artifacts -> weights -> merge ->
+    apply_merged_deltas.  Masks are not stored (reload.py:204-205): exact for unmasked runs, as ``reconstruct_from_artifacts``.
+
+    ``weighting``: None = the stored ``diagnostics["task_weights"]`` -- then this is ``reconstruct_from_artifacts`` bit
+    for bit; "uniform" / "performance" = ``compute_weights`` over the stored tasks (``performance_file``;
+    ``temperature`` None = the stored config's svd_weighting_temperature); "cluster" = the tasks are clustered on the
+    Gram of what the store reconstructs (``cluster_tasks_from_artifacts``, k-means, ``cluster_k`` None = the stored
+    config's svd_cluster_k), the weights are ``compute_weights(..., cluster_assignments=)`` and the merge is
+    ``merge_with_clustering``.  ``base_model_path``: a path or a state dict.
+
+    Returns {"merged_state_dict", "weights", "cluster_assignments" (None unless "cluster"), "diagnostics", "config"}.
+    The store's files are left alone unless ``update_store``: then diagnostics.json is rewritten with the weights used
+    (``task_weights``) and the labels (``cluster_assignments``; dropped when the weighting is not "cluster"), and
+    clusters.json is written (or removed) beside it.  Nothing else of the store is touched."""
+    from .clustering import cluster_tasks_from_artifacts
+    from .driver import adopt_artifacts
+    from .merge import apply_merged_deltas, merge_all_parameters, merge_with_clustering
+    from .weighting import compute_weights
+    if weighting not in (None, "uniform", "performance", "cluster"):
+        raise ValueError(f"Unknown weighting strategy: {weighting}")
+    art = load_all_artifacts(artifact_dir, device=device)
+    config, diagnostics = art["config"], art["diagnostics"]
+    stored = _stored_tasks(art["compressed"], diagnostics)
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
+              if d.get("original_shape") is not None}
+    assignments = None
+    if weighting is None:      # reconstruct_from_artifacts' own lines
+        tasks = list(diagnostics.get("task_weights", {}).keys())
+        if not tasks:
+            tasks = list(next(iter(compressed.values())).keys())
+        weights = diagnostics.get("task_weights") or {t: 1.0 / len(tasks) for t in tasks}
+    else:
+        if not stored:
+            raise ValueError(f"{artifact_dir} holds no task")
+        T = float(config.svd_weighting_temperature if temperature is None else temperature)
+        if weighting == "cluster":
+            k = int(config.svd_cluster_k if cluster_k is None else cluster_k)
+            assignments = cluster_tasks_from_artifacts(compressed, bases, k, method="kmeans", device=device)
+        weights = compute_weights(stored, weighting_strategy=weighting, performance_file=performance_file, temperature=T,
+                                  cluster_assignments=assignments)
+    if assignments is not None:
+        merged = merge_with_clustering(compressed, bases, {}, weights, assignments, shapes, config, device=device)
+    else:
+        merged = merge_all_parameters(compressed, bases, {}, weights, shapes, config, device=device, verbose=False)
+    base = _load_base(base_model_path, device)
+    out = apply_merged_deltas(base, merged, device=device, verbose=False)
+    if output_path:
+        torch.save(out, output_path)
+    if update_store:
+        diagnostics["task_weights"] = {t: float(w) for t, w in weights.items()}
+        clusters = os.path.join(artifact_dir, "clusters.json")
+        if assignments is not None:
+            diagnostics["cluster_assignments"] = {t: int(c) for t, c in assignments.items()}
+            with open(clusters, "w") as f:
+                json.dump(diagnostics["cluster_assignments"], f, indent=2)
+        else:
+            diagnostics.pop("cluster_assignments", None)
+            if os.path.exists(clusters):
+                os.remove(clusters)
+        save_diagnostics(diagnostics, artifact_dir)
+    return {"merged_state_dict": out, "weights": weights, "cluster_assignments": assignments,
+            "diagnostics": diagnostics, "config": config}
+
+
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
     """Reference reload.py:60-139: a pre-saved merged_state_dict.pt in the artifact directory wins; otherwise the
     merged model is rebuilt from bases + coefficients + the base model named in the stored config."""
