@@ -77,30 +77,12 @@ def oracle_case(sq, orc, dev, seed: int, c: int):
     # case: the coefficients are the projections on the DEVICE's own (rounded) basis, and the device's payloads are
     # what the reference quantizer (the C oracle) makes of the device's own c_low, bit for bit.
     if r > 0:
-        Uh, Ul, mu = plan.basis_tensors(0, k, r, D)
-        U = torch.cat([Uh, Ul], dim=1).double().cpu().numpy() if (k > 0 and r > k) else \
-            (Uh if k > 0 else Ul).double().cpu().numpy()
-        mu32 = mu.flatten().cpu().numpy() if mu is not None else None
+        from helpers import own_basis, own_projection_mismatch
+        U, mu32 = own_basis(plan, 0, k, r, D)
         for t in range(N):
-            x32 = deltas[t].numpy() - mu32 if mu32 is not None else deltas[t].numpy()      # fp32, like compress.py:44
-            want = U.T @ x32.astype(np.float64)
-            got = sm.coef[0, t, :r].astype(np.float64)
-            # column i is U_i = Tc v_i / sigma_i formed in fp32: its own error is ~eps32 sigma_0 / sigma_i, and the
-            # coefficient (closed form sigma_i v_i + the fp16-rounding correction) differs from the explicit projection
-            # on the stored column by that much of |x| (seed 5001 case 805: sigma_30 = 5e-4 sigma_0, 3e-5 |x|)
-            # The model has no ceiling of its own: round 3 had capped it at 1e-3 |x| by hand, which a direction at
-            # 1.9e-6 sigma_0 -- above the 1e-6 null threshold, below the 1e-5 floor under which not even singular values
-            # are compared; its fp32-formed column is only ~97 % the singular vector -- exceeded with 1.75e-3 |x| (seed 4
-            # case 37: D = 31 < N = 32; model: 0.16 |x|).  Capped where the model reaches 1e-2 (sigma_i = 3e-5 sigma_0);
-            # such a direction holds < 1e-9 of the energy and the reconstructions still agree to MSE 3e-10.
-            sg = np.maximum(sm.sigma[0, :r].astype(np.float64), 1e-30)
-            tol = float(np.linalg.norm(x32)) * np.minimum(1e-5 + 3e-7 * sg[0] / sg, 1e-2) + 1e-12
-            if mu32 is not None:      # the rows of T - mean sum to a few ulp(mean), not to 0; the device removes that
-                tol = tol + 2.4e-7 * float(np.linalg.norm(mu32))      # component (1 / sqrt(N) is deflated), a GEMV keeps it
-            if np.isfinite(want).all() and not np.all(np.abs(got - want) <= tol):
-                bad_i = int(np.argmax(np.abs(got - want) / tol))
-                msgs.append(f"projection on the device's basis: task {t} column {bad_i}, |dc| "
-                            f"{abs(got[bad_i] - want[bad_i]):.2e} (tol {tol[bad_i]:.1e})")
+            m = own_projection_mismatch(U, mu32, deltas[t], sm.coef[0, t, :r], sm.sigma[0, :r], t)      # tolerance model there
+            if m:
+                msgs.append(m)
                 break
             if r > k:
                 art = sq.pipeline.task_artifact(plan, sm, 0, t)["c_low_quant"]

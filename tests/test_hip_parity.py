@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from helpers import load_golden, bits_equal, align_signs, as_tensors, rel_err
+from helpers import check_pipeline_quantizer as _check_pipeline_quantizer
 
 pytestmark = pytest.mark.gpu
 
@@ -167,23 +168,6 @@ def _reconstruct_all(sq, plan, sm, p, N):
         out.append(sq.reconstruct_from_coefficients(art["c_high_fp16"].to(dev).float(), c_low, U_high, U_low, dev,
                                                     mean=mean).cpu().numpy())
     return np.stack(out)
-
-
-def _check_pipeline_quantizer(orc, plan, sm, p):
-    """Kernel-level parity of the in-pipeline (one lane per task) quantizer: the oracle applied to
-    OUR fp32 coefficients must give OUR codes / scale / zero_point bit for bit, inf and NaN included."""
-    k, r = int(sm.k[p]), int(sm.r[p])
-    nl = r - k
-    for t in range(plan.N):
-        want = orc.rtvq_quantize(sm.coef[p, t, k:r], plan.bits, plan.S)
-        if nl == 0:
-            continue
-        assert np.array_equal(sm.codes[p, t, :, :nl], want["codes"]), (p, t)
-        assert bits_equal(sm.scale[p, t], want["scale"]), (p, t, sm.scale[p, t], want["scale"])
-        assert bits_equal(sm.zero_point[p, t], want["zero_point"]), (p, t)
-        np.testing.assert_allclose(sm.residual_norm[p, t], want["residual_norm"], rtol=1e-5, equal_nan=True)
-        c16 = torch.from_numpy(sm.coef[p, t, :k].copy()).half().numpy()
-        assert np.array_equal(sm.c_high[p, t, :k].view(np.uint16), c16.view(np.uint16))
 
 
 def _compare_recon(ours, ref, nl):
