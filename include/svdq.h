@@ -815,6 +815,97 @@ int svdq_plan_store_gram(const svdq_plan *plan, const int64_t *rows_dev, const v
                          const float *mean_dev, void *work_dev, double *task_gram_dev /*[P][N][N]*/,
                          double *basis_gram_dev /*NULL or [P][33][33]*/, void *stream);
 
+/* ---- consolidate a STORE: bases, rank and mean re-derived from the artifacts alone (the one statement of the contract;
+ *      the sources point here).  No reference counterpart.  svdq_plan_extend_basis appends columns (singular values no
+ *      longer descending, the k + M <= 32 room used up), a task cannot be dropped from a store (its share stays in the
+ *      mean), and a store cannot be taken to another energy threshold, max_rank, low_bits or stage count without the
+ *      fine-tuned checkpoints.  These entry points return a store to the form a fresh compress run of the tasks it
+ *      reconstructs would give it, without materialising a task model: per entry delta_t = A c'_t, so the SVD of the kept
+ *      tasks is an N' x N' problem on top of A^T A, plus one linear map of the stored rows, U' = A W.
+ *   call order      per source plan: svdq_plan_store_gram(src, ..., basis_gram_dev) -> svdq_plan_consolidate_eig ->
+ *                   svdq_plan_rebase.  Four launches (the streaming Gram and its finish, the eigen stage, the streaming
+ *                   rebase); none copies to the host, allocates or synchronises: capturable like every other entry point.
+ *   the two plans   src: the plan that holds the store (any compress route or svdq_plan_import).  dst: a plan created with
+ *                   the SAME rows per parameter and the same basis element type (cfg.fp16), N' task slots and the settings
+ *                   the consolidated store is to have: cfg.center, energy_threshold, max_rank, low_bits (per parameter:
+ *                   svdq_plan_set_low_bits) and rtvq_stages.  No conversion of the element type is offered.
+ *   keep            int32 [P][N']: destination slot j of parameter p takes source slot keep[p][j]; -1 = the slot is absent
+ *                   (this is how tasks are dropped).  keep_host is what the call validates (the device cannot refuse
+ *                   before a launch), keep_dev holds the same values on the device and is what the kernel reads.
+ *   per entry p     (one parameter region) with A = [U_high | U_low | mean] [D, r + 1] as stored (an uncentred source has
+ *                   no mean column) and M = A^T A as svdq_plan_store_gram forms it (fp32 sums inside blocks of at most 256
+ *                   rows, fp64 across blocks, a fixed order):
+ *     coefficients  b_j = [c_j ; 1], c_j = the fp16 c_high then the dequantized c_low of source slot keep[p][j] -- the
+ *                   merge's own dequantizing lines, exactly the values every consumer reconstructs from.
+ *     centring      bbar = the mean of the kept b_j in task order (fp64) on a centred destination, else 0;
+ *                   Bc = B - bbar 1^T.  A centred source going to an uncentred destination keeps the 1 row in B (the old
+ *                   mean is folded into the data); the reverse direction is allowed too.
+ *     eigen stage   K = Bc^T M Bc in fp64, the fp64 Jacobi of the compressor's eigen stage, lambda descending, each
+ *                   eigenvector's sign fixed so that its largest-magnitude component is positive.
+ *     keep rule     M carries a relative error gamma = (256 + r + 3) 2^-24 against |A|^T |A|, and |A|^T |A|[i][j] <=
+ *                   sqrt(M_ii M_jj), so ||dK|| <= eta := gamma sum_j g_j^2 with g_j = sum_i sqrt(M_ii) |Bc[i][j]| (fp64, on
+ *                   the device).  Direction i is kept iff lambda_i > max(4 eta, min_sigma^2 lambda_0), i < min(kept
+ *                   tasks, D) and lambda_i > 0: above 4 eta the true eigenvalue is positive and within 25 % of the computed
+ *                   one; below it the column A w_i / sigma_i is amplified rounding noise.  r' = the number kept.
+ *                   Unresolved directions are DROPPED, not kept as zero or completion columns (svdq_plan_import accepts
+ *                   r < min(rows, N)); dropped_energy = the sum of the dropped lambda_i, each clipped at 0.
+ *                   min_sigma: finite and >= 0, 0 = the noise floor alone.
+ *     rank rule     k' and energy_retained: the reference's fp32 cumulative rule (basis.py:147-156, :199-211) on
+ *                   sigma' = sqrt(lambda[:r']), with svdq_eig_rank_select's fp64 form when the fp32 sum overflows.
+ *     new artifacts W = Bc V_r' Sigma^-1 [r (+ 1)][r'], U' = A W split at k' into U_high' and U_low', mean' = A bbar on a
+ *                   centred destination.  Coefficients: the closed form c'_j[i] = sgn_i sigma_i V[j][i], fp64 then fp32 --
+ *                   the coefficients of the UNROUNDED U'.  By construction A W c'_j + A bbar = A b_j minus the dropped part,
+ *                   whatever the accuracy of V; projecting onto the rounded columns instead would make the reconstruction
+ *                   depend on how orthonormal they came out, so that is not done.  Then compress_single_task's tail
+ *                   through the compressor's own epilogue: coef = the fp32 c', c_high = fp16(c'[:k']), c_low =
+ *                   RTVQ(bits[p], stages)(c'[k':r']) bit for bit.  Absent destination slots: zeros in every field.
+ *     non-finite    a non-finite entry of M or of a kept coefficient flags the entry as every eigen stage does
+ *                   (svdq_eig_rank_select above): energy and sigma are NaN, k = min(1, r), r = min(D, kept tasks), rows = D,
+ *                   W is zero, no Jacobi sweep runs, and svdq_plan_rebase writes nothing of the entry.
+ *     nothing to do rows == 0 or no kept task: nothing of p is read, the destination's fields are zeros (rows = 0: every
+ *                   consumer skips the entry), and no row is written.
+ *   dst_small_dev   the destination plan's small buffer: sigma / k / r / energy / rows / c_high / codes / scale /
+ *                   zero_point / residual_norm / coef / status of EVERY entry are written on every run.
+ *   rebase_dev      svdq_plan_consolidate_layout bytes, 16-byte aligned; every field of every entry is written by
+ *                   svdq_plan_consolidate_eig, so the buffer is the same bytes in every run.
+ *   svdq_plan_rebase   one streaming launch over the SOURCE plan's work units, one wavefront each, the geometry and
+ *                   staging of svdq_plan_store_gram (blocks of 256 rows up to 16 source slots, 128 above; the mean rows
+ *                   beside the basis rows; the next block's loads in flight during compute).  Row d of [U' | mean'] =
+ *                   row d of A times [W | bbar] on the matrix pipe (v_mfma_f32_16x16x4_f32, basis elements widened to fp32
+ *                   exactly): fp32 sums over the source columns in one fixed order, four columns per instruction in column
+ *                   order, U_high then U_low, the mean column last -- the same bits in every run (how the matrix pipe
+ *                   orders the four products of one instruction is the hardware's; the error is that of r + 1 fp32 terms).  Results are rounded to the element type (fp16: nearest
+ *                   even; mean': fp32) and go straight into the DESTINATION plan's buffers at svdq_plan_basis_layout's
+ *                   offsets: U_high' at slab_off[p], U_low' at slab_off[p] + align256(rows k' e), mean' at mean_off[p].
+ *                   k', r' and W are read from rebase_dev ON THE DEVICE.  Nothing is written outside the three ranges of a
+ *                   parameter -- not the gap between U_high' and U_low', not a slab's or the buffers' tails.  The source's
+ *                   buffers are only read.  Reads 2 r + 4 and writes 2 r' + 4 bytes per row with an fp16 basis.
+ *   errors          SVDQ_EINVAL before anything is launched: a NULL plan or buffer; a NULL mean on a centred source (or
+ *                   destination); tables off 8 bytes, buffers off 16; a destination plan whose parameter count, rows or
+ *                   element type differ from the source's; N' > SVDQ_MAX_TASKS; a keep entry outside [-1, N);
+ *                   min_sigma negative or not finite.
+ *   Any N, N' <= SVDQ_MAX_TASKS (the 8-, 16- and 32-slot instantiations of the source), fp16 or fp32 basis, fused or
+ *   adopted source plans. */
+typedef struct svdq_consolidate_layout {
+    int64_t w_off;          /* float  [P][33][32] W[source column][new column]; row r = the mean column of a centred source */
+    int64_t bbar_off;       /* float  [P][33]     bbar over the source columns (zeros on an uncentred destination)        */
+    int64_t r_off;          /* int32  [P]         r': directions kept                                                      */
+    int64_t k_off;          /* int32  [P]         k'                                                                       */
+    int64_t live_off;       /* int32  [P]         1 = svdq_plan_rebase writes the entry (rows > 0, a kept task, finite)    */
+    int64_t dropped_off;    /* double [P]         dropped_energy                                                           */
+    int64_t eta_off;        /* double [P]         eta, the bound on ||dK||                                                 */
+    int64_t lambda_off;     /* double [P][32]     eigenvalues of K over the kept tasks, descending                         */
+    int64_t total_bytes;
+} svdq_consolidate_layout;
+int svdq_plan_consolidate_layout(const svdq_plan *plan, svdq_consolidate_layout *out);
+int svdq_plan_consolidate_eig(const svdq_plan *src_plan, const svdq_plan *dst_plan, const int32_t *keep_host /*[P][N']*/,
+                              const int32_t *keep_dev /*[P][N']*/, const int64_t *rows_dev, const void *src_small_dev,
+                              const double *basis_gram_dev /*[P][33][33]*/, float min_sigma, void *dst_small_dev,
+                              void *rebase_dev, void *stream);
+int svdq_plan_rebase(const svdq_plan *src_plan, const svdq_plan *dst_plan, const int64_t *rows_dev,
+                     const void *src_small_dev, const void *src_basis_dev, const float *src_mean_dev,
+                     const void *rebase_dev, void *dst_basis_dev, float *dst_mean_dev, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

@@ -16,7 +16,7 @@ from .rtvq import (RTVQQuantizer, asymmetric_quantization, asymmetric_dequantiza
 from .basis import (construct_basis, construct_masked_basis, select_rank, compute_energy_spectrum, compute_svd,
                     stack_and_center, compute_energy_statistics)
 from .compress import (project_to_basis, compress_single_task, compress_masked_regions, compress_parameter,
-                       compress_all_parameters, project_all_parameters, extend_bases)
+                       compress_all_parameters, project_all_parameters, extend_bases, consolidate_bases)
 from .mask_loader import (combine_masks, compute_union_mask, compute_intersection_mask, compute_majority_mask,
                           apply_mask_to_tensor, get_unmasked_portion, reconstruct_from_masked, load_task_masks,
                           load_single_mask, load_tall_mask_file, state_dict_to_vector, vector_to_state_dict,
@@ -37,7 +37,8 @@ from .storage import (save_basis, load_basis, save_compressed_coefficients, load
                       save_diagnostics, load_diagnostics, save_config, load_config, save_all_artifacts,
                       load_all_artifacts, save_merged_model, reconstruct_from_artifacts,
                       reload_merged_model_from_artifacts, reconstruct_tasks_from_artifacts,
-                      reconstruct_tasks_from_artifacts_masked, add_tasks_to_artifacts, remerge_from_artifacts)
+                      reconstruct_tasks_from_artifacts_masked, add_tasks_to_artifacts, remerge_from_artifacts,
+                      consolidate_artifacts)
 from .task_vector_loader import (load_checkpoint, compute_task_vector, compute_task_vectors, load_task_vectors,
                                  get_parameter_names, organize_by_parameter, flatten_task_deltas,
                                  get_task_checkpoint_paths)

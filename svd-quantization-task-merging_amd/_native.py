@@ -44,6 +44,11 @@ class SvdqExtendLayout(Structure):
                                        "total_bytes")]
 
 
+class SvdqConsolidateLayout(Structure):
+    _fields_ = [(n, c_int64) for n in ("w_off", "bbar_off", "r_off", "k_off", "live_off", "dropped_off", "eta_off",
+                                       "lambda_off", "total_bytes")]
+
+
 MAX_NEW_TASKS = 8      # SVDQ_MAX_NEW_TASKS: new tasks per svdq_plan_residual_gram / svdq_plan_extend_basis call
 
 
@@ -160,6 +165,11 @@ SIGNATURES = {
     "svdq_plan_store_gram_work_bytes": (c_int64, [c_void_p]),
     "svdq_plan_store_gram": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "svdq_plan_consolidate_layout": (c_int32, [c_void_p, POINTER(SvdqConsolidateLayout)]),
+    "svdq_plan_consolidate_eig": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                            c_void_p, c_void_p, c_void_p]),
+    "svdq_plan_rebase": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
     "svdq_mask_expand": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "svdq_hbm_probe": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
 }

@@ -486,3 +486,164 @@ def extend_bases(task_vectors: Dict[str, Dict[str, torch.Tensor]], masks: Option
     captured = {t: (1.0 - e_sum[t] / x_sum[t]) if x_sum[t] > 0.0 else 1.0 for t in tasks}
     return {"bases": new_bases, "compressed": {n: out[n] for n in sorted(out)}, "columns": columns,
             "captured_energy": captured, "skipped": sorted(rest)}
+
+
+# ---- a store brought back to the form a fresh compress run would give it (include/svdq.h, svdq_plan_consolidate_eig)
+def stored_task_names(compressed_all: Dict[str, Dict]) -> list:
+    """The task names the coefficient dictionaries hold, sorted."""
+    return sorted({t for per_task in compressed_all.values() if isinstance(per_task, dict) for t in per_task})
+
+
+def consolidate_task_list(compressed_all: Dict[str, Dict], tasks=None) -> list:
+    """The kept task list of ``consolidate_bases``: ``tasks`` (None = every stored task), SORTED BY NAME -- the order
+    ``adopt_artifacts``, ``task_gram_from_artifacts`` and the merge's weight rows use for a store's tasks, not the order
+    of ``diagnostics["task_weights"]``.  It is the destination's slot order and so the order of the sum behind bbar; the
+    artifacts are keyed by name, so nothing a consumer reads depends on it.  ``ValueError`` on a task the store does not
+    hold and on an empty list; a pure function of its arguments (no GPU)."""
+    stored = stored_task_names(compressed_all)
+    kept = stored if tasks is None else sorted(set(tasks))
+    for t in kept:
+        if t not in stored:
+            raise ValueError(f"task {t!r} is not in the store, which holds {stored}")
+    if not kept:
+        raise ValueError("no task to keep: consolidating a store needs at least one of its tasks")
+    if len(kept) > nat.MAX_TASKS:
+        raise ValueError(f"{len(kept)} tasks: at most {nat.MAX_TASKS}")
+    return kept
+
+
+def check_consolidate_room(bases: Dict[str, Dict]) -> None:
+    """``ValueError`` for a stored region whose r columns and mean exceed the 33 rows of the rebase table (r + 1 > 33);
+    from shapes and scalars alone (no GPU)."""
+    for name in sorted(bases):
+        for rk, _, b in _regions(bases[name]):
+            r = int(b["k"]) + (int(b["U_low"].shape[1]) if b["U_low"].dim() == 2 else 0)
+            if r + 1 > nat.MAX_TASKS + 1:
+                raise ValueError(f"parameter {name!r} [{rk}]: r + 1 = {r} + 1 > {nat.MAX_TASKS + 1}")
+
+
+def keep_row(entry_tasks, kept) -> list:
+    """One row of the keep table: for every kept task its slot in ``entry_tasks`` (a plan entry's task order), -1 where
+    the entry does not hold the task."""
+    pos = {t: j for j, t in enumerate(entry_tasks)}
+    return [pos.get(t, -1) for t in kept]
+
+
+def unquantizable_slots(scale, zero_point, slots) -> list:
+    """The slots of ``slots`` whose c_low the quantizer could not represent: a stage's scale is not finite or is 0, or its
+    zero point is not finite (``scale`` / ``zero_point``: [N][S] of one entry).  The reference's affine quantizer has
+    scale = (2^b - 1) / (max - min) with no guard (rtvq.py:17-18): a stage whose input has no range -- a single element, or
+    residuals of an earlier stage that came out equal, which two elements do more often than not -- gives 1 / 0, and what
+    it dequantizes to is NaN.  A pure function (numpy)."""
+    import numpy as np
+    sc, zp = np.asarray(scale, dtype=np.float32), np.asarray(zero_point, dtype=np.float32)
+    return [j for j in slots if not (np.isfinite(sc[j]).all() and (sc[j] != 0).all() and np.isfinite(zp[j]).all())]
+
+
+def promoted_entry(basis: Dict, coef, slots) -> Tuple[Dict, Dict]:
+    """One region whose c_low the quantizer cannot represent, stored on the high side instead: U_high' = [U_high | U_low],
+    an empty U_low, k' = r', energy_retained = 1 (every kept direction is a high one), and per slot of ``slots`` the
+    artifact {c_high_fp16 = fp16(coef[slot][:r']), c_low_quant = the quantizer's empty payload} -- fp16 holds what an
+    affine code without a range cannot (``extend_bases`` puts its new columns on the high side for the same reason).
+    ``coef``: the entry's fp32 coefficients [N][N].  Returns (basis', {slot: artifact}); the inputs are not touched."""
+    import numpy as np
+    k, n_low = int(basis["k"]), int(basis["U_low"].shape[1])
+    r = k + n_low
+    out = dict(basis)
+    out["U_high"] = torch.cat([basis["U_high"], basis["U_low"]], dim=1).contiguous()
+    out["U_low"] = basis["U_low"][:, :0].contiguous()
+    out["k"] = r
+    out["energy_retained"] = 1.0 if r > 0 else 0.0
+    arts = {}
+    for j in slots:
+        c = torch.from_numpy(np.ascontiguousarray(np.asarray(coef, dtype=np.float32)[j, :r])).half()
+        arts[j] = {"c_high_fp16": c, "c_low_quant": None}
+    return out, arts
+
+
+def consolidate_bases(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict], config, tasks=None,
+                      min_sigma: float = 0.0, device: str = "cuda") -> Dict:
+    """Re-derive bases, rank, mean and coefficients of a store from its artifacts alone -- after ``extend_bases`` grew it,
+    to drop tasks, or to take it to another ``svd_energy_threshold`` / ``svd_max_rank`` / ``svd_low_bits`` /
+    ``svd_rtvq_stages`` / ``svd_center`` -- without the fine-tuned checkpoints and without materialising a task model
+    (include/svdq.h, svdq_plan_consolidate_eig: per plan the store Gram, the eigen stage and the streaming rebase).
+
+    ``compressed_all`` / ``bases``: whatever ``adopt_artifacts`` accepts (the dictionaries ``load_all_artifacts``
+    returns, or a fused run's).  ``config``: the settings of the consolidated store.  ``tasks``: the tasks to keep
+    (None = all).  ``min_sigma``: directions below ``min_sigma * sigma_0`` are dropped besides those below the noise
+    floor of the stored Gram.  ``ValueError`` before any GPU work: an unknown task, an empty kept list, a stored region
+    with r + 1 > 33.
+
+    Returns {"bases", "compressed"} in the reference's dictionary layouts (ready for ``save_all_artifacts``; ``N``,
+    ``singular_values`` -- descending again --, ``k`` and ``energy_retained`` set; signal and noise regions are entries
+    of their own), "columns": {(param, region): (r, r')}, "dropped_energy": {(param, region): sum of the dropped
+    eigenvalues}, "noise_floor": {(param, region): eta, the bound on the error of the stored Gram's K; directions are
+    kept above 4 eta}, "promoted": {(param, region): (k' of the rank rule, r')} for regions whose c_low the quantizer
+    could not represent for some kept task (``unquantizable_slots``) and which are therefore stored with all r' columns
+    on the high side (``promoted_entry``) -- no store with non-finite coefficients is handed out; a coefficient that is
+    non-finite even so raises ``NonFiniteInput`` --, "skipped": the parameters ``adopt_artifacts`` declines -- they stay on the per-parameter route, their
+    artifacts are handed back as they came."""
+    from .driver import adopt_artifacts
+    from .merge import _batched_entry
+    import numpy as np
+    from .pipeline import CompressPlan, NonFiniteInput, basis_dict, task_artifact
+    kept = consolidate_task_list(compressed_all, tasks)
+    check_consolidate_room(bases)
+    dev = resolve_device(device)
+    a_bases, a_comp = adopt_artifacts(bases, compressed_all, config, device=dev)
+    names = sorted(compressed_all.keys())
+    jobs, skipped = {}, []      # id(plan) -> (plan batch, {entry index: (name, region)})
+    for name in names:
+        got = _batched_entry(name, a_comp, a_bases)
+        if got is None:
+            skipped.append(name)
+            continue
+        batch, i, meta = got
+        jobs.setdefault(id(batch.plan), (batch, {}))[1][i] = (name, "masked")
+        if meta["noise"] is not None:
+            nb, j = meta["noise"]
+            jobs.setdefault(id(nb.plan), (nb, {}))[1][j] = (name, "noise")
+    new_bases = {n: bases[n] for n in bases if n in skipped or n not in compressed_all}
+    new_comp: Dict[str, Dict] = {n: compressed_all[n] for n in skipped}
+    columns, dropped, floor, promoted = {}, {}, {}, {}
+    by_param = getattr(config, "svd_low_bits_by_param", None)
+    with torch.cuda.device(dev):
+        for batch, entries in jobs.values():
+            src = batch.plan
+            keep = [keep_row(batch.task_names[i], kept) if i in entries else [-1] * len(kept) for i in range(src.P)]
+            bits = [int(by_param(batch.entries[i][0])) if by_param is not None else int(config.svd_low_bits)
+                    for i in range(src.P)]
+            dst = CompressPlan(src.rows, len(kept), energy_threshold=config.svd_energy_threshold,
+                               max_rank=config.svd_max_rank, center=config.svd_center, fp16=src.fp16, low_bits=bits,
+                               rtvq_stages=config.svd_rtvq_stages, device=dev, workspace=False)
+            try:
+                sm, tab = src.consolidate(dst, keep, min_sigma=min_sigma)
+            except NonFiniteInput as e:
+                bad = [f"{batch.entries[i][0]} [{batch.entries[i][1]}]" for i in e.indices]
+                raise NonFiniteInput(e.indices, "consolidate_bases: the stored artifacts of " + ", ".join(bad) +
+                                     " contain non-finite values") from None
+            for i, (name, region) in entries.items():
+                art_key = "masked" if region == "masked" else "unmasked"
+                columns[(name, region)] = (int(batch.small.r[i]), int(tab.r[i]))
+                dropped[(name, region)] = float(tab.dropped[i])
+                floor[(name, region)] = float(tab.eta[i])
+                entry = basis_dict(dst, sm, i)
+                entry["N"] = sum(1 for s in keep[i] if s >= 0)      # the kept tasks that hold the region
+                slots = [j for j in range(len(kept)) if keep[i][j] >= 0]
+                rn, kn = int(tab.r[i]), int(tab.k[i])
+                arts = {j: task_artifact(dst, sm, i, j) for j in slots}
+                if rn > kn and unquantizable_slots(sm.scale[i], sm.zero_point[i], slots):
+                    entry, high = promoted_entry(entry, sm.coef[i], slots)
+                    for j in slots:      # the quantizer's own payload of an empty c_low, with this entry's settings
+                        q = dict(arts[j]["c_low_quant"])
+                        q.update(payloads=[], original_shape=torch.Size([0]))
+                        arts[j] = {"c_high_fp16": high[j]["c_high_fp16"], "c_low_quant": q}
+                    promoted[(name, region)] = (kn, rn)
+                if not np.isfinite(sm.coef[i][slots, :rn]).all():
+                    raise NonFiniteInput([i], f"consolidate_bases: {name} [{region}]: non-finite coefficients")
+                new_bases.setdefault(name, {"masked": None, "noise": None})[region] = entry
+                per_task = new_comp.setdefault(name, {})
+                for j in slots:
+                    per_task.setdefault(kept[j], {"masked": None, "unmasked": None})[art_key] = arts[j]
+    return {"bases": new_bases, "compressed": {n: new_comp[n] for n in sorted(new_comp)}, "columns": columns,
+            "dropped_energy": dropped, "noise_floor": floor, "promoted": promoted, "skipped": sorted(skipped)}

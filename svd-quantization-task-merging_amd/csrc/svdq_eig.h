@@ -219,7 +219,8 @@ __device__ void eig_param(double *__restrict__ lds, int p, int tid, int64_t D,
     const int r = (int)(D < (int64_t)n ? D : (int64_t)n);
     EIG_STAMP(4);
     if (tid == 0) {
-        // basis.py:147-156 and :199-211, fp32 like the reference (threshold compared as fp32)
+        // basis.py:147-156 and :199-211, fp32 like the reference (threshold compared as fp32).  cs_rank_rule of
+        // svdq_consolidate.hip restates these lines down to the fp64 form below: a change here is a change there.
         float S[NMAX], cum[NMAX];
         float total = 0.f;
         for (int i = 0; i < r; ++i) {

@@ -181,6 +181,48 @@ def extend_views(host: np.ndarray, L, P: int) -> ExtendArtifacts:
                            xnorm=view(L.xnorm_off, np.float64, (P, M)), enorm=view(L.enorm_off, np.float64, (P, M)))
 
 
+@dataclass
+class ConsolidateArtifacts:
+    """Host copy of a plan's rebase table (include/svdq.h, svdq_consolidate_layout), as typed numpy views."""
+    w: np.ndarray          # [P, 33, 32] f32  W[source column][new column]; row r = the mean column of a centred source
+    bbar: np.ndarray       # [P, 33] f32      bbar over the source columns
+    r: np.ndarray          # [P] i32          r': directions kept
+    k: np.ndarray          # [P] i32          k'
+    live: np.ndarray       # [P] i32          1 = the rebase pass writes the entry
+    dropped: np.ndarray    # [P] f64          dropped_energy
+    eta: np.ndarray        # [P] f64          the bound on ||dK||
+    lam: np.ndarray        # [P, 32] f64      eigenvalues of K over the kept tasks, descending
+
+
+def consolidate_views(host: np.ndarray, L, P: int) -> ConsolidateArtifacts:
+    """The typed views of one rebase table (``host``: its bytes as a uint8 array; ``L``: its layout).  No copy."""
+    def view(off, dtype, shape):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return host[off:off + n].view(dtype).reshape(shape)
+
+    return ConsolidateArtifacts(w=view(L.w_off, np.float32, (P, 33, 32)), bbar=view(L.bbar_off, np.float32, (P, 33)),
+                                r=view(L.r_off, np.int32, (P,)), k=view(L.k_off, np.int32, (P,)),
+                                live=view(L.live_off, np.int32, (P,)), dropped=view(L.dropped_off, np.float64, (P,)),
+                                eta=view(L.eta_off, np.float64, (P,)), lam=view(L.lambda_off, np.float64, (P, 32)))
+
+
+def keep_table(keep, P: int, n_dst: int, n_src: int) -> np.ndarray:
+    """The keep table of ``CompressPlan.consolidate`` as a contiguous int32 array [P][n_dst]: destination slot j of
+    parameter p takes source slot ``keep[p][j]``, -1 = absent.  ``keep``: that table, or one row [n_dst] for every
+    parameter.  A pure function: raises ``ValueError`` on a wrong shape or an entry outside [-1, n_src)."""
+    arr = np.asarray(keep)
+    if arr.dtype.kind not in "iu":
+        raise ValueError("keep must hold integers")
+    arr = arr.astype(np.int64)
+    if arr.ndim == 1:
+        arr = np.broadcast_to(arr, (P, arr.shape[0]))
+    if arr.shape != (P, n_dst):
+        raise ValueError(f"keep must be [{P}][{n_dst}] (or one row of {n_dst}), got {list(arr.shape)}")
+    if arr.size and (arr.min() < -1 or arr.max() >= n_src):
+        raise ValueError(f"keep entries must be -1 (absent) or a source slot in [0, {n_src})")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
 def pack_small(layout, P: int, N: int, S: int, entries: Sequence[Optional[Dict]]) -> np.ndarray:
     """The bytes of a plan's small-artifact buffer (include/svdq.h, svdq_small_layout) from per-parameter artifact
     values -- what ``CompressPlan.import_artifacts`` uploads.  A pure function of its arguments (``layout`` is any object
@@ -545,6 +587,79 @@ class CompressPlan:
             nat.check(self.lib.svdq_plan_store_gram(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
                                                     _ptr(self.mean), _ptr(work), _ptr(G), _ptr(B), _stream_ptr()), who)
         return (G, B) if basis_gram else G
+
+    # ---- the store brought back to the form a fresh compress run would give it (svdq_consolidate.hip)
+    def consolidate_layout(self):
+        lay = getattr(self, "_consolidate_layout", None)
+        if lay is None:
+            lay = self._consolidate_layout = nat.SvdqConsolidateLayout()
+            nat.check(self.lib.svdq_plan_consolidate_layout(self._h, byref(lay)), "svdq_plan_consolidate_layout")
+        return lay
+
+    def _consolidate_args(self, who, dst_plan, rows_dev):
+        if self.basis is None or dst_plan.basis is None:
+            raise ValueError(f"{who}: a gram_only plan holds no artifacts")
+        if dst_plan.device != self.device:
+            raise ValueError(f"{who}: the destination plan is on {dst_plan.device}, the source on {self.device}")
+        if rows_dev is None:
+            return self.small[self.layout.rows_off:self.layout.rows_off + 8 * self.P].view(torch.int64)
+        if (rows_dev.dtype is not torch.int64 or rows_dev.device != self.device or not rows_dev.is_contiguous()
+                or rows_dev.numel() != self.P):
+            raise ValueError(f"{who}: rows_dev must be a contiguous int64 tensor of {self.P} entries on {self.device}")
+        return rows_dev
+
+    def consolidate_eig(self, dst_plan: "CompressPlan", keep, min_sigma: float = 0.0,
+                        rows_dev: Optional[torch.Tensor] = None, basis_gram: Optional[torch.Tensor] = None) -> None:
+        """The eigen stage of ``consolidate`` on its own (svdq_plan_consolidate_eig, one launch): from ``basis_gram``
+        [P, 33, 33] float64 -- ``store_gram(basis_gram=True)``'s second result; None = it is formed here -- the kept slots'
+        coefficients and the destination's settings to ``dst_plan.small`` and the rebase table ``self.rebase_table``
+        (device).  Asynchronous on the current stream."""
+        who = "svdq_plan_consolidate_eig"
+        rows_dev = self._consolidate_args(who, dst_plan, rows_dev)
+        kt = keep_table(keep, self.P, dst_plan.N, self.N)
+        if basis_gram is None:
+            _, basis_gram = self.store_gram(rows_dev=rows_dev, basis_gram=True)
+        elif (basis_gram.dtype is not torch.float64 or basis_gram.device != self.device or not basis_gram.is_contiguous()
+              or basis_gram.numel() != self.P * 33 * 33):
+            raise ValueError(f"{who}: basis_gram must be a contiguous float64 tensor [{self.P}, 33, 33] on {self.device}")
+        lay = self.consolidate_layout()
+        tab = getattr(self, "rebase_table", None)
+        if tab is None or tab.numel() != int(lay.total_bytes):
+            tab = self.rebase_table = torch.zeros(int(lay.total_bytes), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            kd = torch.from_numpy(kt).to(self.device)
+            nat.check(self.lib.svdq_plan_consolidate_eig(self._h, dst_plan._h, c_void_p(kt.ctypes.data), _ptr(kd),
+                                                         _ptr(rows_dev), _ptr(self.small), _ptr(basis_gram),
+                                                         float(min_sigma), _ptr(dst_plan.small), _ptr(tab),
+                                                         _stream_ptr()), who)
+
+    def rebase(self, dst_plan: "CompressPlan", rows_dev: Optional[torch.Tensor] = None) -> None:
+        """The streaming pass of ``consolidate`` on its own (svdq_plan_rebase, one launch): [U' | mean'] = A [W | bbar]
+        from this plan's basis and mean and ``self.rebase_table`` into ``dst_plan``'s basis and mean buffers.
+        Asynchronous on the current stream."""
+        who = "svdq_plan_rebase"
+        rows_dev = self._consolidate_args(who, dst_plan, rows_dev)
+        if getattr(self, "rebase_table", None) is None:
+            raise ValueError(f"{who}: consolidate_eig has not run on this plan")
+        with torch.cuda.device(self.device):
+            nat.check(self.lib.svdq_plan_rebase(self._h, dst_plan._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                _ptr(self.mean), _ptr(self.rebase_table), _ptr(dst_plan.basis),
+                                                _ptr(dst_plan.mean), _stream_ptr()), who)
+        dst_plan._typed = None
+
+    def consolidate(self, dst_plan: "CompressPlan", keep, min_sigma: float = 0.0,
+                    rows_dev: Optional[torch.Tensor] = None):
+        """Re-derive bases, rank, mean and coefficients of the tasks this plan's stored artifacts reconstruct into
+        ``dst_plan`` -- a plan with the same rows and basis dtype, its own task slots and settings -- without
+        materialising a task model (include/svdq.h, svdq_plan_consolidate_eig: four launches, nothing copied to the host
+        in between).  ``keep``: int [P][N'] (or one row [N']), destination slot j takes source slot ``keep[p][j]``,
+        -1 = absent.  ``rows_dev``: int64 [P] rows per parameter; None = the rows field of this plan's small buffer.
+        Returns ``(small, table)``: the destination's small views and the rebase table's (two device-to-host copies,
+        which synchronise); raises ``NonFiniteInput`` naming the flagged parameters."""
+        self.consolidate_eig(dst_plan, keep, min_sigma=min_sigma, rows_dev=rows_dev)
+        self.rebase(dst_plan, rows_dev=rows_dev)
+        table = consolidate_views(self.rebase_table.cpu().numpy(), self.consolidate_layout(), self.P)
+        return dst_plan.fetch_small(), table
 
     # ---- the basis grown by what new tasks add outside its span (svdq_plan_extend.hip)
     def _extend_args(self, who, table, base_table, index_table, rows_dev):

@@ -362,6 +362,101 @@ def add_tasks_to_artifacts(artifact_dir: str, base_state_dict, finetuned: Dict[s
     return result
 
 
+def consolidated_config(config, energy_threshold=None, max_rank=None, low_bits=None, rtvq_stages=None, center=None):
+    """The stored config with the arguments given put over it (None = as stored); the dataclass's own checks apply."""
+    from dataclasses import replace
+    over = {k: v for k, v in (("svd_energy_threshold", energy_threshold), ("svd_max_rank", max_rank),
+                              ("svd_low_bits", low_bits), ("svd_rtvq_stages", rtvq_stages), ("svd_center", center))
+            if v is not None}
+    return replace(config, **over) if over else config
+
+
+def consolidated_diagnostics(diagnostics: Dict[str, Any], kept, result: Dict[str, Any]) -> Dict[str, Any]:
+    """diagnostics.json of a consolidated store: the stored one with ``task_weights`` restricted to the kept tasks and,
+    when a task was dropped, renormalised (uniform where the store had none), and ``tasks`` / ``columns`` ({"param [region]": [r, r']}) /
+    ``dropped_energy`` / ``noise_floor`` / ``promoted`` recorded; ``cluster_assignments`` and ``captured_energy`` lose
+    the dropped tasks.  A pure function: the input is not touched."""
+    out = dict(diagnostics)
+    old = diagnostics.get("task_weights") or {}
+    ws = {t: float(old[t]) for t in kept if t in old}
+    tot = sum(ws.values())
+    if len(ws) == len(kept) == len(old):      # no task left: the stored weights as they are
+        out["task_weights"] = ws
+    else:
+        out["task_weights"] = ({t: ws[t] / tot for t in kept} if len(ws) == len(kept) and tot > 0
+                               else {t: 1.0 / len(kept) for t in kept})
+    out["tasks"] = list(kept)
+    out["columns"] = {f"{n} [{r}]": [int(a), int(b)] for (n, r), (a, b) in result["columns"].items()}
+    out["dropped_energy"] = {f"{n} [{r}]": float(v) for (n, r), v in result["dropped_energy"].items()}
+    out["noise_floor"] = {f"{n} [{r}]": float(v) for (n, r), v in result.get("noise_floor", {}).items()}
+    out["promoted"] = {f"{n} [{r}]": [int(a), int(b)] for (n, r), (a, b) in result.get("promoted", {}).items()}
+    for key in ("cluster_assignments", "captured_energy"):      # other per-task records: the dropped tasks leave them too
+        if isinstance(diagnostics.get(key), dict):
+            out[key] = {t: v for t, v in diagnostics[key].items() if t in kept}
+    return out
+
+
+def _replace_store_files(staged: str, artifact_dir: str) -> None:
+    """Move every file of the staged store over its counterpart in ``artifact_dir`` (os.replace, file by file: each file
+    is old or new, never partial).  Files of the store that consolidation does not write (a merged model, masks) stay.
+    The window: a failure INSIDE this loop -- after everything was computed and written to the staging directory --
+    leaves a store that mixes old and new files; the staging directory is then kept, so that the move can be finished
+    by hand."""
+    for root, _, files in os.walk(staged):
+        rel = os.path.relpath(root, staged)
+        dst = artifact_dir if rel == "." else os.path.join(artifact_dir, rel)
+        os.makedirs(dst, exist_ok=True)
+        for f in files:
+            os.replace(os.path.join(root, f), os.path.join(dst, f))
+
+
+def consolidate_artifacts(artifact_dir: str, output_dir: str = None, tasks=None, energy_threshold=None, max_rank=None,
+                          low_bits=None, rtvq_stages=None, center=None, min_sigma: float = 0.0, device: str = "cuda"
+                          ) -> Dict[str, Any]:
+    """Consolidate a stored artifact set: bases, rank, mean and coefficients re-derived from the artifacts alone
+    (``compress.consolidate_bases``) -- after ``add_tasks_to_artifacts(extend_basis=True)`` grew the store, to drop
+    tasks from it (``tasks``: the ones to keep; None = all), or to take it to another ``energy_threshold`` /
+    ``max_rank`` / ``low_bits`` / ``rtvq_stages`` / ``center`` (None = as stored).  No checkpoint is read.
+    The consolidated store goes to ``output_dir``; None = in place, and then through a temporary directory beside the
+    store: everything is computed and written there first, so a failure up to that point leaves the old store whole;
+    the files are then moved over the old ones one by one (``_replace_store_files`` states that window).  The dropped
+    tasks are in no file of the new store; ``tasks``, ``columns`` and ``dropped_energy`` are recorded in
+    diagnostics.json.  A region whose c_low the quantizer cannot represent is stored on the high side and listed under
+    ``promoted`` (``compress.consolidate_bases``): no store with non-finite coefficients is written.
+    Returns {"tasks", "dropped", "columns", "dropped_energy", "promoted", "skipped", "output_dir"}."""
+    import shutil
+    import tempfile
+    from .compress import consolidate_bases, consolidate_task_list, check_consolidate_room
+    art = load_all_artifacts(artifact_dir, device="cpu")
+    diagnostics, bases, compressed = art["diagnostics"], art["bases"], art["compressed"]
+    kept = consolidate_task_list(compressed, tasks)
+    check_consolidate_room(bases)
+    config = consolidated_config(art["config"], energy_threshold, max_rank, low_bits, rtvq_stages, center)
+    stored = _stored_tasks(compressed, diagnostics)
+    res = consolidate_bases(compressed, bases, config, tasks=kept, min_sigma=min_sigma, device=device)
+    new_comp = {n: ({t: a for t, a in per_task.items() if t in kept} if n in res["skipped"] else per_task)
+                for n, per_task in res["compressed"].items()}
+    new_diag = consolidated_diagnostics(diagnostics, kept, res)
+    in_place = output_dir is None or os.path.realpath(output_dir) == os.path.realpath(artifact_dir)
+    out = artifact_dir if in_place else output_dir
+    if in_place:
+        parent = os.path.dirname(os.path.realpath(artifact_dir))
+        staged = tempfile.mkdtemp(prefix=".consolidate-", dir=parent)
+        try:
+            save_all_artifacts(res["bases"], new_comp, new_diag, config, staged)
+        except BaseException:
+            shutil.rmtree(staged, ignore_errors=True)      # nothing of the store was touched
+            raise
+        _replace_store_files(staged, artifact_dir)
+        shutil.rmtree(staged, ignore_errors=True)
+    else:
+        save_all_artifacts(res["bases"], new_comp, new_diag, config, out)
+    return {"tasks": kept, "dropped": [t for t in stored if t not in kept],
+            "columns": new_diag["columns"], "dropped_energy": new_diag["dropped_energy"],
+            "promoted": new_diag["promoted"], "skipped": res["skipped"],
+            "output_dir": out}
+
+
 def remerge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None, weighting: Optional[str] = None,
                            cluster_k: Optional[int] = None, performance_file: Optional[str] = None,
                            temperature: Optional[float] = None, device: str = "cuda", update_store: bool = False
