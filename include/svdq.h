@@ -906,6 +906,68 @@ int svdq_plan_rebase(const svdq_plan *src_plan, const svdq_plan *dst_plan, const
                      const void *src_small_dev, const void *src_basis_dev, const float *src_mean_dev,
                      const void *rebase_dev, void *dst_basis_dev, float *dst_mean_dev, void *stream);
 
+/* ---- the sign-elected (TIES) merge of a store, in streaming passes over the basis.  The reference's dispatcher lists
+ *      "ties" beside "svd_hybrid" and implements none (cli.py answers "not yet implemented"); the definition is Yadav et
+ *      al. 2023 as published in the authors' code (topk_values_mask -> resolve_sign -> disjoint_merge), on what the store
+ *      reconstructs: v_t[d] = the value svdq_task_reconstruct writes for task t at row d, bit for bit
+ *      (RTVQQuantizer.dequantize rtvq.py:85-103 + reconstruct_from_coefficients merge.py:144-194), 0 on the rows of a
+ *      parameter the task lacks.  With D the rows of ALL parameters of the store and T its tasks in sorted-name order:
+ *        trim   tau_t = the j-th smallest |v_t[.]| over all D rows, j = max(D - int(D * density), 1); v_t[d] is kept iff
+ *               |v_t[d]| >= tau_t (equal magnitudes at the threshold are all kept)
+ *        elect  s[d] = the kept v_t[d] added in task order, each sum rounded in fp32; positive iff s[d] >= 0 (s == 0
+ *               elects positive: the published code asks the sign majority of the whole model there)
+ *        merge  a[d] = the kept values whose sign strictly agrees (v > 0 / v < 0) added in task order, c[d] their number;
+ *               mean: a / max(c, 1) (one fp32 division), sum: a
+ *        apply  out = base + scaling * merged (one product, one sum; without base the product)
+ *      No buffer proportional to D * T exists at any point: the values are formed in registers, pass by pass, by the
+ *      streaming structure of svdq_task_reconstruct (fma chains, hi + lo, + mean on a centred plan), so every pass sees
+ *      the same bits.  tau_t is found EXACTLY by a radix selection on the magnitude bits (bits & 0x7fffffff, as unsigned
+ *      integers ordered like the magnitudes), 8 bits per pass from the top, SVDQ_TIES_DIGITS passes:
+ *        for digit in 0 .. SVDQ_TIES_DIGITS - 1:
+ *            svdq_plan_ties_hist(plan, ..., digit, state, ...)      for every plan of the store
+ *            svdq_ties_select_step(state, T, digit, j, zeros)       once
+ *        svdq_plan_ties_merge(plan, ..., state, ...)                for every plan of the store
+ *      state_dev: ONE table of svdq_ties_work_bytes(T) bytes shared by all plans of the store (thresholds are global),
+ *      zeroed by the caller before digit 0; uint64 words: hist [T][256] | prefix [T] (after the last digit: the bit
+ *      pattern of tau_t in the low 32 bits) | rank [T] | kept [T] (values kept per task, implicit zeros included) |
+ *      rows with kept values of both signs | rows with nothing kept.  Counts are integers added by atomics, one flush per
+ *      work unit: no result depends on the order the units run in.  State, histogram and thresholds stay on the device.
+ *   slot_task_dev int32 [P][n_out]: the plan task index behind slot j of parameter p.
+ *   task_map_dev  int32 [P][n_out]: the store task (0 .. T-1) behind slot j of parameter p, -1 = the slot is unused.  The
+ *                 live slots of a parameter must name its store tasks in ASCENDING order: slot order is the order of the
+ *                 sums.  Like svdq_task_reconstruct's table the entries live on the device and are the caller's to have
+ *                 checked; a slot outside [0, T) or [0, N) is skipped.
+ *   svdq_plan_ties_hist   counts, for every row of the plan and every live slot whose magnitude bits above `digit` equal
+ *                 the task's prefix, the digit's value.  Reads the basis once (as svdq_task_reconstruct), writes nothing
+ *                 but the table.
+ *   svdq_ties_select_step  one small launch: per task the bin that holds the wanted rank (walked from the top), appended
+ *                 to the prefix; the remaining rank; the histogram zeroed for the next digit.  rank: j, read at digit 0.
+ *                 zeros_dev NULL or int64 [T]: the rows of the parameters task t lacks -- implicit zeros, counted in bin 0
+ *                 while the prefix is all zero.
+ *   svdq_plan_ties_merge  elect, merge, apply for every parameter with a non-NULL output: out_ptrs_dev [P] fp32 tensors of
+ *                 rows[p] elements, base_ptrs_dev NULL or [P] (NULL entry = no base); merge_sum 0 = mean, else sum.  Adds
+ *                 the by-products to the table.
+ *   rows_dev, small_dev, basis_dev, mean_dev: as for svdq_task_reconstruct.  work_dev: svdq_task_reconstruct_work_bytes(
+ *                 plan, n_out) bytes (the live tasks' coefficients).
+ *   errors        SVDQ_EINVAL before anything is launched: a NULL plan, buffer or table; n_out or n_tasks outside
+ *                 [1, SVDQ_MAX_TASKS]; a digit outside [0, SVDQ_TIES_DIGITS); a missing mean on a centred plan; rank < 1.
+ *   Allocates nothing, copies nothing to the host, synchronises nothing: capturable like every other entry point.  Works
+ *   on plans filled by any compress route and on plans filled by svdq_plan_import.  Non-finite values are outside the
+ *   definition. */
+#define SVDQ_TIES_DIGITS 4
+int64_t svdq_ties_work_bytes(int32_t n_tasks);
+int svdq_plan_ties_hist(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                        const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                        const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks, int32_t digit,
+                        void *state_dev, void *work_dev, void *stream);
+int svdq_ties_select_step(void *state_dev, int32_t n_tasks, int32_t digit, int64_t rank,
+                          const int64_t *zeros_dev /*NULL or [T]*/, void *stream);
+int svdq_plan_ties_merge(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                         const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                         const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks, int32_t merge_sum,
+                         float scaling, const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/,
+                         void *state_dev, void *work_dev, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

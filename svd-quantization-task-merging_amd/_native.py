@@ -170,6 +170,12 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p]),
     "svdq_plan_rebase": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
+    "svdq_ties_work_bytes": (c_int64, [c_int32]),
+    "svdq_plan_ties_hist": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "svdq_ties_select_step": (c_int32, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
+    "svdq_plan_ties_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                       c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svdq_mask_expand": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "svdq_hbm_probe": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
 }

@@ -2,8 +2,8 @@
 // k_task_reconstruct and k_task_expand are the order in which they call these pieces plus their family's epilogue;
 // k_diag takes the byte count, ustage_fetch and unit_source_range; k_merge_expand takes the types, ustage_plan,
 // lds_fence and unit_source_range and carries its own copy of the other steps (its launch is sized by StreamLds; the
-// comment at the kernel says why).  Included by svdq_merge.hip alone (-ffp-contract=off: every product and sum is
-// rounded where the reference's torch ops round).
+// comment at the kernel says why).  svdq_ties.hip builds its two streaming kernels from the same pieces.  Included by
+// files compiled with -ffp-contract=off alone (every product and sum is rounded where the reference's torch ops round).
 #pragma once
 
 #include "svdq_common.h"

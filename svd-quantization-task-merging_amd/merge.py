@@ -637,3 +637,125 @@ def merge_with_clustering(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
                                                 verbose=False)
         performance[cid] = sum(weights.get(m, 1.0) for m in members) / len(members)
     return merge_cluster_results(per_cluster, performance, device)
+
+
+def _ties_jobs(names, wanted, compressed_all, bases, original_shapes):
+    """The plans behind a TIES merge: {id(plan): (batch, {entry index: name})}, the rows of every parameter and, per
+    parameter, the (store task, plan task) pairs of the wanted tasks that have it, in store order.  Raises the named
+    ValueError for what the streaming route cannot serve."""
+    import math
+    jobs, rows, live = {}, {}, {}
+    for name in names:
+        got = _batched_entry(name, compressed_all, bases)
+        if got is None:
+            raise ValueError(f"ties_merge_parameters: parameter {name!r} is not backed by a plan (adoption declined it, or "
+                             "its dictionaries were edited): the TIES merge reads the values from plans only")
+        batch, i, meta = got
+        stored = int(batch.small.rows[i])
+        if (getattr(batch, "mode", "plain") != "plain" or meta["noise"] is not None
+                or stored != math.prod(original_shapes[name])):
+            raise ValueError(f"ties_merge_parameters: parameter {name!r} stores {stored} rows for a tensor of "
+                             f"{math.prod(original_shapes[name])} elements -- a masked run's store; masks are not stored, "
+                             "and the TIES merge is defined on whole tensors")
+        jobs.setdefault(id(batch.plan), (batch, {}))[1][i] = name
+        rows[name] = stored
+        pos = {t: q for q, t in enumerate(batch.task_names[i])}
+        live[name] = [(g, pos[t]) for g, t in enumerate(wanted) if t in meta["have"] and t in pos]
+    return jobs, rows, live
+
+
+def ties_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                          original_shapes: Dict[str, torch.Size], config, density: float = 0.2, scaling: float = 1.0,
+                          merge_func: str = "mean", tasks=None, base_state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                          device: str = "cuda", return_stats: bool = False):
+    """The sign-elected (TIES, Yadav et al. 2023) merge of what a store reconstructs, without a task model ever being
+    written (the contract is at svdq_plan_ties_hist in include/svdq.h).  With v_t what
+    ``reconstruct_task_vectors`` returns for task t (0 where a task lacks a parameter), D the rows of all parameters and
+    the tasks in sorted-name order: trim every task to the values with |v_t| >= tau_t, the j-th smallest magnitude over
+    all D rows, j = max(D - int(D * density), 1); elect the sign of the fp32 sum of the kept values per row (>= 0 is
+    positive); average (``merge_func="mean"``) or add ("sum") the kept values that agree with it; return
+    ``scaling * merged`` per parameter, ``base + scaling * merged`` for the parameters ``base_state_dict`` holds.
+
+    Takes dictionaries backed by a fused run or by ``adopt_artifacts``; ``tasks``: the names to merge (None = all).  A
+    parameter that no plan backs, or whose stored rows differ from its shape's element count (a masked run's store),
+    raises a ValueError naming it.  ``config`` is the run's (the dictionaries carry everything the merge needs; it is
+    taken for symmetry with ``merge_all_parameters``).
+
+    Returns {param: tensor}; with ``return_stats`` also {"thresholds": {task: float}, "kept": {task: int},
+    "sign_conflict_rows": int, "empty_rows": int, "rows": D}.  4 passes over the basis find the thresholds exactly, one
+    more merges: the only buffers that grow with the model are the outputs."""
+    import numpy as np
+    from .pipeline import ties_thresholds
+    if not (isinstance(density, (int, float)) and 0.0 < float(density) <= 1.0):
+        raise ValueError(f"density must be in (0, 1], got {density!r}")
+    if merge_func not in ("mean", "sum"):
+        raise ValueError(f"merge_func must be 'mean' or 'sum', got {merge_func!r}")
+    known = []
+    for per_task in compressed_all.values():
+        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
+                  if t not in known]
+    for t in (tasks if tasks is not None else []):
+        if t not in known:
+            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    wanted = sorted(set(known if tasks is None else tasks))
+    T = len(wanted)
+    if not 1 <= T <= nat.MAX_TASKS:
+        raise ValueError(f"ties_merge_parameters: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
+    names = sorted(compressed_all.keys())
+    jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes)      # refusals before device work
+    dev = resolve_device(device)
+    D = sum(rows.values())
+    rank = max(D - int(D * float(density)), 1)
+    zeros = np.full(T, D, dtype=np.int64)
+    for name, pairs in live.items():
+        for g, _ in pairs:
+            zeros[g] -= rows[name]
+    out, later = {}, {}
+    stats = {"thresholds": {}, "kept": {}, "sign_conflict_rows": 0, "empty_rows": 0, "rows": D}
+    if D == 0:
+        out = {name: torch.zeros(original_shapes[name], device=dev) for name in names}
+        return (out, stats) if return_stats else out
+    with torch.cuda.device(dev):
+        calls, keep = [], []
+        for batch, entries in jobs.values():
+            plan = batch.plan
+            P = plan.P
+            n_out = max([len(live[name]) for name in entries.values()] + [1])
+            slot_task = np.zeros((P, n_out), dtype=np.int32)
+            task_map = np.full((P, n_out), -1, dtype=np.int32)
+            out_tab = np.zeros(P, dtype=np.int64)
+            base_tab = np.zeros(P, dtype=np.int64)
+            for i, name in entries.items():
+                for j, (g, q) in enumerate(live[name]):
+                    task_map[i, j], slot_task[i, j] = g, q
+                if rows[name] <= 0:
+                    out[name] = torch.zeros(original_shapes[name], device=plan.device)
+                    continue
+                res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
+                out_tab[i] = res.data_ptr()
+                b = base_state_dict.get(name) if base_state_dict is not None else None
+                if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
+                    keep.append(prepare_vector(b, plan.device))
+                    base_tab[i] = keep[-1].data_ptr()
+                elif b is not None:
+                    later[name] = b
+            rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+            calls.append((plan, torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device),
+                          rows_dev, torch.from_numpy(out_tab).to(plan.device),
+                          torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None))
+        state = ties_thresholds([c[:4] for c in calls], T, rank, torch.from_numpy(zeros).to(dev), device=dev)
+        for plan, slot_task, task_map, rows_dev, out_tab, base_tab in calls:
+            plan.ties_merge(slot_task, task_map, T, state.table, out_tab, merge_func=merge_func, scaling=scaling,
+                            base_table=base_tab, rows_dev=rows_dev)
+        if return_stats:
+            host = state.table[256 * T:].cpu().numpy()
+            tau = (host[:T] & 0xffffffff).astype(np.uint32).view(np.float32)
+            stats["thresholds"] = {t: float(tau[g]) for g, t in enumerate(wanted)}
+            stats["kept"] = {t: int(host[2 * T + g]) for g, t in enumerate(wanted)}
+            stats["sign_conflict_rows"], stats["empty_rows"] = int(host[3 * T]), int(host[3 * T + 1])
+        for name in names:
+            res = out[name].view(original_shapes[name])
+            if name in later:
+                res = later[name].to(res.device) + res
+            out[name] = res.cpu() if wants_cpu(device) else res
+    return (out, stats) if return_stats else out

@@ -871,6 +871,54 @@ class CompressPlan:
                                              _ptr(mask_table), _ptr(unit_start), _ptr(fill), _ptr(base_table),
                                              _ptr(out_table), _ptr(work), _stream_ptr()), "svdq_merge_masked")
 
+    # ---- the sign-elected (TIES) merge (svdq_ties.hip)
+    def _ties_tables(self, who: str, slot_task: torch.Tensor, task_map: torch.Tensor) -> int:
+        """n_out of a pair of int32 device tables [P, n_out] (``ties_hist`` / ``ties_merge``), and the coefficient work
+        buffer sized for it."""
+        for t in (slot_task, task_map):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype is torch.int32 and t.is_contiguous()
+                    and t.dim() == 2 and t.shape[0] == self.P):
+                raise ValueError(f"{who}: slot_task and task_map must be contiguous int32 device tables [{self.P}, n_out]")
+        if slot_task.shape != task_map.shape or not 1 <= int(task_map.shape[1]) <= nat.MAX_TASKS:
+            raise ValueError(f"{who}: slot_task and task_map need the same shape [P, n_out], 1 <= n_out <= {nat.MAX_TASKS}")
+        n_out = int(task_map.shape[1])
+        work = getattr(self, "_task_work", None)
+        need = int(self.lib.svdq_task_reconstruct_work_bytes(self._h, n_out))
+        if work is None or work.numel() < need:
+            self._task_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return n_out
+
+    def ties_hist(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, digit: int, state: torch.Tensor,
+                  rows_dev: Optional[torch.Tensor] = None) -> None:
+        """One digit of the radix selection of the TIES thresholds over this plan's rows (svdq_plan_ties_hist): every
+        live slot's magnitudes whose upper bits equal the task's prefix are counted by the digit's value into ``state``,
+        the store's table (``ties_state``).  ``slot_task`` / ``task_map``: int32 device tables [P, n_out] -- the plan
+        task and the store task behind slot j of parameter p (-1 = unused; live slots in ascending store order).
+        Reads the basis once, writes nothing but the table.  Asynchronous on the current stream."""
+        who = "svdq_plan_ties_hist"
+        n_out = self._ties_tables(who, slot_task, task_map)
+        nat.check(self.lib.svdq_plan_ties_hist(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis), _ptr(self.mean),
+                                               _ptr(slot_task), _ptr(task_map), n_out, int(n_tasks), int(digit),
+                                               _ptr(state), _ptr(self._task_work), _stream_ptr()), who)
+
+    def ties_merge(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, state: torch.Tensor,
+                   out_table: torch.Tensor, merge_func: str = "mean", scaling: float = 1.0,
+                   base_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None) -> None:
+        """Elect, merge and apply for every parameter of the plan in one pass over the basis (svdq_plan_ties_merge), with
+        the thresholds ``ties_thresholds`` left in ``state``: ``out_table`` int64 [P] fp32 outputs of rows[p] elements (0 =
+        skip), ``base_table`` int64 [P] or None (out = base + scaling * merged).  Adds the kept counts and the two row
+        counters to ``state``."""
+        who = "svdq_plan_ties_merge"
+        if merge_func not in ("mean", "sum"):
+            raise ValueError(f"{who}: merge_func must be 'mean' or 'sum', got {merge_func!r}")
+        n_out = self._ties_tables(who, slot_task, task_map)
+        if out_table.numel() != self.P:
+            raise ValueError(f"{who}: out_table needs {self.P} entries, got {out_table.numel()}")
+        nat.check(self.lib.svdq_plan_ties_merge(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                _ptr(self.mean), _ptr(slot_task), _ptr(task_map), n_out, int(n_tasks),
+                                                int(merge_func == "sum"), float(scaling), _ptr(base_table),
+                                                _ptr(out_table), _ptr(state), _ptr(self._task_work), _stream_ptr()), who)
+
     def diagnostics_masked(self, table, mask_table: torch.Tensor, unit_start: torch.Tensor, rows_dev: torch.Tensor,
                            add_mean: bool = False) -> torch.Tensor:
         """``diagnostics`` for a plan of masked regions: ``table`` names the UNMASKED task deltas, the selection
@@ -1156,6 +1204,47 @@ class BatchResult:
                  task_names: List[List[str]]):
         self.plan, self.small, self.entries, self.task_names = plan, small, entries, task_names
         self.index = {e: i for i, e in enumerate(entries)}
+
+
+TIES_DIGITS = 4      # SVDQ_TIES_DIGITS: 8-bit digits of the 31 magnitude bits
+
+
+class TiesState:
+    """Views of the TIES state table (include/svdq.h: hist | prefix | rank | kept | conflict rows | empty rows)."""
+
+    def __init__(self, n_tasks: int, device):
+        n_tasks = int(n_tasks)
+        need = int(nat.lib().svdq_ties_work_bytes(n_tasks))
+        if need <= 0:
+            raise ValueError(f"svdq_ties_work_bytes: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
+        self.n_tasks = n_tasks
+        self.table = torch.zeros(need // 8, dtype=torch.int64, device=device)
+        T = n_tasks
+        self.thresholds = self.table[256 * T:257 * T]      # the bit pattern of tau_t in the low 32 bits
+        self.kept = self.table[258 * T:259 * T]
+        self.counters = self.table[259 * T:259 * T + 2]     # rows with kept values of both signs, rows with nothing kept
+
+
+def ties_thresholds(jobs, n_tasks: int, rank: int, zeros: Optional[torch.Tensor] = None, device=None) -> TiesState:
+    """The digit loop of the TIES trim across the plans of a store: ``jobs`` = [(plan, slot_task, task_map, rows_dev)]
+    (the arguments of ``CompressPlan.ties_hist``).  ONE state table serves all plans, because the thresholds are global:
+    per digit every plan adds its counts (svdq_plan_ties_hist), then one small launch picks each task's bin
+    (svdq_ties_select_step).  ``rank``: the j of "j-th smallest magnitude"; ``zeros``: int64 device tensor [n_tasks], the
+    rows of the parameters a task lacks.  Nothing is read back between the passes; returns the state with
+    ``thresholds`` filled."""
+    jobs = list(jobs)
+    if not jobs:
+        raise ValueError("ties_thresholds: no plan")
+    dev = jobs[0][0].device if device is None else device
+    state = TiesState(n_tasks, dev)
+    lib = nat.lib()
+    with torch.cuda.device(dev):
+        for digit in range(TIES_DIGITS):
+            for plan, slot_task, task_map, rows_dev in jobs:
+                plan.ties_hist(slot_task, task_map, n_tasks, digit, state.table, rows_dev=rows_dev)
+            nat.check(lib.svdq_ties_select_step(_ptr(state.table), int(n_tasks), digit, int(rank), _ptr(zeros),
+                                                _stream_ptr()), "svdq_ties_select_step")
+    return state
 
 
 def compress_batch(vectors: List[List[torch.Tensor]], *, energy_threshold: float, max_rank: Optional[int],
