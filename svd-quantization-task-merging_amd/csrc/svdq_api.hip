@@ -2,6 +2,7 @@
 // Host-side only: builds the unit / parameter tables of a plan and enqueues the kernels.
 
 #include "svdq_common.h"
+#include "svdq_small_view.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -154,23 +155,8 @@ extern "C" int svdq_plan_create(svdq_plan **out, int32_t n_tasks, int32_t n_para
     pl->sizes.n_slots = pl->n_slots;
 
     // small artifacts
-    const int64_t P = n_params, S = cfg->rtvq_stages;
-    svdq_small_layout &L = pl->small;
-    off = 0;
-    L.sigma_off = off;  off += svdq_align_up(P * N * 4, 64);
-    L.k_off = off;      off += svdq_align_up(P * 4, 64);
-    L.r_off = off;      off += svdq_align_up(P * 4, 64);
-    L.energy_off = off; off += svdq_align_up(P * 4, 64);
-    L.rows_off = off;   off += svdq_align_up(P * 8, 64);
-    L.chigh_off = off;  off += svdq_align_up(P * nn * 2, 64);
-    L.codes_off = off;  off += svdq_align_up(P * N * S * N, 64);
-    L.scale_off = off;  off += svdq_align_up(P * N * S * 4, 64);
-    L.zp_off = off;     off += svdq_align_up(P * N * S * 4, 64);
-    L.rnorm_off = off;  off += svdq_align_up(P * N * S * 4, 64);
-    L.coef_off = off;   off += svdq_align_up(P * nn * 4, 64);
-    L.status_off = off; off += 64;
-    L.total_bytes = off;
-    pl->sizes.small_bytes = off;
+    pl->small = svdq_small_layout_of(n_params, N, cfg->rtvq_stages);
+    pl->sizes.small_bytes = pl->small.total_bytes;
 
     hipError_t e = hipMalloc((void **)&pl->d_params, sizeof(SvdqParam) * n_params);
     if (e == hipSuccess) e = hipMalloc((void **)&pl->d_units, sizeof(SvdqUnit) * n_units);

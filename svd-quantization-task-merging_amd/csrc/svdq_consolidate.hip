@@ -21,6 +21,8 @@
 #include "svdq_coeff.h"
 #include "svdq_dispatch.h"
 #include "svdq_merge_stream.h"
+#include "svdq_small_view.h"
+#include "svdq_store_pass.h"
 
 #define CS_RA 33      // rows of W and of basis_gram_dev: r <= 32 source columns and the mean
 #define CS_WC 32      // columns of W: r' <= 32
@@ -29,27 +31,9 @@
 
 typedef __attribute__((address_space(1))) f32x4 cs_gf32x4_w;
 
-// k and r as every consumer reads them, held to what the slab has room for (svdq_plan_import's rule)
-__device__ __forceinline__ void cs_ranks(const int32_t *k_in, const int32_t *r_in, int p, int64_t rows, int n, int &k,
-                                         int &r) {
-    const int64_t rmax = rows < n ? rows : n;
-    int64_t rr = r_in[p], kk = k_in[p];
-    rr = rr < 0 ? 0 : (rr > rmax ? rmax : rr);
-    kk = kk < 0 ? 0 : (kk > rr ? rr : kk);
-    k = (int)kk;
-    r = (int)rr;
-}
-
-struct CsSmall {      // the typed arrays of one small buffer
-    float *sigma;
-    int32_t *k, *r;
-    float *energy;
-    int64_t *rows;
-    uint16_t *chigh;
-    uint8_t *codes;
-    float *scale, *zp, *rnorm, *coef;
-    int32_t *status;
-};
+// the destination's small buffer as k_plan_consolidate_eig takes it: the mutable SmallView under the name the kernel's
+// symbol carries
+struct CsSmall : SmallViewMut {};
 struct CsTable {      // the typed arrays of the rebase table (svdq_consolidate_layout)
     float *w, *bbar;
     int32_t *r, *k, *live;
@@ -120,8 +104,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_plan_consolidate_eig(
     __shared__ const void *present[32];
     const int p = blockIdx.x, tid = threadIdx.x, nd = ND;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
+    const int64_t D = plan_rows_of(pd, rows_dev, p);
 
     // every field of the entry is written, whatever follows: the same bytes in every run
     for (int e = tid; e < nd * nd; e += EIG_THREADS) {
@@ -171,7 +154,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_plan_consolidate_eig(
     if (tid < nk) present[slot[tid]] = params;      // any non-NULL value: coeff_store_quantize writes the slot
 
     int k, r;
-    cs_ranks(k_in, r_in, p, D, NS, k, r);
+    plan_ranks(k_in, r_in, p, D, NS, k, r);
     const int ra = r + (src_centred ? 1 : 0);      // columns of A = [U | mean]
     int bad = 0;
     const double *Mg = basis_gram + (size_t)p * CS_RA * CS_RA;
@@ -334,8 +317,6 @@ __host__ __device__ constexpr size_t cs_lds_bytes(int rb, int ns, int nd, int es
            (size_t)cs_align16(rb * nd * es) + 32 + (size_t)rb * 4;
 }
 
-__device__ __forceinline__ float cs_lds_u(const uint8_t *a, __half) { return __half2float(*reinterpret_cast<const __half *>(a)); }
-__device__ __forceinline__ float cs_lds_u(const uint8_t *a, float) { return *reinterpret_cast<const float *>(a); }
 __device__ __forceinline__ void cs_put(__half *dst, float v) { *dst = __float2half_rn(v); }
 __device__ __forceinline__ void cs_put(float *dst, float v) { *dst = v; }
 
@@ -362,8 +343,7 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
                                                     float *__restrict__ omean) {
     using T = typename UElem<U16>::type;
     constexpr int ES = U16 ? 2 : 4;
-    constexpr int RPL = CMAX > 16 ? 2 : 4, RB = 64 * RPL;
-    constexpr int SV = (RB * CMAX * ES / 16 + 2 + 63) / 64;
+    constexpr int RPL = store_rpl(CMAX), RB = store_rb(CMAX), SV = store_sv(CMAX, ES);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NS, u = blockIdx.x;
     const int g = lane >> 4, col = lane & 15;
@@ -372,15 +352,16 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
     if (!live[p]) return;      // wave-uniform: nothing of p is written
     const SvdqParam pd = params[p];
     const SvdqParam dd = dparams[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
-    if (D > dd.rows) D = dd.rows;
+    int64_t D = plan_rows_of(pd, rows_dev, p);
+    if (D > dd.rows) D = dd.rows;      // and never more than the destination's slab has room for
+    // the unit's view of the plan and the block loop written out: as store_unit / stream_blocks (svdq_store_pass.h) this
+    // kernel spills more scalar registers
     int64_t cpos = ud.row0;
     int64_t cend = ud.row0 + ud.nrows;
     if (cend > D) cend = D;
     if (cpos >= cend) return;      // wave-uniform
     int k, r;
-    cs_ranks(k_in, r_in, p, D, n, k, r);
+    plan_ranks(k_in, r_in, p, D, n, k, r);
     const int nl = r - k;
     mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
     const int ra = r + (gmean ? 1 : 0);
@@ -415,9 +396,9 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
     }
 
     const uint8_t *gUh = basis + pd.slab_off;
-    const uint8_t *gUl = gUh + svdq_align_up(D * (int64_t)k * ES, 256);
+    const uint8_t *gUl = SVDQ_SLAB_LOW(gUh, D, k, ES);
     uint8_t *goh = obasis + dd.slab_off;
-    uint8_t *gol = goh + svdq_align_up(D * (int64_t)kn * ES, 256);
+    uint8_t *gol = SVDQ_SLAB_LOW(goh, D, kn, ES);
     float *gom = wmean ? omean + dd.mean_off : nullptr;
 
     float mpf[RPL] = {}, bpf[RPL] = {};
@@ -428,15 +409,18 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
         ustage_fetch(ureg, ustage_plan<ES>(c0, nr, k, nl), gUh, gUl, lane);
     };
 
-    prefetch(cpos);
-    while (true) {
-        const int nr = block_rows<RB>(cpos, cend);
-        const UStage cur = ustage_plan<ES>(cpos, nr, k, nl);
+    auto stage = [&](const UStage &cur, int) {
         ustage_commit(Ubuf, ureg, cur, lane);
         if (gmean) {
 #pragma unroll
             for (int m = 0; m < RPL; ++m) Ms[64 * m + lane] = mpf[m];
         }
+    };
+    prefetch(cpos);
+    while (true) {
+        const int nr = block_rows<RB>(cpos, cend);
+        const UStage cur = ustage_plan<ES>(cpos, nr, k, nl);
+        stage(cur, nr);
         lds_fence();
         const bool more = cpos + RB < cend;
         if (more) prefetch(cpos + RB);
@@ -452,9 +436,7 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
             aoff[s] = 0;
             astr[s] = 0;
             if (i < r) {
-                const bool hi = i < k;
-                astr[s] = (hi ? k : nl) * ES;
-                aoff[s] = (hi ? cur.offh * ES : 16 * cur.nvh + cur.offl * ES) + (hi ? i : i - k) * ES;
+                ustage_column(cur, i, k, nl, ES, aoff[s], astr[s]);
             } else if (i < ra) {
                 aoff[s] = moff;
                 astr[s] = 4;
@@ -464,10 +446,10 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
             }
         }
         auto a_operand = [&](int s, int row) -> float {
-            const uint8_t *ap = lds_raw + aoff[s] + row * astr[s];
+            const int ao = aoff[s] + row * astr[s];
             float a;
-            if ((mmask >> s) & 1u) a = *reinterpret_cast<const float *>(ap);
-            else a = cs_lds_u(ap, T{});
+            if ((mmask >> s) & 1u) a = lds_u(lds_raw, ao, float{});
+            else a = lds_u(lds_raw, ao, T{});
             return ((zmask >> s) & 1u) ? 0.f : a;
         };
         const int nrt = (nr + 15) >> 4;
@@ -506,8 +488,8 @@ __global__ __launch_bounds__(64) void k_plan_rebase(const SvdqParam *__restrict_
                     if (s < nsteps) {      // wave-uniform, and so is s < nfull
                         float a0, a1;
                         if (s < nfull) {
-                            a0 = cs_lds_u(lds_raw + aoff[s] + row0 * astr[s], T{});
-                            a1 = cs_lds_u(lds_raw + aoff[s] + row1 * astr[s], T{});
+                            a0 = lds_u(lds_raw, aoff[s] + row0 * astr[s], T{});
+                            a1 = lds_u(lds_raw, aoff[s] + row1 * astr[s], T{});
                         } else {
                             a0 = a_operand(s, row0);
                             a1 = a_operand(s, row1);
@@ -632,14 +614,10 @@ extern "C" int svdq_plan_consolidate_eig(const svdq_plan *src, const svdq_plan *
         svdq_set_error("%s: keep (host and device), the two small buffers, basis_gram and rebase are required", who);
         return SVDQ_EINVAL;
     }
-    if (((uintptr_t)keep_dev | (uintptr_t)rows_dev | (uintptr_t)basis_gram) & 7) {
-        svdq_set_error("%s: keep, rows and basis_gram must be 8-byte aligned", who);
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(keep_dev, rows_dev, basis_gram), 8, "keep, rows and basis_gram"))
         return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)src_small | (uintptr_t)dst_small | (uintptr_t)rebase) & 15) {
-        svdq_set_error("%s: the small buffers and rebase must be 16-byte aligned", who);
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(src_small, dst_small, rebase), 16, "the small buffers and rebase"))
         return SVDQ_EINVAL;
-    }
     if (!(min_sigma >= 0.f) || !(min_sigma <= 3.0e38f)) {
         svdq_set_error("%s: min_sigma must be finite and >= 0", who);
         return SVDQ_EINVAL;
@@ -651,30 +629,13 @@ extern "C" int svdq_plan_consolidate_eig(const svdq_plan *src, const svdq_plan *
                            (long long)(e / ND), (long long)(e % ND), (int)keep_host[e], NS);
             return SVDQ_EINVAL;
         }
-    const svdq_small_layout &LS = src->small, &LD = dst->small;
-    const uint8_t *ss = reinterpret_cast<const uint8_t *>(src_small);
-    uint8_t *ds = reinterpret_cast<uint8_t *>(dst_small);
-    CsSmall o;
-    o.sigma = reinterpret_cast<float *>(ds + LD.sigma_off);
-    o.k = reinterpret_cast<int32_t *>(ds + LD.k_off);
-    o.r = reinterpret_cast<int32_t *>(ds + LD.r_off);
-    o.energy = reinterpret_cast<float *>(ds + LD.energy_off);
-    o.rows = reinterpret_cast<int64_t *>(ds + LD.rows_off);
-    o.chigh = reinterpret_cast<uint16_t *>(ds + LD.chigh_off);
-    o.codes = ds + LD.codes_off;
-    o.scale = reinterpret_cast<float *>(ds + LD.scale_off);
-    o.zp = reinterpret_cast<float *>(ds + LD.zp_off);
-    o.rnorm = reinterpret_cast<float *>(ds + LD.rnorm_off);
-    o.coef = reinterpret_cast<float *>(ds + LD.coef_off);
-    o.status = reinterpret_cast<int32_t *>(ds + LD.status_off);
+    const SmallView ss = small_view(src->small, src_small);
+    const CsSmall o{small_view_mut(dst->small, dst_small)};
     hipLaunchKernelGGL(k_plan_consolidate_eig, dim3(P), dim3(EIG_THREADS), 0, (hipStream_t)stream, src->d_params, rows_dev,
                        NS, ND, src->cfg.rtvq_stages, src->cfg.center != 0, dst->cfg.center != 0,
                        dst->cfg.energy_threshold, dst->cfg.max_rank, dst->cfg.low_bits, dst->d_bits,
-                       dst->cfg.rtvq_stages, (double)min_sigma, keep_dev, basis_gram,
-                       reinterpret_cast<const int32_t *>(ss + LS.k_off), reinterpret_cast<const int32_t *>(ss + LS.r_off),
-                       reinterpret_cast<const uint16_t *>(ss + LS.chigh_off), ss + LS.codes_off,
-                       reinterpret_cast<const float *>(ss + LS.scale_off), reinterpret_cast<const float *>(ss + LS.zp_off),
-                       o, cs_table(rebase, P));
+                       dst->cfg.rtvq_stages, (double)min_sigma, keep_dev, basis_gram, ss.k, ss.r, ss.chigh, ss.codes,
+                       ss.scale, ss.zp, o, cs_table(rebase, P));
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
 
@@ -696,31 +657,23 @@ extern "C" int svdq_plan_rebase(const svdq_plan *src, const svdq_plan *dst, cons
         svdq_set_error("%s: the destination's mean is required on a centred destination", who);
         return SVDQ_EINVAL;
     }
-    if ((uintptr_t)rows_dev & 7) {
-        svdq_set_error("%s: rows must be 8-byte aligned", who);
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(rows_dev), 8, "rows")) return SVDQ_EINVAL;
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(src_small, src_basis, src_mean, rebase, dst_basis, dst_mean), 16,
+                              "small, the basis and mean buffers and rebase"))
         return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)src_small | (uintptr_t)src_basis | (uintptr_t)src_mean | (uintptr_t)rebase | (uintptr_t)dst_basis |
-         (uintptr_t)dst_mean) & 15) {
-        svdq_set_error("%s: small, the basis and mean buffers and rebase must be 16-byte aligned", who);
-        return SVDQ_EINVAL;
-    }
     if (src->n_units <= 0) return SVDQ_OK;
-    const svdq_small_layout &LS = src->small;
-    const uint8_t *ss = reinterpret_cast<const uint8_t *>(src_small);
-    auto kk = reinterpret_cast<const int32_t *>(ss + LS.k_off), rr = reinterpret_cast<const int32_t *>(ss + LS.r_off);
+    const SmallView ss = small_view(src->small, src_small);
     const CsTable t = cs_table(const_cast<void *>(rebase), src->n_params);
     const float *mn = src->cfg.center ? src_mean : nullptr;      // an uncentred source has A = U
     float *om = dst->cfg.center ? dst_mean : nullptr;
     const int n = src->n_tasks, nd = dst->n_tasks;
     const bool ok = svdq_dispatch_bool(src->cfg.fp16 != 0, [&](auto f16_c) {
         constexpr bool U16 = f16_c;
-        return svdq_dispatch_int<8, 16, 32>(n <= 8 ? 8 : (n <= 16 ? 16 : 32), [&](auto cmax_c) {
+        return svdq_dispatch_int<8, 16, 32>(svdq_slot_class(n), [&](auto cmax_c) {
             constexpr int CMAX = cmax_c;
-            constexpr int RB = CMAX <= 16 ? 256 : 128, ES = U16 ? 2 : 4;
-            const size_t lds = cs_lds_bytes(RB, n, nd, ES);
+            const size_t lds = cs_lds_bytes(store_rb(CMAX), n, nd, U16 ? 2 : 4);
             hipLaunchKernelGGL((k_plan_rebase<U16, CMAX>), dim3(src->n_units), dim3(64), lds, (hipStream_t)stream,
-                               src->d_params, src->d_units, dst->d_params, rows_dev, n, nd, dst->cfg.center != 0, kk, rr,
+                               src->d_params, src->d_units, dst->d_params, rows_dev, n, nd, dst->cfg.center != 0, ss.k, ss.r,
                                reinterpret_cast<const uint8_t *>(src_basis), mn, t.w, t.bbar, t.r, t.k, t.live,
                                reinterpret_cast<uint8_t *>(dst_basis), om);
             return true;

@@ -38,6 +38,7 @@
 #include "svdq_dispatch.h"
 #include "svdq_input.h"
 #include "svdq_merge_stream.h"
+#include "svdq_small_view.h"
 
 #define MRG_MAX_SETS 8
 
@@ -1089,21 +1090,6 @@ __global__ __launch_bounds__(64) void k_diag_finish(const SvdqParam *__restrict_
 }
 
 // ------------------------------------------------------------------------------------ entry points
-// typed pointers into the packed small-artifact buffer the compressor left in HBM
-struct SmallView {
-    const int32_t *k, *r;
-    const uint16_t *chigh;
-    const uint8_t *codes;
-    const float *scale, *zp;
-};
-static SmallView small_view(const svdq_plan *pl, const void *small) {
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    return {reinterpret_cast<const int32_t *>(sm + L.k_off),   reinterpret_cast<const int32_t *>(sm + L.r_off),
-            reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
-            reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off)};
-}
-
 static int merge_args_ok(const svdq_plan *pl, const void *small, int32_t n_sets, const char *who) {
     if (!pl || !small) {
         svdq_set_error("%s: plan and small are required", who);
@@ -1128,7 +1114,7 @@ extern "C" int svdq_merge_coeffs(const svdq_plan *pl, const void *small, const f
         svdq_set_error("svdq_merge_coeffs: weights and cbar are required");
         return SVDQ_EINVAL;
     }
-    const SmallView sv = small_view(pl, small);
+    const SmallView sv = small_view(pl->small, small);
     hipLaunchKernelGGL(k_merge_coeff, dim3(pl->n_params), dim3(64), 0, (hipStream_t)stream, pl->n_tasks,
                        pl->cfg.rtvq_stages, n_sets, per_param, sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, weights,
                        order, cbar);
@@ -1138,7 +1124,7 @@ extern "C" int svdq_merge_coeffs(const svdq_plan *pl, const void *small, const f
 // the coefficients of single tasks: task [n_out] plan task indices, NULL = tasks 0 .. n_out - 1
 static void launch_task_coeff(const svdq_plan *pl, const void *small, const int32_t *task, int n_out, float *cbar,
                               hipStream_t st) {
-    const SmallView sv = small_view(pl, small);
+    const SmallView sv = small_view(pl->small, small);
     hipLaunchKernelGGL(k_task_coeff, dim3(pl->n_params), dim3(64), 0, st, pl->n_tasks, pl->cfg.rtvq_stages, n_out, task,
                        sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, cbar);
 }
@@ -1165,7 +1151,7 @@ static int launch_reconstruct(const char *who, const svdq_plan *pl, const int64_
         svdq_set_error("%s: set_share is required when n_sets > 1", who);
         return SVDQ_EINVAL;
     }
-    const SmallView sv = small_view(pl, small);
+    const SmallView sv = small_view(pl->small, small);
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
@@ -1267,7 +1253,7 @@ static int launch_task_reconstruct(const char *who, bool masked, const svdq_plan
     hipStream_t st = (hipStream_t)stream;
     float *cbar = reinterpret_cast<float *>(work);
     launch_task_coeff(pl, small, task, (int)n_out, cbar, st);
-    const SmallView sv = small_view(pl, small);
+    const SmallView sv = small_view(pl->small, small);
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);
@@ -1342,7 +1328,7 @@ static int run_diagnostics(const char *who, const svdq_plan *pl, const void *del
     // every task's own coefficients: what k_merge_coeff gives for the one-hot sets, without a weight table
     launch_task_coeff(pl, small, nullptr, (int)n, ctask, st);
     if (hipGetLastError() != hipSuccess) return SVDQ_EHIP;
-    const SmallView sv = small_view(pl, small);
+    const SmallView sv = small_view(pl->small, small);
     auto bs = reinterpret_cast<const uint8_t *>(basis);
     auto pp = reinterpret_cast<const float *const *>(delta_ptrs);
     auto mp = reinterpret_cast<const uint8_t *const *>(mask_ptrs);

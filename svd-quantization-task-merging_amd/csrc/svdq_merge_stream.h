@@ -2,8 +2,11 @@
 // k_task_reconstruct and k_task_expand are the order in which they call these pieces plus their family's epilogue;
 // k_diag takes the byte count, ustage_fetch and unit_source_range; k_merge_expand takes the types, ustage_plan,
 // lds_fence and unit_source_range and carries its own copy of the other steps (its launch is sized by StreamLds; the
-// comment at the kernel says why).  svdq_ties.hip builds its two streaming kernels from the same pieces.  Included by
-// files compiled with -ffp-contract=off alone (every product and sum is rounded where the reference's torch ops round).
+// comment at the kernel says why).  svdq_ties.hip builds its two streaming kernels from the same pieces, and the passes
+// over a plan's stored artifacts (plan_project, plan_extend, store_gram, consolidate) take the staging from here and
+// their own shared steps -- the clamped unit view, the staged image by column, the block loop -- from svdq_store_pass.h,
+// which includes this file.  Included by files compiled with -ffp-contract=off alone (every product and sum is rounded
+// where the reference's torch ops round).
 #pragma once
 
 #include "svdq_common.h"
@@ -63,6 +66,10 @@ template <int RB> __device__ __forceinline__ int block_rows(int64_t pos, int64_t
 }
 
 // ------------------------------------------------------------------------------------ a unit's view of the plan
+// THE slab split: U_low [D][r - k] starts on the first 256-byte boundary behind U_high [D][k] (include/svdq.h).  A macro:
+// as an inlined function the same expression reaches the scheduler in another order and the merge kernels move.
+#define SVDQ_SLAB_LOW(gUh, D, k, ES) ((gUh) + svdq_align_up((D) * (int64_t)(k) * (ES), 256))
+
 struct UnitView {
     int64_t D;                    // rows of the parameter (compacted rows of a masked region)
     int k, nl;                    // columns of U_high, of U_low
@@ -79,7 +86,7 @@ __device__ __forceinline__ UnitView unit_view(const SvdqParam &pd, int p, const 
     v.k = k_in[p];
     v.nl = r_in[p] - v.k;
     v.gUh = basis + pd.slab_off;
-    v.gUl = v.gUh + svdq_align_up(v.D * (int64_t)v.k * ES, 256);
+    v.gUl = SVDQ_SLAB_LOW(v.gUh, v.D, v.k, ES);
     v.gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
     v.gbase = base_ptrs ? (mg_gfloat *)base_ptrs[p] : nullptr;
     return v;

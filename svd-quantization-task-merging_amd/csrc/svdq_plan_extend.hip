@@ -23,27 +23,15 @@
 #include "svdq_input.h"
 #include "svdq_merge_stream.h"
 #include "svdq_plan_rows.h"
+#include "svdq_small_view.h"
+#include "svdq_store_pass.h"
 
 #define PE_MT SVDQ_MAX_NEW_TASKS
 #define PE_NS 68      // stride (floats) of one task's 64 lane sums of xc^2
 
-typedef float pe_f32x2 __attribute__((ext_vector_type(2)));
-
-__host__ __device__ constexpr int pe_xs(int rb) { return rb + 4; }      // strip stride (floats)
 // dynamic LDS: the staged basis rows | X [8][XS] | C [32][8] coefficient image | [8][PE_NS] lane sums (write pass: Z [8][8])
 __host__ __device__ constexpr size_t pe_lds_bytes(int rb, int n, int es) {
-    return (size_t)stream_ubytes(rb, n, es) + (size_t)PE_MT * pe_xs(rb) * 4 + 32 * PE_MT * 4 + PE_MT * PE_NS * 4;
-}
-
-// k and r as every consumer reads them, held to what the slab has room for (svdq_plan_import's rule)
-__device__ __forceinline__ void pe_ranks(const int32_t *k_in, const int32_t *r_in, int p, int64_t rows, int n, int &k,
-                                         int &r) {
-    const int64_t rmax = rows < n ? rows : n;
-    int64_t rr = r_in[p], kk = k_in[p];
-    rr = rr < 0 ? 0 : (rr > rmax ? rmax : rr);
-    kk = kk < 0 ? 0 : (kk > rr ? rr : kk);
-    k = (int)kk;
-    r = (int)rr;
+    return (size_t)stream_ubytes(rb, n, es) + (size_t)PE_MT * plan_strip_stride(rb) * 4 + 32 * PE_MT * 4 + PE_MT * PE_NS * 4;
 }
 
 // THE residual: e[m][s] <- fma(-u[rl[m]][i], C[i][t0 + s], e[m][s]) over the columns in order, U_high then U_low; e holds
@@ -90,8 +78,7 @@ __device__ __forceinline__ void pe_unit(const SvdqParam *__restrict__ params, co
                                         void *const *__restrict__ out_ptrs) {
     using T = typename UElem<U16>::type;
     constexpr int ES = U16 ? 2 : 4;
-    constexpr int RPL = NTP > 16 ? 2 : 4, RB = 64 * RPL, XS = pe_xs(RB);
-    constexpr int SV = (RB * NTP * ES / 16 + 2 + 63) / 64;
+    constexpr int RPL = store_rpl(NTP), RB = store_rb(NTP), XS = plan_strip_stride(RB), SV = store_sv(NTP, ES);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NT, u = blockIdx.x;
     const int g = lane >> 4, col = lane & 15;
@@ -102,8 +89,9 @@ __device__ __forceinline__ void pe_unit(const SvdqParam *__restrict__ params, co
     const SvdqUnit ud = units[u];
     const int p = ud.param;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
+    // the unit's rows and, below, its view of the plan and the block loop, written out: as store_unit / stream_blocks
+    // (svdq_store_pass.h) this kernel spills more scalar registers
+    const int64_t D = plan_rows_of(pd, rows_dev, p);
     int64_t cpos = ud.row0;
     int64_t cend = ud.row0 + ud.nrows;
     if (cend > D) cend = D;
@@ -118,10 +106,10 @@ __device__ __forceinline__ void pe_unit(const SvdqParam *__restrict__ params, co
     }
     if (cpos < cend) {      // wave-uniform
         int k, r;
-        pe_ranks(k_in, r_in, p, D, n, k, r);
+        plan_ranks(k_in, r_in, p, D, n, k, r);
         const int nl = r - k;
         const uint8_t *gUh = basis + pd.slab_off;
-        const uint8_t *gUl = gUh + svdq_align_up(D * (int64_t)k * ES, 256);
+        const uint8_t *gUl = SVDQ_SLAB_LOW(gUh, D, k, ES);
         mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
         gin<TIN> *dp[PE_MT];
 #pragma unroll
@@ -151,36 +139,18 @@ __device__ __forceinline__ void pe_unit(const SvdqParam *__restrict__ params, co
             ustage_fetch(ureg, ustage_plan<ES>(c0, block_rows<RB>(c0, cend), k, nl), gUh, gUl, lane);
         };
 
+        auto stage = [&](const UStage &cur, int) {
+            ustage_commit(Ubuf, ureg, cur, lane);
+            plan_rows_commit<PE_MT, RPL, FB, !WRITE>(X, xpf, mpf, bpf, dp, gmean != nullptr, lane, NS, PE_NS);
+        };
         prefetch(cpos);
         while (true) {
             const int nr = block_rows<RB>(cpos, cend);
             const UStage cur = ustage_plan<ES>(cpos, nr, k, nl);
-            ustage_commit(Ubuf, ureg, cur, lane);
-            // xc = (finetuned - base) - mean, each a single fp32 subtraction; rows past the block's end are 0 - 0 - 0
-#pragma unroll
-            for (int t = 0; t < PE_MT; ++t)
-                if (dp[t]) {
-                    float xc[RPL];
-                    float sq = 0.f;
-#pragma unroll
-                    for (int e = 0; e < RPL; ++e) {
-                        float x = xpf[t][e];
-                        if constexpr (FB) x = __fsub_rn(x, bpf[e]);
-                        if (gmean) x = __fsub_rn(x, mpf[e]);
-                        xc[e] = x;
-                        sq = fmaf(x, x, sq);
-                    }
-                    if constexpr (RPL == 4) {
-                        *reinterpret_cast<f32x4 *>(X + t * XS + 4 * lane) = f32x4{xc[0], xc[1], xc[2], xc[3]};
-                    } else {
-                        *reinterpret_cast<pe_f32x2 *>(X + t * XS + 2 * lane) = pe_f32x2{xc[0], xc[1]};
-                    }
-                    if constexpr (!WRITE) NS[t * PE_NS + lane] = sq;
-                }
+            stage(cur, nr);
             lds_fence();
             const bool more = cpos + RB < cend;
             if (more) prefetch(cpos + RB);
-
             // ---- e in place: lane l takes rows l, 64 + l, ... of the block (conflict-free reads of the row-major basis
             // image).  A row past the block's count was never staged: its basis row is clamped into the block and its e
             // forced to the exact zero its xc is (NaN * 0 is NaN).
@@ -300,8 +270,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_plan_extend_eig(
     __shared__ int order[PE_MT], slot[PE_MT], s_m;
     const int p = blockIdx.x, n = NT, tid = threadIdx.x;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
+    const int64_t D = plan_rows_of(pd, rows_dev, p);
     // every field of the entry is written, whatever follows: the same bytes in every run
     if (tid < PE_MT * PE_MT) {
         z_out[(size_t)p * 64 + tid] = 0.f;
@@ -367,7 +336,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_plan_extend_eig(
     }
     if (tid == 0) {
         int k, r;
-        pe_ranks(k_in, r_in, p, D, n, k, r);
+        plan_ranks(k_in, r_in, p, D, n, k, r);
         double nmax = 0.0;
         for (int j = 0; j < np; ++j) nmax = Ns[slot[j]] > nmax ? Ns[slot[j]] : nmax;
         const double thr = min_residual * min_residual * nmax;
@@ -433,18 +402,12 @@ static int pe_check(const char *who, const svdq_plan *pl, const void *task_ptrs,
         svdq_set_error("%s: the plan, task_ptrs, basis, small, ext and %s are required", who, other_name);
         return SVDQ_EINVAL;
     }
-    if (pl->cfg.center && !mean) {
-        svdq_set_error("%s: mean is required on a centred plan", who);
+    if (svdq_refuse_no_mean(who, pl, mean)) return SVDQ_EINVAL;
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(task_ptrs, base_ptrs, index_ptrs, rows_dev, other), 8,
+                              "pointer tables, rows and ", other_name))
         return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)task_ptrs | (uintptr_t)base_ptrs | (uintptr_t)index_ptrs | (uintptr_t)rows_dev | (uintptr_t)other) & 7) {
-        svdq_set_error("%s: pointer tables, rows and %s must be 8-byte aligned", who, other_name);
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(small, basis, mean, ext), 16, "small, basis, mean and ext"))
         return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)small | (uintptr_t)basis | (uintptr_t)mean | (uintptr_t)ext) & 15) {
-        svdq_set_error("%s: small, basis, mean and ext must be 16-byte aligned", who);
-        return SVDQ_EINVAL;
-    }
     if (n_new < 1 || n_new > PE_MT || n_new > pl->n_tasks) {
         svdq_set_error("%s: n_new = %d new tasks, need 1 <= n_new <= min(%d, the plan's %d slots)", who, (int)n_new, PE_MT,
                        (int)pl->n_tasks);
@@ -458,10 +421,7 @@ template <bool WRITE, typename... Tail>
 static bool pe_launch(const svdq_plan *pl, const void *task_ptrs, const void *base_ptrs, const void *index_ptrs,
                       const int64_t *rows_dev, const void *basis, const float *mean, const void *small, int n_new,
                       hipStream_t st, Tail... tail) {
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
-    auto cf = reinterpret_cast<const float *>(sm + L.coef_off);
+    const SmallView sv = small_view(pl->small, small);
     auto tp = reinterpret_cast<const void *const *>(task_ptrs), bp = reinterpret_cast<const void *const *>(base_ptrs);
     auto ip = reinterpret_cast<const int32_t *const *>(index_ptrs);
     auto bs = reinterpret_cast<const uint8_t *>(basis);
@@ -471,22 +431,21 @@ static bool pe_launch(const svdq_plan *pl, const void *task_ptrs, const void *ba
         using TIN = typename decltype(tin_c)::type;
         return svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
             constexpr bool U16 = f16_c;
-            return svdq_dispatch_int<8, 16, 32>(n <= 8 ? 8 : (n <= 16 ? 16 : 32), [&](auto ntp_c) {
+            return svdq_dispatch_int<8, 16, 32>(svdq_slot_class(n), [&](auto ntp_c) {
                 constexpr int NTP = ntp_c;
                 return svdq_dispatch_bool(index_ptrs != nullptr, [&](auto gather_c) {
                     constexpr bool GATHER = gather_c;
                     return svdq_dispatch_bool(base_ptrs != nullptr, [&](auto fb_c) {
                         constexpr bool FB = fb_c;
-                        constexpr int RB = NTP <= 16 ? 256 : 128, ES = U16 ? 2 : 4;
-                        const size_t lds = pe_lds_bytes(RB, n, ES);
+                        const size_t lds = pe_lds_bytes(store_rb(NTP), n, U16 ? 2 : 4);
                         if constexpr (WRITE)
                             hipLaunchKernelGGL((k_plan_extend_write<U16, TIN, NTP, GATHER, FB>), dim3(pl->n_units), dim3(64),
-                                               lds, st, pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, n_new, kk, rr, cf,
-                                               bs, mn, tail...);
+                                               lds, st, pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, n_new, sv.k, sv.r,
+                                               sv.coef, bs, mn, tail...);
                         else
                             hipLaunchKernelGGL((k_plan_residual_gram<U16, TIN, NTP, GATHER, FB>), dim3(pl->n_units), dim3(64),
-                                               lds, st, pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, n_new, kk, rr, cf,
-                                               bs, mn, tail...);
+                                               lds, st, pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, n_new, sv.k, sv.r,
+                                               sv.coef, bs, mn, tail...);
                         return true;
                     });
                 });
@@ -517,13 +476,11 @@ extern "C" int svdq_plan_residual_gram(const svdq_plan *pl, const void *task_ptr
     }
     if (pl->n_params <= 0) return SVDQ_OK;
     const svdq_extend_layout E = pe_layout(pl->n_params);
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
+    const SmallView sv = small_view(pl->small, small);
     uint8_t *ex = reinterpret_cast<uint8_t *>(ext);
     hipLaunchKernelGGL(k_plan_extend_eig, dim3(pl->n_params), dim3(EIG_THREADS), 0, st, pl->d_params,
                        reinterpret_cast<const void *const *>(task_ptrs), rows_dev, pl->n_tasks, (int)n_new,
-                       reinterpret_cast<const int32_t *>(sm + L.k_off), reinterpret_cast<const int32_t *>(sm + L.r_off),
-                       partH, partN, (double)min_residual, reinterpret_cast<int32_t *>(ex + E.m_off),
+                       sv.k, sv.r, partH, partN, (double)min_residual, reinterpret_cast<int32_t *>(ex + E.m_off),
                        reinterpret_cast<double *>(ex + E.lambda_off), reinterpret_cast<float *>(ex + E.z_off),
                        reinterpret_cast<float *>(ex + E.d_off), reinterpret_cast<double *>(ex + E.xnorm_off),
                        reinterpret_cast<double *>(ex + E.enorm_off));

@@ -24,28 +24,14 @@
 #include "svdq_input.h"
 #include "svdq_merge_stream.h"
 #include "svdq_plan_rows.h"
+#include "svdq_small_view.h"
+#include "svdq_store_pass.h"
 
-typedef float pp_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float pp_lds_u(const uint8_t *base, int byte_off, __half) {
-    return __half2float(*reinterpret_cast<const __half *>(base + byte_off));
+// dynamic LDS: the staged basis rows | X [n][XS].  The launcher sizes it with bytes, the kernel carves it with the offset.
+__host__ __device__ constexpr size_t pp_x_off(int rb, int n, int es) { return (size_t)stream_ubytes(rb, n, es); }
+__host__ __device__ constexpr size_t pp_lds_bytes(int rb, int n, int es) {
+    return pp_x_off(rb, n, es) + (size_t)n * plan_strip_stride(rb) * 4;
 }
-__device__ __forceinline__ float pp_lds_u(const uint8_t *base, int byte_off, float) {
-    return *reinterpret_cast<const float *>(base + byte_off);
-}
-
-// k and r as every consumer reads them, held to what the slab has room for (svdq_plan_import's rule)
-__device__ __forceinline__ void pp_ranks(const int32_t *k_in, const int32_t *r_in, int p, int64_t rows, int n, int &k,
-                                         int &r) {
-    const int64_t rmax = rows < n ? rows : n;
-    int64_t rr = r_in[p], kk = k_in[p];
-    rr = rr < 0 ? 0 : (rr > rmax ? rmax : rr);
-    kk = kk < 0 ? 0 : (kk > rr ? rr : kk);
-    k = (int)kk;
-    r = (int)rr;
-}
-
-__host__ __device__ constexpr int pp_xs(int rb) { return rb + 4; }      // strip stride (floats)
 
 // NTP: the task slots the instantiation has registers for (8, 16 or 32 >= N): the prefetch registers of a block are
 // NTP x RPL task values and the block's basis rows, and with them sized to the plan the kernel runs at three to four
@@ -65,21 +51,18 @@ __global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict
     using T = typename UElem<U16>::type;
     constexpr int ES = U16 ? 2 : 4;
     constexpr int TL = NTP > 16 ? 2 : 1;
-    constexpr int RPL = TL == 1 ? 4 : 2, RB = 64 * RPL, XS = pp_xs(RB);
-    constexpr int SV = (RB * NTP * ES / 16 + 2 + 63) / 64;
+    constexpr int RPL = store_rpl(NTP), RB = store_rb(NTP), XS = plan_strip_stride(RB), SV = store_sv(NTP, ES);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NT, u = blockIdx.x;
     const int g = lane >> 4, col = lane & 15;
     uint8_t *Ubuf = lds_raw;
-    float *X = reinterpret_cast<float *>(lds_raw + stream_ubytes(RB, n, ES));      // [n][XS]
+    float *X = reinterpret_cast<float *>(lds_raw + pp_x_off(RB, n, ES));      // [n][XS]
     const SvdqUnit ud = units[u];
     const int p = ud.param;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
-    int64_t cpos = ud.row0;
-    int64_t cend = ud.row0 + ud.nrows;
-    if (cend > D) cend = D;
+    const StoreUnit su = store_unit<ES>(pd, ud, p, plan_rows_of(pd, rows_dev, p), n, k_in, r_in, basis, meanbuf);
+    const int64_t cend = su.cend;
+    const int k = su.k, r = su.r, nl = su.nl;
     double accd[TL][TL][4];
 #pragma unroll
     for (int ti = 0; ti < TL; ++ti)
@@ -87,13 +70,9 @@ __global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict
         for (int tt = 0; tt < TL; ++tt)
 #pragma unroll
             for (int v = 0; v < 4; ++v) accd[ti][tt][v] = 0.0;
-    int k = 0, r = 0;
-    if (cpos < cend) pp_ranks(k_in, r_in, p, D, n, k, r);
-    if (cpos < cend && r > 0) {      // wave-uniform
-        const int nl = r - k;
-        const uint8_t *gUh = basis + pd.slab_off;
-        const uint8_t *gUl = gUh + svdq_align_up(D * (int64_t)k * ES, 256);
-        mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
+    if (su.cpos < cend && r > 0) {      // wave-uniform
+        const uint8_t *gUh = su.gUh, *gUl = su.gUl;
+        mg_gfloat *gmean = su.gmean;
         gin<TIN> *dp[NTP];
 #pragma unroll
         for (int t = 0; t < NTP; ++t) dp[t] = t < n ? (gin<TIN> *)ptrs[(size_t)p * n + t] : nullptr;
@@ -120,6 +99,9 @@ __global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict
             for (int ti = 0; ti < TL; ++ti) {
                 int i = col + 16 * ti;
                 if (i >= r) i = 0;
+                // ustage_column's expression with the lane's row 4 g inside it, written out: through the shared function
+                // the 32-slot fp32-input instantiations wait for the next block's loads inside the matrix loop (DESIGN.md
+                // section 27)
                 const bool hi = i < k;
                 const int w = hi ? k : nl;
                 urow[ti] = w * ES;
@@ -151,7 +133,7 @@ __global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict
                     for (int ti = 0; ti < TL; ++ti) {
                         a[ti] = 0.f;
                         if (ti < ntile_i) {      // wave-uniform
-                            a[ti] = pp_lds_u(Ubuf, ua[ti] + (16 * s + v) * urow[ti], T{});
+                            a[ti] = lds_u(Ubuf, ua[ti] + (16 * s + v) * urow[ti], T{});
                             // rows past the block's count were never staged: whatever sits there must not reach the
                             // matrix pipe (their x is an exact zero, but NaN * 0 is NaN)
                             if constexpr (MASKED) a[ti] = (16 * s + 4 * g + v < count) ? a[ti] : 0.f;
@@ -174,38 +156,16 @@ __global__ __launch_bounds__(64) void k_plan_project(const SvdqParam *__restrict
                     for (int v = 0; v < 4; ++v) accd[ti][tt][v] += (double)acc[ti][tt][v];
         };
 
-        prefetch(cpos);
-        while (true) {
-            const int nr = block_rows<RB>(cpos, cend);
-            const UStage cur = ustage_plan<ES>(cpos, nr, k, nl);
-            ustage_commit(Ubuf, ureg, cur, lane);
-            // xc = (finetuned - base) - mean, each a single fp32 subtraction; rows past the block's end are 0 - 0 - 0
-#pragma unroll
-            for (int t = 0; t < NTP; ++t)
-                if (dp[t]) {
-                    float xc[RPL];
-#pragma unroll
-                    for (int e = 0; e < RPL; ++e) {
-                        float x = xpf[t][e];
-                        if constexpr (FB) x = __fsub_rn(x, bpf[e]);
-                        if (gmean) x = __fsub_rn(x, mpf[e]);
-                        xc[e] = x;
-                    }
-                    if constexpr (RPL == 4) {
-                        *reinterpret_cast<f32x4 *>(X + t * XS + 4 * lane) = f32x4{xc[0], xc[1], xc[2], xc[3]};
-                    } else {
-                        *reinterpret_cast<pp_f32x2 *>(X + t * XS + 2 * lane) = pp_f32x2{xc[0], xc[1]};
-                    }
-                }
-            lds_fence();
-            const bool more = cpos + RB < cend;
-            if (more) prefetch(cpos + RB);
-            if (nr == RB) compute(cur, nr, std::false_type{});
-            else compute(cur, nr, std::true_type{});
-            if (!more) break;
-            cpos += RB;
-            lds_fence();      // the strips and the basis rows are rewritten next
-        }
+        stream_blocks<RB, ES>(
+            su.cpos, cend, k, nl, prefetch,
+            [&](const UStage &cur, int) {
+                ustage_commit(Ubuf, ureg, cur, lane);
+                plan_rows_commit<NTP, RPL, FB, false>(X, xpf, mpf, bpf, dp, gmean != nullptr, lane);
+            },
+            [&](const UStage &cur, int64_t, int nr, bool) {
+                if (nr == RB) compute(cur, nr, std::false_type{});
+                else compute(cur, nr, std::true_type{});
+            });
     }
     // the unit's partial [task][column]: result register v of tile (ti, tt) is column 16 ti + 4 g + v of task 16 tt + col.
     // Columns past r and absent slots leave as zeros, so work_dev is the same bytes in every run.
@@ -236,13 +196,12 @@ __global__ __launch_bounds__(EIG_THREADS) void k_plan_project_finish(
     __shared__ float res[32 * LDN];
     const int p = blockIdx.x, n = NT;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
+    const int64_t D = plan_rows_of(pd, rows_dev, p);
     if (D <= 0) return;      // workgroup-uniform: nothing of p is written
     if (bits_tab) bits = bits_tab[p];
     reduce_partials(part, pd.unit_begin, pd.unit_begin + pd.unit_count, n * n, red, C);
     int k, r;
-    pp_ranks(k_in, r_in, p, D, n, k, r);
+    plan_ranks(k_in, r_in, p, D, n, k, r);
     coeff_store_quantize(p, n, k, r, bits, stages, C, nullptr, ptrs + (size_t)p * n, res, coef_out, chigh_out, codes_out,
                          scale_out, zp_out, rnorm_out);
 }
@@ -259,21 +218,13 @@ extern "C" int svdq_plan_project(const svdq_plan *pl, const void *task_ptrs, con
         svdq_set_error("svdq_plan_project: the plan, task_ptrs, basis, small and work are required");
         return SVDQ_EINVAL;
     }
-    if (pl->cfg.center && !mean) {
-        svdq_set_error("svdq_plan_project: mean is required on a centred plan");
+    const char *who = "svdq_plan_project";
+    if (svdq_refuse_no_mean(who, pl, mean)) return SVDQ_EINVAL;
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(task_ptrs, base_ptrs, index_ptrs, rows_dev, work), 8,
+                              "pointer tables, rows and work"))
         return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)task_ptrs | (uintptr_t)base_ptrs | (uintptr_t)index_ptrs | (uintptr_t)rows_dev | (uintptr_t)work) & 7) {
-        svdq_set_error("svdq_plan_project: pointer tables, rows and work must be 8-byte aligned");
-        return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)small | (uintptr_t)basis | (uintptr_t)mean) & 15) {
-        svdq_set_error("svdq_plan_project: small, basis and mean must be 16-byte aligned");
-        return SVDQ_EINVAL;
-    }
-    const svdq_small_layout &L = pl->small;
-    uint8_t *sm = reinterpret_cast<uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(small, basis, mean), 16, "small, basis and mean")) return SVDQ_EINVAL;
+    const SmallViewMut sv = small_view_mut(pl->small, small);
     auto tp = reinterpret_cast<const void *const *>(task_ptrs), bp = reinterpret_cast<const void *const *>(base_ptrs);
     auto ip = reinterpret_cast<const int32_t *const *>(index_ptrs);
     auto bs = reinterpret_cast<const uint8_t *>(basis);
@@ -285,16 +236,15 @@ extern "C" int svdq_plan_project(const svdq_plan *pl, const void *task_ptrs, con
         using TIN = typename decltype(tin_c)::type;
         return svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
             constexpr bool U16 = f16_c;
-            return svdq_dispatch_int<8, 16, 32>(n <= 8 ? 8 : (n <= 16 ? 16 : 32), [&](auto ntp_c) {
+            return svdq_dispatch_int<8, 16, 32>(svdq_slot_class(n), [&](auto ntp_c) {
                 constexpr int NTP = ntp_c;
                 return svdq_dispatch_bool(index_ptrs != nullptr, [&](auto gather_c) {
                     constexpr bool GATHER = gather_c;
                     return svdq_dispatch_bool(base_ptrs != nullptr, [&](auto fb_c) {
                         constexpr bool FB = fb_c;
-                        constexpr int RB = NTP <= 16 ? 256 : 128, ES = U16 ? 2 : 4;
-                        const size_t lds = (size_t)stream_ubytes(RB, n, ES) + (size_t)n * pp_xs(RB) * 4;
+                        const size_t lds = pp_lds_bytes(store_rb(NTP), n, U16 ? 2 : 4);
                         hipLaunchKernelGGL((k_plan_project<U16, TIN, NTP, GATHER, FB>), dim3(pl->n_units), dim3(64), lds, st,
-                                           pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, kk, rr, bs, mn, part);
+                                           pl->d_params, pl->d_units, tp, bp, ip, rows_dev, n, sv.k, sv.r, bs, mn, part);
                         return true;
                     });
                 });
@@ -304,9 +254,7 @@ extern "C" int svdq_plan_project(const svdq_plan *pl, const void *task_ptrs, con
     if (!ok) return svdq_launch_status(false, "k_plan_project");
     if (hipGetLastError() != hipSuccess) return SVDQ_EHIP;
     hipLaunchKernelGGL(k_plan_project_finish, dim3(pl->n_params), dim3(EIG_THREADS), 0, st, pl->d_params, tp, rows_dev, n,
-                       pl->cfg.low_bits, pl->cfg.rtvq_stages, pl->d_bits, part, kk, rr,
-                       reinterpret_cast<float *>(sm + L.coef_off), reinterpret_cast<uint16_t *>(sm + L.chigh_off),
-                       sm + L.codes_off, reinterpret_cast<float *>(sm + L.scale_off),
-                       reinterpret_cast<float *>(sm + L.zp_off), reinterpret_cast<float *>(sm + L.rnorm_off));
+                       pl->cfg.low_bits, pl->cfg.rtvq_stages, pl->d_bits, part, sv.k, sv.r, sv.coef, sv.chigh, sv.codes,
+                       sv.scale, sv.zp, sv.rnorm);
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }

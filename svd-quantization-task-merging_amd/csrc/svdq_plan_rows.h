@@ -1,7 +1,8 @@
 // svdq_plan_rows.h -- the row loads of one block of a plan's work unit, shared by the kernels that form xc from new
 // task tensors against a stored basis: k_plan_project (svdq_plan_project.hip) and the two streaming passes of
 // svdq_plan_extend.hip.  "xc formed exactly as svdq_plan_project forms it" is part of the extension's contract
-// (include/svdq.h), so both read their rows through this one function: the same loads, the same zeros past the block.
+// (include/svdq.h), so both read their rows through plan_rows_fetch (the same loads, the same zeros past the block) and
+// form xc and write its strips through plan_rows_commit (the same two subtractions in the same order).
 #pragma once
 
 #include "svdq_input.h"
@@ -76,4 +77,37 @@ __device__ __forceinline__ void plan_rows_fetch(float (&xpf)[NS][RPL], float (&m
 #pragma unroll
         for (int e = 0; e < RPL; ++e) mpf[e] = (r0 + e < cend) ? gmean[r0 + e] : 0.f;
     }
+}
+
+// stride (floats) of one task slot's strip of a block of rb rows: rb + pad, a multiple of 4 (16-byte alignment)
+__host__ __device__ constexpr int plan_strip_stride(int rb) { return rb + 4; }
+
+// xc = (finetuned - base) - mean of what plan_rows_fetch left, each a single fp32 subtraction (rows past the block's end
+// are 0 - 0 - 0), written to the strips X[t][RPL lane ..] of the present slots.  SQ: the lane's sum of xc^2 per slot, an
+// fp32 fma chain over its rows, goes to sq[t * sq_stride + lane] (the extension's |xc|^2).
+template <int NS, int RPL, bool FB, bool SQ, typename DP>
+__device__ __forceinline__ void plan_rows_commit(float *X, const float (&xpf)[NS][RPL], const float (&mpf)[RPL],
+                                                 const float (&bpf)[RPL], const DP (&dp)[NS], bool has_mean, int lane,
+                                                 float *sq = nullptr, int sq_stride = 0) {
+    constexpr int XS = plan_strip_stride(64 * RPL);
+#pragma unroll
+    for (int t = 0; t < NS; ++t)
+        if (dp[t]) {
+            float xc[RPL];
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < RPL; ++e) {
+                float x = xpf[t][e];
+                if constexpr (FB) x = __fsub_rn(x, bpf[e]);
+                if (has_mean) x = __fsub_rn(x, mpf[e]);
+                xc[e] = x;
+                if constexpr (SQ) s = fmaf(x, x, s);
+            }
+            if constexpr (RPL == 4) {
+                *reinterpret_cast<f32x4 *>(X + t * XS + 4 * lane) = f32x4{xc[0], xc[1], xc[2], xc[3]};
+            } else {
+                *reinterpret_cast<svdq_f32x2 *>(X + t * XS + 2 * lane) = svdq_f32x2{xc[0], xc[1]};
+            }
+            if constexpr (SQ) sq[t * sq_stride + lane] = s;
+        }
 }

@@ -11,6 +11,7 @@
 #include "svdq_common.h"
 #include "svdq_dispatch.h"
 #include "svdq_coeff.h"
+#include "svdq_small_view.h"
 
 // First-level reduction, spread over the chip: chunk c of parameter p sums its share of the unit slots into
 // part2[(p*SVDQ_RC + c)][nn]; k_eig / k_coeff then only add SVDQ_RC partials per parameter.  Keeps the whole reduction
@@ -256,11 +257,7 @@ int svdq_launch_eig(const svdq_plan *pl, const SvdqInput &in, const double *gram
     // resolution of the data; fp32-product sums (SVDQ_SW_GRAM_F32, and N > 16 before its refinement) do not
     const bool exact = (pl->ntp <= 16 && !(pl->cfg.reserved & SVDQ_SW_GRAM_F32)) || only != nullptr;
     const float resolve = exact ? 1e-6f : 3e-4f;
-    const svdq_small_layout &L = pl->small;
-    float *sg = reinterpret_cast<float *>(small + L.sigma_off);
-    int32_t *kk = reinterpret_cast<int32_t *>(small + L.k_off), *rr = reinterpret_cast<int32_t *>(small + L.r_off);
-    float *en = reinterpret_cast<float *>(small + L.energy_off);
-    int64_t *ro = reinterpret_cast<int64_t *>(small + L.rows_off);
+    const SmallViewMut sv = small_view_mut(pl->small, small);
     // the input type only changes how k_eig reads row 0 of every task (the completion column)
     const bool ok = svdq_dispatch_input(pl->in_type, [&](auto tin_c) {
         using TIN = typename decltype(tin_c)::type;
@@ -268,7 +265,7 @@ int svdq_launch_eig(const svdq_plan *pl, const SvdqInput &in, const double *gram
             constexpr int THREADS = small_c ? 64 : 256, NMAX = small_c ? 8 : 32;
             hipLaunchKernelGGL((k_eig<THREADS, NMAX, TIN>), dim3(nparams), dim3(THREADS), 0, st, pl->d_params, in.tensors(),
                                in.rows_dev, pl->n_tasks, pl->cfg.center, pl->cfg.energy_threshold, pl->cfg.max_rank,
-                               gram_part2, W, c0, param0, sg, kk, rr, en, ro,
+                               gram_part2, W, c0, param0, sv.sigma, sv.k, sv.r, sv.energy, sv.rows,
                                static_cast<const int32_t *const *>(in.index), static_cast<const float *const *>(in.base), only,
                                refine_out, resolve, in.ustart);
             return true;
@@ -279,12 +276,9 @@ int svdq_launch_eig(const svdq_plan *pl, const SvdqInput &in, const double *gram
 
 int svdq_launch_coeff(const svdq_plan *pl, const double *cpart, const double *c0, uint8_t *small, int param0,
                       int nparams, hipStream_t st) {
-    const svdq_small_layout &L = pl->small;
+    const SmallViewMut sv = small_view_mut(pl->small, small);
     hipLaunchKernelGGL(k_coeff, dim3(nparams), dim3(EIG_THREADS), 0, st, pl->d_params, pl->n_tasks, pl->pack,
-                       pl->cfg.low_bits, pl->cfg.rtvq_stages, cpart, c0, reinterpret_cast<const int32_t *>(small + L.k_off),
-                       reinterpret_cast<const int32_t *>(small + L.r_off), reinterpret_cast<float *>(small + L.coef_off),
-                       reinterpret_cast<uint16_t *>(small + L.chigh_off), small + L.codes_off,
-                       reinterpret_cast<float *>(small + L.scale_off), reinterpret_cast<float *>(small + L.zp_off),
-                       reinterpret_cast<float *>(small + L.rnorm_off), param0, pl->d_bits);
+                       pl->cfg.low_bits, pl->cfg.rtvq_stages, cpart, c0, sv.k, sv.r, sv.coef, sv.chigh, sv.codes, sv.scale,
+                       sv.zp, sv.rnorm, param0, pl->d_bits);
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }

@@ -25,32 +25,14 @@
 #include "svdq_coeff.h"
 #include "svdq_dispatch.h"
 #include "svdq_merge_stream.h"
+#include "svdq_small_view.h"
+#include "svdq_store_pass.h"
 
 typedef _Float16 sg_f16x8 __attribute__((ext_vector_type(8)));
 
 #define SG_BG 33      // rows / columns of one parameter's basis_gram_dev matrix: r <= 32 columns and the mean
 
-// k and r as every consumer reads them, held to what the slab has room for (svdq_plan_import's rule)
-__device__ __forceinline__ void sg_ranks(const int32_t *k_in, const int32_t *r_in, int p, int64_t rows, int n, int &k,
-                                         int &r) {
-    const int64_t rmax = rows < n ? rows : n;
-    int64_t rr = r_in[p], kk = k_in[p];
-    rr = rr < 0 ? 0 : (rr > rmax ? rmax : rr);
-    kk = kk < 0 ? 0 : (kk > rr ? rr : kk);
-    k = (int)kk;
-    r = (int)rr;
-}
-
-// where column c (< r) of the basis sits in a block's staged image: byte offset of its element of the block's row 0, and
-// the byte stride from row to row
-__device__ __forceinline__ void sg_column(const UStage &cur, int c, int k, int nl, int es, int &off, int &stride) {
-    const bool hi = c < k;
-    const int w = hi ? k : nl;
-    stride = w * es;
-    off = (hi ? cur.offh * es : 16 * cur.nvh + cur.offl * es) + (hi ? c : c - k) * es;
-}
-
-// The lane's operand of one MFMA step: column `off`/`stride` (sg_column) of the rows the instruction's k index gives the
+// The lane's operand of one MFMA step: column `off`/`stride` (ustage_column) of the rows the instruction's k index gives the
 // lane.  fp16: 8 rows 32 s + 8 g + j (v_mfma_f32_16x16x32_f16; the same register set serves as A and B, so any k
 // assignment is consistent as long as both operands use it); fp32: row 4 s + g.  Rows past `count` were never staged:
 // whatever sits there must not reach the matrix pipe.
@@ -78,13 +60,6 @@ __device__ __forceinline__ f32x4 sg_mfma(const sg_f16x8 &a, const sg_f16x8 &b, c
 }
 __device__ __forceinline__ f32x4 sg_mfma(float a, float b, const f32x4 &c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float sg_lds_u(const uint8_t *lds, int byte_off, __half) {
-    return __half2float(*reinterpret_cast<const __half *>(lds + byte_off));
-}
-__device__ __forceinline__ float sg_lds_u(const uint8_t *lds, int byte_off, float) {
-    return *reinterpret_cast<const float *>(lds + byte_off);
 }
 
 // the sum of the 16 lanes of the lane's row (lanes 16 g .. 16 g + 15), in each of them: four DPP steps on the vector ALU
@@ -119,21 +94,18 @@ __global__ __launch_bounds__(64) void k_store_gram(const SvdqParam *__restrict__
     using T = typename UElem<U16>::type;
     constexpr int ES = U16 ? 2 : 4;
     constexpr int TL = CMAX > 16 ? 2 : 1;
-    constexpr int RPL = TL == 1 ? 4 : 2, RB = 64 * RPL;
+    constexpr int RPL = store_rpl(CMAX), RB = store_rb(CMAX), SV = store_sv(CMAX, ES);
     constexpr int KS = U16 ? 32 : 4;      // rows one MFMA contracts
-    constexpr int SV = (RB * CMAX * ES / 16 + 2 + 63) / 64;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NT, u = blockIdx.x;
     const int g = lane >> 4, col = lane & 15;
-    uint8_t *Ubuf = lds_raw;
+    uint8_t *Ubuf = lds_raw;      // sg_lds_bytes: the staged basis rows and nothing else
     const SvdqUnit ud = units[u];
     const int p = ud.param;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
-    int64_t cpos = ud.row0;
-    int64_t cend = ud.row0 + ud.nrows;
-    if (cend > D) cend = D;
+    const StoreUnit su = store_unit<ES>(pd, ud, p, plan_rows_of(pd, rows_dev, p), n, k_in, r_in, basis, meanbuf);
+    const int64_t cend = su.cend;
+    const int k = su.k, r = su.r, nl = su.nl;
     double accd[TL][TL][4];
 #pragma unroll
     for (int ti = 0; ti < TL; ++ti)
@@ -142,13 +114,9 @@ __global__ __launch_bounds__(64) void k_store_gram(const SvdqParam *__restrict__
 #pragma unroll
             for (int v = 0; v < 4; ++v) accd[ti][tj][v] = 0.0;
     double dm0 = 0.0, dm1 = 0.0, dmm = 0.0;      // lane (g, c): columns c and 16 + c of U^T m, and m^T m, of row g's rows
-    int k = 0, r = 0;
-    mg_gfloat *gmean = meanbuf ? (mg_gfloat *)(meanbuf + pd.mean_off) : nullptr;
-    if (cpos < cend) sg_ranks(k_in, r_in, p, D, n, k, r);
-    if (cpos < cend && (r > 0 || gmean)) {      // wave-uniform
-        const int nl = r - k;
-        const uint8_t *gUh = basis + pd.slab_off;
-        const uint8_t *gUl = gUh + svdq_align_up(D * (int64_t)k * ES, 256);
+    mg_gfloat *gmean = su.gmean;
+    if (su.cpos < cend && (r > 0 || gmean)) {      // wave-uniform
+        const uint8_t *gUh = su.gUh, *gUl = su.gUl;
 
         // ---- the loads of one block into registers; lane l owns rows l, 64 + l, ... of the block for the mean column
         float mpf[RPL] = {}, bpf[RPL] = {}, mcur[RPL] = {};
@@ -170,7 +138,7 @@ __global__ __launch_bounds__(64) void k_store_gram(const SvdqParam *__restrict__
                 for (int ti = 0; ti < TL; ++ti) {
                     int i = col + 16 * ti;
                     if (i >= r) i = 0;
-                    sg_column(cur, i, k, nl, ES, uo[ti], us[ti]);
+                    ustage_column(cur, i, k, nl, ES, uo[ti], us[ti]);
                 }
                 f32x4 acc[TL][TL];
 #pragma unroll
@@ -216,10 +184,10 @@ __global__ __launch_bounds__(64) void k_store_gram(const SvdqParam *__restrict__
 #pragma unroll 4
                 for (int c = 0; c < r; ++c) {
                     int off, stride;
-                    sg_column(cur, c, k, nl, ES, off, stride);
+                    ustage_column(cur, c, k, nl, ES, off, stride);
                     float um = 0.f;
 #pragma unroll
-                    for (int m = 0; m < RPL; ++m) um = fmaf(sg_lds_u(Ubuf, off + rl[m] * stride, T{}), mv[m], um);
+                    for (int m = 0; m < RPL; ++m) um = fmaf(lds_u(Ubuf, off + rl[m] * stride, T{}), mv[m], um);
                     um = sg_row_sum(um);
                     if (col == (c & 15)) {
                         if (CMAX <= 16 || c < 16) dm0 += (double)um;
@@ -229,6 +197,9 @@ __global__ __launch_bounds__(64) void k_store_gram(const SvdqParam *__restrict__
             }
         };
 
+        // the block loop written out: as stream_blocks (svdq_store_pass.h) <fp16, 32> measured 2 % slower (DESIGN.md
+        // section 27)
+        int64_t cpos = su.cpos;
         prefetch(cpos);
         while (true) {
             const int nr = block_rows<RB>(cpos, cend);
@@ -287,8 +258,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_store_gram_finish(
     __shared__ double Cc[32 * SG_BG], Tm[SG_BG * 32];
     const int p = blockIdx.x, n = NT, tid = threadIdx.x;
     const SvdqParam pd = params[p];
-    int64_t D = rows_dev ? rows_dev[p] : pd.rows;
-    if (D > pd.rows) D = pd.rows;
+    const int64_t D = plan_rows_of(pd, rows_dev, p);
     double *G = task_gram + (size_t)p * n * n;
     double *B = basis_gram ? basis_gram + (size_t)p * SG_BG * SG_BG : nullptr;
     if (D <= 0) {      // workgroup-uniform: nothing of p is read, zeros are written
@@ -300,7 +270,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_store_gram_finish(
     reduce_partials(partU, pd.unit_begin, pd.unit_begin + pd.unit_count, n * n, red, S);
     reduce_partials(partM, pd.unit_begin, pd.unit_begin + pd.unit_count, n + 1, red, Mv);
     int k, r;
-    sg_ranks(k_in, r_in, p, D, n, k, r);
+    plan_ranks(k_in, r_in, p, D, n, k, r);
     const int ra = r + (centred ? 1 : 0);      // columns of A = [U | mean]
     // A^T A, read from the upper triangle of the totals: entry (a, b) and (b, a) are one number
     auto ata = [&](int a, int b) -> double {
@@ -344,6 +314,9 @@ __global__ __launch_bounds__(EIG_THREADS) void k_store_gram_finish(
     }
 }
 
+// dynamic LDS of k_store_gram
+__host__ __device__ constexpr size_t sg_lds_bytes(int rb, int n, int es) { return (size_t)stream_ubytes(rb, n, es); }
+
 extern "C" int64_t svdq_plan_store_gram_work_bytes(const svdq_plan *pl) {
     if (!pl) return 0;
     return svdq_align_up((int64_t)pl->n_units * ((int64_t)pl->n_tasks * pl->n_tasks + pl->n_tasks + 1) * 8, 256);
@@ -355,21 +328,12 @@ extern "C" int svdq_plan_store_gram(const svdq_plan *pl, const int64_t *rows_dev
         svdq_set_error("svdq_plan_store_gram: the plan, small, basis, work and task_gram are required");
         return SVDQ_EINVAL;
     }
-    if (pl->cfg.center && !mean) {
-        svdq_set_error("svdq_plan_store_gram: mean is required on a centred plan");
+    const char *who = "svdq_plan_store_gram";
+    if (svdq_refuse_no_mean(who, pl, mean)) return SVDQ_EINVAL;
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(rows_dev, work, task_gram, basis_gram), 8, "rows, work and the outputs"))
         return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)rows_dev | (uintptr_t)work | (uintptr_t)task_gram | (uintptr_t)basis_gram) & 7) {
-        svdq_set_error("svdq_plan_store_gram: rows, work and the outputs must be 8-byte aligned");
-        return SVDQ_EINVAL;
-    }
-    if (((uintptr_t)small | (uintptr_t)basis | (uintptr_t)mean) & 15) {
-        svdq_set_error("svdq_plan_store_gram: small, basis and mean must be 16-byte aligned");
-        return SVDQ_EINVAL;
-    }
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    auto kk = reinterpret_cast<const int32_t *>(sm + L.k_off), rr = reinterpret_cast<const int32_t *>(sm + L.r_off);
+    if (svdq_refuse_unaligned(who, svdq_addr_bits(small, basis, mean), 16, "small, basis and mean")) return SVDQ_EINVAL;
+    const SmallView sv = small_view(pl->small, small);
     auto bs = reinterpret_cast<const uint8_t *>(basis);
     const float *mn = pl->cfg.center ? mean : nullptr;      // an uncentred plan has A = U
     const int n = pl->n_tasks;
@@ -378,21 +342,18 @@ extern "C" int svdq_plan_store_gram(const svdq_plan *pl, const int64_t *rows_dev
     hipStream_t st = (hipStream_t)stream;
     const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
         constexpr bool U16 = f16_c;
-        return svdq_dispatch_int<8, 16, 32>(n <= 8 ? 8 : (n <= 16 ? 16 : 32), [&](auto cmax_c) {
+        return svdq_dispatch_int<8, 16, 32>(svdq_slot_class(n), [&](auto cmax_c) {
             constexpr int CMAX = cmax_c;
-            constexpr int RB = CMAX <= 16 ? 256 : 128, ES = U16 ? 2 : 4;
-            const size_t lds = (size_t)stream_ubytes(RB, n, ES);
+            const size_t lds = sg_lds_bytes(store_rb(CMAX), n, U16 ? 2 : 4);
             hipLaunchKernelGGL((k_store_gram<U16, CMAX>), dim3(pl->n_units), dim3(64), lds, st, pl->d_params, pl->d_units,
-                               rows_dev, n, kk, rr, bs, mn, partU, partM);
+                               rows_dev, n, sv.k, sv.r, bs, mn, partU, partM);
             return true;
         });
     });
     if (!ok) return svdq_launch_status(false, "k_store_gram");
     if (hipGetLastError() != hipSuccess) return SVDQ_EHIP;
     hipLaunchKernelGGL(k_store_gram_finish, dim3(pl->n_params), dim3(EIG_THREADS), 0, st, pl->d_params, rows_dev, n,
-                       pl->cfg.rtvq_stages, pl->cfg.center != 0, partU, partM, kk, rr,
-                       reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
-                       reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off),
-                       task_gram, basis_gram);
+                       pl->cfg.rtvq_stages, pl->cfg.center != 0, partU, partM, sv.k, sv.r, sv.chigh, sv.codes, sv.scale,
+                       sv.zp, task_gram, basis_gram);
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }

@@ -23,6 +23,8 @@
 #include "svdq_common.h"
 #include "svdq_dispatch.h"
 #include "svdq_merge_stream.h"
+#include "svdq_small_view.h"
+#include "svdq_store_pass.h"
 
 #define TIES_BINS 256
 #define TIES_DIGIT_BITS 8
@@ -107,18 +109,15 @@ __global__ __launch_bounds__(64) void k_ties_hist(const SvdqParam *__restrict__ 
         ustage_fetch(ureg, ustage_plan<ES>(rb, nr, k, nl), uv.gUh, uv.gUl, lane);
         load_rows(mpf, bpf, uv.gmean, uv.gbase, rb, nr, lane);
     };
-    prefetch(r_begin);
-    for (int64_t rb = r_begin; rb < r_end; rb += RB) {
-        const int rows_blk = block_rows<RB>(rb, r_end);
-        const UStage cur = ustage_plan<ES>(rb, rows_blk, k, nl);
+    float mv[RPL];
+    auto stage = [&](const UStage &cur, int) {
         ustage_commit(lds_raw, ureg, cur, lane);
-        float mv[RPL];
-        int rl[RPL];
-        block_rows_of_lane(rl, rows_blk, lane);
 #pragma unroll
         for (int m = 0; m < RPL; ++m) mv[m] = mpf[m];
-        lds_fence();
-        if (rb + RB < r_end) prefetch(rb + RB);
+    };
+    stream_blocks<RB, ES>(r_begin, r_end, k, nl, prefetch, stage, [&](const UStage &cur, int64_t, int rows_blk, bool) {
+        int rl[RPL];
+        block_rows_of_lane(rl, rows_blk, lane);
         const TU *Uh = ustage_high<TU>(lds_raw, cur), *Ul = ustage_low<TU>(lds_raw, cur);
         for (int g0 = 0; g0 < n_out; g0 += TG) {
             const unsigned gm = (live >> g0) & ((1u << TG) - 1u);
@@ -149,8 +148,7 @@ __global__ __launch_bounds__(64) void k_ties_hist(const SvdqParam *__restrict__ 
                 }
             }
         }
-        lds_fence();      // the basis rows are rewritten next
-    }
+    });
     // ---- one flush per unit
     lds_fence();
     for (int e = lane; e < nop * TIES_BINS; e += 64) {
@@ -247,6 +245,7 @@ __global__ __launch_bounds__(64) void k_ties_merge(const SvdqParam *__restrict__
         ustage_fetch(ureg, ustage_plan<ES>(rb, nr, k, nl), uv.gUh, uv.gUl, lane);
         load_rows(mpf, bpf, uv.gmean, uv.gbase, rb, nr, lane);
     };
+    // the block loop written out: as stream_blocks (svdq_store_pass.h) two instantiations spill more scalar registers
     prefetch(r_begin);
     for (int64_t rb = r_begin; rb < r_end; rb += RB) {
         const int rows_blk = block_rows<RB>(rb, r_end);
@@ -351,20 +350,6 @@ extern "C" int64_t svdq_ties_work_bytes(int32_t n_tasks) {
     return svdq_align_up(ties_words(n_tasks) * 8, 256);
 }
 
-struct TiesSmall {
-    const int32_t *k, *r;
-    const uint16_t *chigh;
-    const uint8_t *codes;
-    const float *scale, *zp;
-};
-static TiesSmall ties_small(const svdq_plan *pl, const void *small) {
-    const svdq_small_layout &L = pl->small;
-    const uint8_t *sm = reinterpret_cast<const uint8_t *>(small);
-    return {reinterpret_cast<const int32_t *>(sm + L.k_off),   reinterpret_cast<const int32_t *>(sm + L.r_off),
-            reinterpret_cast<const uint16_t *>(sm + L.chigh_off), sm + L.codes_off,
-            reinterpret_cast<const float *>(sm + L.scale_off), reinterpret_cast<const float *>(sm + L.zp_off)};
-}
-
 static int ties_args_ok(const char *who, const svdq_plan *pl, const void *small, const void *basis, const float *mean,
                         const int32_t *slot_task, const int32_t *task_map, int32_t n_out, int32_t n_tasks,
                         const void *state, const void *work) {
@@ -376,18 +361,14 @@ static int ties_args_ok(const char *who, const svdq_plan *pl, const void *small,
         svdq_set_error("%s: n_out and n_tasks must be in [1, %d], got %d and %d", who, SVDQ_MAX_TASKS, n_out, n_tasks);
         return SVDQ_EINVAL;
     }
-    if (pl->cfg.center && !mean) {
-        svdq_set_error("%s: mean is required on a centred plan", who);
-        return SVDQ_EINVAL;
-    }
-    return SVDQ_OK;
+    return svdq_refuse_no_mean(who, pl, mean) ? SVDQ_EINVAL : SVDQ_OK;
 }
 
 // the live tasks' coefficients, then `launch` with the compiled-in basis type, task group and rows per lane
 template <typename F>
 static int ties_stream(const char *who, const svdq_plan *pl, const void *small, const int32_t *slot_task,
                        const int32_t *task_map, int n_out, float *cbar, hipStream_t st, F &&launch) {
-    const TiesSmall sv = ties_small(pl, small);
+    const SmallView sv = small_view(pl->small, small);
     hipLaunchKernelGGL(k_ties_coeff, dim3(pl->n_params), dim3(64), 0, st, pl->n_tasks, pl->cfg.rtvq_stages, n_out,
                        slot_task, task_map, sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, cbar);
     const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
@@ -418,7 +399,7 @@ extern "C" int svdq_plan_ties_hist(const svdq_plan *pl, const int64_t *rows_dev,
     const float *mn = pl->cfg.center ? mean : nullptr;
     float *cbar = reinterpret_cast<float *>(work);
     return ties_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
-                       [&](auto f16_c, auto tg_c, auto rpl_c, const TiesSmall &sv, int nop) {
+                       [&](auto f16_c, auto tg_c, auto rpl_c, const SmallView &sv, int nop) {
                            constexpr bool F16 = f16_c;
                            constexpr int TG = tg_c, RPL = rpl_c;
                            using Plain = StreamLds<F16, RPL, false>;
@@ -471,7 +452,7 @@ extern "C" int svdq_plan_ties_merge(const svdq_plan *pl, const int64_t *rows_dev
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
     return ties_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
-                       [&](auto f16_c, auto tg_c, auto rpl_c, const TiesSmall &sv, int nop) {
+                       [&](auto f16_c, auto tg_c, auto rpl_c, const SmallView &sv, int nop) {
                            constexpr bool F16 = f16_c;
                            constexpr int TG = tg_c, RPL = rpl_c;
                            using Plain = StreamLds<F16, RPL, false>;

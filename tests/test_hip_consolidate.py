@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 U32 = 2.0 ** -24
 EPS64 = 2.0 ** -53
 SENT = 0xA5
-ROWS = [1, 3, 13, 255, 256, 257, 700, 4097]
+ROWS = [1, 3, 13, 255, 256, 257, 700, 4097, 127, 128, 129, 513]      # both block sizes' edges: RB = 256 and 128
 TASKS = [1, 3, 8, 9, 17, 32]
 KINDS = ["k0", "kr", "rlt", "rN"]      # k = 0; k = r; r < N; r = N
 UNIT_ROWS = 512

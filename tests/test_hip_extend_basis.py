@@ -35,7 +35,9 @@ SENT = 0x5A
 GUARD = 64
 UNIT_ROWS = 256
 # rows of the basis (None: a parameter whose rows are 0) and the kind of (k, r) it stores
-SHAPES = [(1, "k=r"), (13, "r<N"), (255, "k0"), (256, "k=r<N"), (257, "r<N"), (None, "k0"), (700, "r=N")]
+# with the block edges of both block sizes (256 rows up to 16 slots, 128 above): 1, RB - 1, RB, RB + 1, 2 RB + 1
+SHAPES = [(1, "k=r"), (13, "r<N"), (255, "k0"), (256, "k=r<N"), (257, "r<N"), (None, "k0"), (700, "r=N"),
+          (127, "r<N"), (128, "k=r<N"), (129, "k0"), (513, "r=N")]
 ABSENT_P = 3      # the last new task lacks this parameter
 CASES = [(n, m) for n in (8, 9, 17) for m in (1, 3, 8)]
 

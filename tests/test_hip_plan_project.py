@@ -50,7 +50,9 @@ def _kr(rows, n, which):
 
 
 # (rows of the basis, kind) of the parameters of the standard plan; rows None = a parameter whose rows are 0
-STANDARD = [(1, "k=r"), (255, "k0"), (256, "k=r"), (257, "r<N"), (None, "k0"), (1027, "r=N")]
+# the block edges of both block sizes (256 rows up to 16 slots, 128 above): 1, RB - 1, RB, RB + 1, 2 RB + 1
+STANDARD = [(1, "k=r"), (255, "k0"), (256, "k=r"), (257, "r<N"), (None, "k0"), (1027, "r=N"),
+            (127, "r<N"), (128, "k=r"), (129, "k0"), (513, "r=N")]
 
 
 class Plan:

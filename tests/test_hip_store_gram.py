@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 U32 = 2.0 ** -24
 SENT = 0xA5
-ROWS = [1, 3, 13, 63, 64, 255, 256, 257, 4095, 4096, 4097, 8193, 70001]
+ROWS = [1, 3, 13, 63, 64, 255, 256, 257, 4095, 4096, 4097, 8193, 70001, 127, 128, 129, 513]      # + RB = 128's edges, 2 RB + 1
 TASKS = [1, 3, 8, 16, 17, 32]
 KINDS = ["r1k0", "r1k1", "rNk0", "rNk1", "rNkr"]
 SPIKES = [0, 63, 64, 255, 256, 4095, 4096]
