@@ -968,6 +968,46 @@ int svdq_plan_ties_merge(const svdq_plan *plan, const int64_t *rows_dev, const v
                          float scaling, const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/,
                          void *state_dev, void *work_dev, void *stream);
 
+/* ---- the drop-and-rescale (DARE) merge of a store, and task arithmetic from a store, in ONE streaming pass over the
+ *      basis.  The reference's dispatcher lists "dare" and "task_arithmetic" beside "svd_hybrid" and implements neither
+ *      (cli.py answers "not yet implemented"; scripts/main.py keeps that answer); the definition is Yu et al. 2024
+ *      ("Language Models are Super Mario": thin every task vector by a random mask with drop rate p, rescale the
+ *      survivors by 1 / (1 - p), combine linearly), on what the store reconstructs:
+ *        inputs   T tasks in sorted-name order, store task index g = 0 .. T-1; the parameters of the store in sorted-name
+ *                 order, row_base[name] = the sum of the rows of the parameters before it, G = row_base + d (int64) the
+ *                 GLOBAL row of row d; v_t[G] = the value svdq_task_reconstruct writes for task t, bit for bit
+ *                 (RTVQQuantizer.dequantize rtvq.py:85-103 + reconstruct_from_coefficients merge.py:144-194).  A task that
+ *                 lacks a parameter contributes nothing on its rows.
+ *        draw     Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ *                 0xBB67AE85), key (seed & 0xffffffff, seed >> 32), counter (G & 0xffffffff, G >> 32, g >> 2, 0); task g
+ *                 uses output word g & 3 (one call serves four tasks of a row).  drop_threshold = min(int(drop_rate *
+ *                 2^32), 2^32 - 1), computed by the caller in double; the value is DROPPED iff word < drop_threshold.
+ *                 drop_threshold 0 drops nothing and the generator is skipped (wave-uniform): task arithmetic.
+ *        rescale  q = float32(1.0 - drop_rate) (a double subtraction, rounded once) = keep_scale; a kept value becomes
+ *                 v / q, ONE correctly rounded fp32 division; keep_scale 0 = no rescale, the kept value is v.
+ *        combine  m[G] starts at +0; for the kept tasks in ascending g: m = m + w_g * x, the product rounded, then the sum
+ *                 rounded.  Dropped and lacking tasks are skipped, not added as zeros.  w_g fp32 (weights_dev [T]).
+ *        apply    out = base + scaling * m (one product, one sum, each rounded; without base the product)
+ *      By-product: the values kept per task, uint64 kept [T] in state_dev (svdq_dare_work_bytes(T) bytes, zeroed by the
+ *      caller, shared by all plans of the store), integer atomics, one flush per work unit.  No result depends on the order
+ *      the units run in: two calls give identical bits.  Non-finite store values are outside the definition, as for TIES.
+ *   slot_task_dev, task_map_dev, n_out, n_tasks, rows_dev, small_dev, basis_dev, mean_dev, base_ptrs_dev, out_ptrs_dev:
+ *                 as for svdq_plan_ties_merge (live slots in ASCENDING store order: slot order is the order of the sums,
+ *                 and what lets a quad's Philox block be computed once).  row_base_dev int64 [P]: row_base of every
+ *                 parameter of the plan.  work_dev: svdq_task_reconstruct_work_bytes(plan, n_out) bytes.
+ *   errors        SVDQ_EINVAL before anything is launched: a NULL plan, buffer or table (row_base_dev, weights_dev and
+ *                 out_ptrs_dev included); n_out or n_tasks outside [1, SVDQ_MAX_TASKS]; a missing mean on a centred plan.
+ *   Allocates nothing, copies nothing to the host, synchronises nothing.  Works on plans filled by any compress route and
+ *   on plans filled by svdq_plan_import. */
+int64_t svdq_dare_work_bytes(int32_t n_tasks);
+int svdq_plan_dare_merge(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                         const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                         const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks,
+                         const int64_t *row_base_dev /*[P]*/, const float *weights_dev /*[T]*/, uint64_t seed,
+                         uint32_t drop_threshold, float keep_scale /*q; 0 = no rescale*/, float scaling,
+                         const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/, void *state_dev,
+                         void *work_dev, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

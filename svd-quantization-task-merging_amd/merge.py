@@ -639,24 +639,24 @@ def merge_with_clustering(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
     return merge_cluster_results(per_cluster, performance, device)
 
 
-def _ties_jobs(names, wanted, compressed_all, bases, original_shapes):
-    """The plans behind a TIES merge: {id(plan): (batch, {entry index: name})}, the rows of every parameter and, per
-    parameter, the (store task, plan task) pairs of the wanted tasks that have it, in store order.  Raises the named
-    ValueError for what the streaming route cannot serve."""
+def _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who="ties_merge_parameters", what="the TIES merge"):
+    """The plans behind a TIES (or DARE: ``who`` / ``what`` name the caller in the messages) merge: {id(plan): (batch,
+    {entry index: name})}, the rows of every parameter and, per parameter, the (store task, plan task) pairs of the
+    wanted tasks that have it, in store order.  Raises the named ValueError for what the streaming route cannot serve."""
     import math
     jobs, rows, live = {}, {}, {}
     for name in names:
         got = _batched_entry(name, compressed_all, bases)
         if got is None:
-            raise ValueError(f"ties_merge_parameters: parameter {name!r} is not backed by a plan (adoption declined it, or "
-                             "its dictionaries were edited): the TIES merge reads the values from plans only")
+            raise ValueError(f"{who}: parameter {name!r} is not backed by a plan (adoption declined it, or "
+                             f"its dictionaries were edited): {what} reads the values from plans only")
         batch, i, meta = got
         stored = int(batch.small.rows[i])
         if (getattr(batch, "mode", "plain") != "plain" or meta["noise"] is not None
                 or stored != math.prod(original_shapes[name])):
-            raise ValueError(f"ties_merge_parameters: parameter {name!r} stores {stored} rows for a tensor of "
+            raise ValueError(f"{who}: parameter {name!r} stores {stored} rows for a tensor of "
                              f"{math.prod(original_shapes[name])} elements -- a masked run's store; masks are not stored, "
-                             "and the TIES merge is defined on whole tensors")
+                             f"and {what} is defined on whole tensors")
         jobs.setdefault(id(batch.plan), (batch, {}))[1][i] = name
         rows[name] = stored
         pos = {t: q for q, t in enumerate(batch.task_names[i])}
@@ -753,6 +753,141 @@ def ties_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
             stats["thresholds"] = {t: float(tau[g]) for g, t in enumerate(wanted)}
             stats["kept"] = {t: int(host[2 * T + g]) for g, t in enumerate(wanted)}
             stats["sign_conflict_rows"], stats["empty_rows"] = int(host[3 * T]), int(host[3 * T + 1])
+        for name in names:
+            res = out[name].view(original_shapes[name])
+            if name in later:
+                res = later[name].to(res.device) + res
+            out[name] = res.cpu() if wants_cpu(device) else res
+    return (out, stats) if return_stats else out
+
+
+def _dare_arguments(drop_rate, seed):
+    """(drop threshold, q = float32(1 - drop_rate)) of a DARE merge; the named ValueError for what lies outside the
+    definition.  Host arithmetic in double: thr = min(int(drop_rate * 2^32), 2^32 - 1); dropped iff word < thr."""
+    import math
+    import numpy as np
+    if (isinstance(drop_rate, bool) or not isinstance(drop_rate, (int, float)) or not math.isfinite(drop_rate)
+            or not 0.0 <= float(drop_rate) < 1.0):
+        raise ValueError(f"drop_rate must be in [0, 1), got {drop_rate!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    thr = min(int(float(drop_rate) * 2.0 ** 32), 2 ** 32 - 1)
+    return thr, float(np.float32(1.0 - float(drop_rate)))
+
+
+def dare_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                          original_shapes: Dict[str, torch.Size], config, drop_rate: float = 0.9, seed: int = 0,
+                          rescale: bool = True, weights=None, normalize: bool = False, scaling: float = 1.0, tasks=None,
+                          base_state_dict: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda",
+                          return_stats: bool = False):
+    """The drop-and-rescale (DARE, Yu et al. 2024) merge of what a store reconstructs -- and, with ``drop_rate=0``, plain
+    task arithmetic from a store -- in one pass over the basis, without a task model ever being written (DESIGN.md
+    section 28; the contract is at svdq_plan_dare_merge in include/svdq.h).  With v_t what ``reconstruct_task_vectors``
+    returns for task t, the tasks and the parameters in sorted-name order, G the global row (the rows of the parameters
+    before it + the row inside the parameter) and g the task's index: the value is dropped iff word ``g & 3`` of
+    Philox4x32-10 with key ``seed`` and counter (G, g >> 2) is below ``min(int(drop_rate * 2^32), 2^32 - 1)``; a kept value
+    becomes ``v / float32(1 - drop_rate)`` (``rescale=False``: stays v); ``m = m + w_g * x`` over the kept tasks in
+    ascending g; the result is ``scaling * m`` per parameter, ``base + scaling * m`` for the parameters
+    ``base_state_dict`` holds.  A task that lacks a parameter contributes nothing on its rows.
+
+    ``weights``: None (1.0 for every task: task arithmetic) or {task: number} naming every merged task;
+    ``normalize=True`` divides them by their sum (on the host, in double, before rounding to fp32).  ``tasks``: the names
+    to merge (None = all).  Takes dictionaries backed by a fused run or by ``adopt_artifacts`` and refuses what
+    ``ties_merge_parameters`` refuses, under its own name.  ``drop_rate`` outside [0, 1), a ``seed`` outside [0, 2^64) or
+    a weight that is missing or not finite raises a ValueError.  Outputs are fp32.
+
+    Returns {param: tensor}; with ``return_stats`` also {"kept": {task: int}, "rows": D, "drop_threshold": thr}.  The
+    same arguments give the same bits on every call."""
+    import math
+    import numpy as np
+    who = "dare_merge_parameters"
+    thr, q = _dare_arguments(drop_rate, seed)
+    known = []
+    for per_task in compressed_all.values():
+        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
+                  if t not in known]
+    for t in (tasks if tasks is not None else []):
+        if t not in known:
+            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    wanted = sorted(set(known if tasks is None else tasks))
+    T = len(wanted)
+    if not 1 <= T <= nat.MAX_TASKS:
+        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
+    if weights is None:
+        w64 = [1.0] * T
+    else:
+        if not hasattr(weights, "get"):
+            raise ValueError(f"{who}: weights must be None or a mapping {{task: number}}, got {type(weights).__name__}")
+        w64 = []
+        for t in wanted:
+            w = weights.get(t)
+            if w is None:
+                raise ValueError(f"{who}: the weight of task {t!r} is missing")
+            if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w):
+                raise ValueError(f"{who}: the weight of task {t!r} is not a finite number: {w!r}")
+            w64.append(float(w))
+    if normalize:
+        total = math.fsum(w64)
+        if not (math.isfinite(total) and total != 0.0):
+            raise ValueError(f"{who}: normalize=True needs weights with a non-zero sum, got {total!r}")
+        w64 = [w / total for w in w64]
+    with np.errstate(over="ignore"):
+        w32 = np.asarray(w64, dtype=np.float64).astype(np.float32)
+    if not np.isfinite(w32).all():
+        raise ValueError(f"{who}: a weight is not finite in fp32: {w32.tolist()}")
+    names = sorted(compressed_all.keys())
+    jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
+                                  "the DARE merge")      # refusals before device work
+    dev = resolve_device(device)
+    D = sum(rows.values())
+    row_base, at = {}, 0
+    for name in names:
+        row_base[name] = at
+        at += rows[name]
+    out, later = {}, {}
+    stats = {"kept": {t: 0 for t in wanted}, "rows": D, "drop_threshold": thr}
+    if D == 0:
+        out = {name: torch.zeros(original_shapes[name], device=dev) for name in names}
+        return (out, stats) if return_stats else out
+    with torch.cuda.device(dev):
+        need = int(nat.lib().svdq_dare_work_bytes(T))
+        state = torch.zeros(need // 8, dtype=torch.int64, device=dev)
+        w_dev = torch.from_numpy(w32).to(dev)
+        keep = []
+        for batch, entries in jobs.values():
+            plan = batch.plan
+            P = plan.P
+            n_out = max([len(live[name]) for name in entries.values()] + [1])
+            slot_task = np.zeros((P, n_out), dtype=np.int32)
+            task_map = np.full((P, n_out), -1, dtype=np.int32)
+            out_tab = np.zeros(P, dtype=np.int64)
+            base_tab = np.zeros(P, dtype=np.int64)
+            base_rows = np.zeros(P, dtype=np.int64)
+            for i, name in entries.items():
+                for j, (g, pq) in enumerate(live[name]):
+                    task_map[i, j], slot_task[i, j] = g, pq
+                base_rows[i] = row_base[name]
+                if rows[name] <= 0:
+                    out[name] = torch.zeros(original_shapes[name], device=plan.device)
+                    continue
+                res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
+                out_tab[i] = res.data_ptr()
+                b = base_state_dict.get(name) if base_state_dict is not None else None
+                if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
+                    keep.append(prepare_vector(b, plan.device))
+                    base_tab[i] = keep[-1].data_ptr()
+                elif b is not None:
+                    later[name] = b
+            rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+            plan.dare_merge(torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device), T,
+                            torch.from_numpy(base_rows).to(plan.device), w_dev, state,
+                            torch.from_numpy(out_tab).to(plan.device), seed=seed, drop_threshold=thr,
+                            keep_scale=q if rescale else 0.0, scaling=scaling,
+                            base_table=torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None,
+                            rows_dev=rows_dev)
+        if return_stats:
+            host = state.cpu().numpy()
+            stats["kept"] = {t: int(host[g]) for g, t in enumerate(wanted)}
         for name in names:
             res = out[name].view(original_shapes[name])
             if name in later:

@@ -919,6 +919,45 @@ class CompressPlan:
                                                 int(merge_func == "sum"), float(scaling), _ptr(base_table),
                                                 _ptr(out_table), _ptr(state), _ptr(self._task_work), _stream_ptr()), who)
 
+    # ---- the drop-and-rescale (DARE) merge and task arithmetic (svdq_dare.hip)
+    def dare_merge(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, row_base: torch.Tensor,
+                   weights: torch.Tensor, state: torch.Tensor, out_table: torch.Tensor, seed: int = 0,
+                   drop_threshold: int = 0, keep_scale: float = 0.0, scaling: float = 1.0,
+                   base_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None) -> None:
+        """Draw, rescale, combine and apply for every parameter of the plan in one pass over the basis
+        (svdq_plan_dare_merge; the definition is at that name in include/svdq.h).  ``slot_task`` / ``task_map``: as for
+        ``ties_merge``; ``row_base`` int64 device tensor [P], the global row of every parameter's row 0; ``weights``
+        float32 device tensor [n_tasks]; ``state`` int64 device tensor of svdq_dare_work_bytes(n_tasks) bytes, zeroed by
+        the caller, which receives the kept counts; ``seed`` in [0, 2^64); a value is dropped iff its Philox word is below
+        ``drop_threshold`` (0 = task arithmetic); ``keep_scale`` q divides the kept values (0 = no rescale);
+        ``out_table`` / ``base_table``: as for ``ties_merge``.  Asynchronous on the current stream."""
+        who = "svdq_plan_dare_merge"
+        n_out = self._ties_tables(who, slot_task, task_map)
+        n_tasks = int(n_tasks)
+        need = int(self.lib.svdq_dare_work_bytes(n_tasks))
+        if need <= 0:
+            raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
+        if not (isinstance(row_base, torch.Tensor) and row_base.is_cuda and row_base.dtype is torch.int64
+                and row_base.is_contiguous() and row_base.numel() == self.P):
+            raise ValueError(f"{who}: row_base must be a contiguous int64 device tensor of {self.P} entries")
+        if not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.dtype is torch.float32
+                and weights.is_contiguous() and weights.numel() == n_tasks):
+            raise ValueError(f"{who}: weights must be a contiguous float32 device tensor of {n_tasks} entries")
+        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype is torch.int64
+                and state.is_contiguous() and state.numel() * 8 >= need):
+            raise ValueError(f"{who}: state must be a contiguous int64 device tensor of at least {need} bytes")
+        if out_table.numel() != self.P:
+            raise ValueError(f"{who}: out_table needs {self.P} entries, got {out_table.numel()}")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"{who}: seed must be in [0, 2^64), got {seed!r}")
+        if not 0 <= int(drop_threshold) < 1 << 32:
+            raise ValueError(f"{who}: drop_threshold must be in [0, 2^32), got {drop_threshold!r}")
+        nat.check(self.lib.svdq_plan_dare_merge(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                _ptr(self.mean), _ptr(slot_task), _ptr(task_map), n_out, n_tasks,
+                                                _ptr(row_base), _ptr(weights), int(seed), int(drop_threshold),
+                                                float(keep_scale), float(scaling), _ptr(base_table), _ptr(out_table),
+                                                _ptr(state), _ptr(self._task_work), _stream_ptr()), who)
+
     def diagnostics_masked(self, table, mask_table: torch.Tensor, unit_start: torch.Tensor, rows_dev: torch.Tensor,
                            add_mean: bool = False) -> torch.Tensor:
         """``diagnostics`` for a plan of masked regions: ``table`` names the UNMASKED task deltas, the selection

@@ -563,6 +563,41 @@ def ties_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: s
     return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
 
 
+def dare_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None, drop_rate: float = 0.9,
+                              seed: int = 0, rescale: bool = True, weights=None, normalize: bool = False,
+                              scaling: float = 1.0, tasks=None, device: str = "cuda") -> Dict[str, Any]:
+    """The drop-and-rescale (DARE) merge of a stored artifact set, task arithmetic with ``drop_rate=0``
+    (``merge.dare_merge_parameters``, which see for the definition): load_all_artifacts -> adopt_artifacts ->
+    dare_merge_parameters with the base inside the launch -> the base's other tensors cloned (as apply_merged_deltas
+    does) -> optional save.  Masks are not stored (reload.py:204-205): a masked run's store is refused with a ValueError
+    naming the parameter.  ``base_model_path``: a path or a state dict; ``tasks``: names (None = every stored task).  The
+    store's files are only read.
+
+    Returns {"merged_state_dict", "stats" (kept counts, rows, drop threshold), "diagnostics", "config"}."""
+    from .driver import adopt_artifacts
+    from .merge import _dare_arguments, dare_merge_parameters
+    _dare_arguments(drop_rate, seed)      # before any file or device work
+    art = load_all_artifacts(artifact_dir, device=device)
+    config, diagnostics = art["config"], art["diagnostics"]
+    if tasks is not None:
+        known = {t for per_task in art["compressed"].values() for t in per_task}
+        for t in tasks:
+            if t not in known:
+                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
+    base = _load_base(base_model_path, device)
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
+              if d.get("original_shape") is not None}
+    covered = {n: b for n, b in base.items() if n in compressed}
+    merged, stats = dare_merge_parameters(compressed, bases, shapes, config, drop_rate=drop_rate, seed=seed,
+                                          rescale=rescale, weights=weights, normalize=normalize, scaling=scaling,
+                                          tasks=tasks, base_state_dict=covered, device=device, return_stats=True)
+    out = {n: (merged[n] if n in merged else b.clone()) for n, b in base.items()}
+    if output_path:
+        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
+
+
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
     """Reference reload.py:60-139: a pre-saved merged_state_dict.pt in the artifact directory wins; otherwise the
     merged model is rebuilt from bases + coefficients + the base model named in the stored config."""
