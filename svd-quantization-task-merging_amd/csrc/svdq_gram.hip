@@ -4,13 +4,15 @@
 
 // ------------------------------------------------------------------------------------ pass 1
 // One work unit of pass 1 (a run of 256-row blocks of one parameter) by ONE wavefront.
-// X: NTP*XS floats of wave-private LDS.
+// X: wave-private LDS, gram_lds_floats<NTP, F64>() floats: the strip of NTP*XS floats, and at N <= 8 with exact products
+// room for a round of the end-of-unit reduction.
 // MODE bit 0: gather through an index list (aux[p] = int32 list); bit 1: the task tensors are fine-tuned weights and a
 // base tensor is subtracted in registers (aux2[p] = base).  0 = contiguous task vectors, 3 = both.
-// F64: the products are accumulated by v_mfma_f64_16x16x4_f64 (exact fp32 x fp32 products, fp64 running sums over the
-// whole unit), which resolves singular values down to ~1e-6 sigma_0 like the reference's LAPACK path; the fp32 form
-// (fp32 sums inside a 256-row block) only reaches ~1e-3..1e-4 sigma_0.  Pass 1 is HBM-bound for N <= 16, so the fp64
-// form is the default there; N > 16 would become MFMA-bound and keeps fp32 products.
+// F64: exact fp32 x fp32 products and fp64 running sums over the whole unit -- in registers with v_fma_f64 at N <= 8
+// (the register form below), on the fp64 MFMA above (v_mfma_f64_4x4x4 at N = 9..12, v_mfma_f64_16x16x4 at 13..16) --
+// which resolves singular values down to ~1e-6 sigma_0 like the reference's LAPACK path; the fp32 form (fp32 sums
+// inside a 256-row block) only reaches ~1e-3..1e-4 sigma_0.  Pass 1 is HBM-bound for N <= 16, so the fp64 form is the
+// default there; N > 16 would become MFMA-bound and keeps fp32 products.
 // TIN: element type of the task / base tensors (svdq_input.h), widened to fp32 by the loaders; float for the walk.
 // SIDE (MODE 0 / 2 only; the task-Gram by-product, svdq_plan_task_gram): beside the Gram of the centred rows Tc the
 // unit sums a[t] = sum_rows Tc[row][t] m[row] and s = sum_rows m[row]^2 (m = the row mean that was subtracted), from
@@ -19,8 +21,8 @@
 // (fixed order) and lane i keeps sum i, which it carries in fp64 across the blocks of the unit -- a handful of
 // registers, where N + 1 fp64 lane accumulators, and a reduce-scatter of all N + 1 lane values at once, cost the
 // N <= 8 and N <= 16 kernels their launch bounds (spills) and N = 20 its second wave.
-// side_part[unit][NT + 1].  The strip in LDS, the MFMA phase and the Gram partials are those of the SIDE = false
-// kernel, bit for bit.
+// side_part[unit][NT + 1].  The Gram partials are those of the SIDE = false kernel, bit for bit (above 8 tasks the strip
+// in LDS and the MFMA phase are; the register form takes the lane's rows for the side sums from its registers).
 // Sum of x over the 64 lanes, the same bits in every lane: inside a row of 16 lanes four DPP adds (lane ^ 1, lane ^ 2,
 // the mirror of the half row, the mirror of the row: both lanes of a pair add the same two numbers), across the four
 // rows two shuffles.  In place: one value at a time needs one register.
@@ -36,6 +38,37 @@ __device__ __forceinline__ float side_wave_sum(float x) {
     x += __shfl_xor(x, 16);
     x += __shfl_xor(x, 32);
     return x;
+}
+
+// Register form (N <= 8, exact products).  The lane that loads a block holds rows 4l..4l+3 of every task, and the Gram
+// is a sum of per-row outer products: per row the lane converts its NTP centred values to fp64 once and adds the
+// NTP (NTP + 1) / 2 products on or above the diagonal to fp64 accumulators of its own with v_fma_f64 (a product of two
+// fp32 values is exact in fp64, so an entry is the correctly rounded running sum of exact products, as on the fp64
+// MFMA).  32 conversions and 144 FMAs per 256-row block at N = 8, where the v_mfma_f64_4x4x4 form this replaced paid
+// 8 + 32 LDS instructions, 128 conversions (every 4x4x4 instruction wants two freshly converted operands per lane) and
+// 64 MFMAs to re-shape the same registers.  v_fma_f64 issues at the rate of v_fma_f32 on gfx950, v_cvt_f64_f32 at 0.6
+// of it (tools/probe/valu_f64_rate.hip).  Measured on ViT-L-14, pass 1 alone, MFMA form -> this: x 8 1.67 -> 1.60 ms
+// (fp32 inputs), 1.23 -> 1.02 (half); x 5 1.39 -> 1.12; x 4 0.82 -> 0.83; x 2 0.52 -> 0.47.
+// Summation order of one entry, which every mode keeps so that the routes stay bit-identical:
+//   lane l: the rows 4l + e (e = 0..3) of block 0, then of block 1, ... of the unit, one running sum;
+//   across lanes at the end of the unit, through LDS: the lanes q, PER + q, 2 PER + q, ... in turn (PER = 64 / (2 NTP)
+//   lanes share an entry), then the PER partial sums in a butterfly (lane ^ 1, ^ 2, ^ 4);
+//   the unit's first slot takes the sum, the second is zeros; k_reduce goes on from there.
+// Plain and minus-base: two register sets, the block after the one being summed is in flight; no strip in LDS.  With
+// 36 fp64 accumulators that is two waves per SIMD (about 200 VGPRs); three waves spill and run at half the speed, one
+// set at three waves leaves too little in flight (1.90 ms), a third set at two waves measured the same as two.
+// Gather and walk: the strip stays as a transposer -- rows are scattered into it as before and every lane reads rows
+// 4l..4l+3 of each task back (NTP ds_read_b128), so a compacted row sits in the lane and the position of the sum where
+// the plain kernel has it.
+template <int NTP, bool F64>
+__host__ __device__ constexpr bool gram_registers() {
+    return F64 && NTP <= 8;
+}
+// LDS floats of k_gram: the strip, or the 2 NTP entries x (64 + PER) lane values (fp64) of one reduction round
+template <int NTP, bool F64>
+__host__ __device__ constexpr int gram_lds_floats() {
+    constexpr int strip = NTP * XS, round = 2 * (2 * NTP) * (64 + 64 / (2 * NTP));
+    return (gram_registers<NTP, F64>() && round > strip) ? round : strip;
 }
 
 template <int NTP, int MODE = 0, bool F64 = false, bool FULL = false, typename TIN = float, bool SIDE = false>
@@ -65,24 +98,22 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
     // 2 688 matrix-pipe cycles per 256-row block instead of 4 096 plus the vector-ALU corner.
     constexpr bool VBB = (NTP == 20) && !F64;
     constexpr int NACC = (NB == 1 || VBB) ? 1 : 3;  // AA | AA, AB, BB
-    // N = 5..8 with exact products: the 8 x 8 Gram is four 4 x 4 tiles, which is exactly one v_mfma_f64_4x4x4_4b_f64
-    // (four blocks, K = 4 rows, 16 cycles) -- the 16x16x4 form spends 64 cycles on two useful 8 x 8 corners of a 16 x 16
-    // tile.  Layout probed on the device (tools/probe/mfma_f64_layout.hip): lane l = (k = l >> 4, b = (l >> 2) & 3,
-    // x = l & 3) supplies A_b[x][k] and B_b[k][x] and holds D_b[i = l >> 4][j = l & 3]; block b = tile (b >> 1, b & 1).
-    // The lane's k selects rows 4k..4k+3 of a 16-row sub-tile (one 16-byte LDS read per operand), the four
-    // instructions of a sub-tile take one of them each.  1 024 instead of 2 048 matrix-pipe cycles per block.
-    // The same instruction serves every N <= 16 (T = NTP / 4 tile rows): only the T (T + 1) / 2 tiles on or above the
-    // diagonal are computed, four per instruction -- T = 1: the four blocks take four different 16-row groups of the
-    // one tile (summed at the end); T = 2: all four tiles in one instruction; T = 3: six tiles in two instructions;
-    // (T = 4: ten tiles in three, was measured SLOWER than the 16x16x4 form -- 4.62 against 3.58 ms at ViT-L-14 x 16:
-    // every 4x4x4 instruction needs two converted operands per lane, eight times the v_cvt_f64_f32 work per output --
-    // so N = 13..16 stays on 16x16x4.)  Matrix-pipe cycles per four rows: 4 / 16 / 32 against 64 for the 16x16x4 form,
-    // which at N <= 4 made pass 1 matrix-bound (1.52 -> 0.52 ms for the 2.4 GB of ViT-L-14 x 2; N = 4: 1.58 -> 0.83;
-    // N = 12: 3.21 -> 2.98).
-    constexpr bool Q64 = F64 && (NTP <= 12);
+    // N = 9..12 with exact products: v_mfma_f64_4x4x4_4b_f64 (four independent 4 x 4 blocks, K = 4 rows, 16 cycles)
+    // over the six 4 x 4 tiles on or above the diagonal, four per instruction, so two instructions per four rows: 32
+    // matrix-pipe cycles against 64 for the 16x16x4 form (3.21 -> 2.98 ms at N = 12).  Layout probed on the device
+    // (tools/probe/mfma_f64_layout.hip): lane l = (k = l >> 4, b = (l >> 2) & 3, x = l & 3) supplies A_b[x][k] and
+    // B_b[k][x] and holds D_b[i = l >> 4][j = l & 3].  The lane's k selects rows 4k..4k+3 of a 16-row sub-tile (one
+    // 16-byte LDS read per operand), the four instructions of a sub-tile take one of them each.  (Ten tiles in three
+    // instructions at N = 13..16 were measured SLOWER than the 16x16x4 form -- 4.62 against 3.58 ms at ViT-L-14 x 16:
+    // every 4x4x4 instruction needs two converted operands per lane, eight times the v_cvt_f64_f32 work per output.
+    // N <= 8 ran on this instruction too, one or four tiles, until the register form took it over.)
+    constexpr bool Q64 = F64 && NTP > 8 && NTP <= 12;
     constexpr int TQ = NTP / 4;
     constexpr int NTILE = TQ * (TQ + 1) / 2;
-    constexpr int NSET = (TQ == 2) ? 1 : (NTILE + 3) / 4;   // T = 2 keeps its redundant (1,0) tile: one instruction anyway
+    constexpr int NSET = (NTILE + 3) / 4;
+    // N <= 8 with exact products: no matrix pipe at all (REG, "register form" in the notes above gram_unit).
+    constexpr bool REG = gram_registers<NTP, F64>();
+    constexpr int NRACC = NTP * (NTP + 1) / 2;
 
     const int lane = threadIdx.x & 63;
     const SvdqUnit ud = units[uidx];
@@ -139,6 +170,46 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
         for (int e = 0; e < 4; ++e) qd[i][e] = 0.0;
     const int b4 = lane >> 2, i4 = lane & 3, mg4 = b4 & 3, rg4 = b4 >> 2;
     double side = 0.0;   // SIDE: lane t < NT: a[t], lane NTP: s, over the whole unit
+    double racc[REG ? NRACC : 1];   // REG: entries (i <= j) of this lane's rows in row-major order, over the whole unit
+#pragma unroll
+    for (int i = 0; i < (REG ? NRACC : 1); ++i) racc[i] = 0.0;
+    // REG: the lane's four rows of a block (centred, zero in padded tasks and past the end), row after row
+    auto accumulate = [&](const f32x4 (&xc)[NTP]) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            double d[NTP];
+#pragma unroll
+            for (int t = 0; t < NTP; ++t) d[t] = (double)xc[t][e];
+            int q = 0;
+#pragma unroll
+            for (int i = 0; i < NTP; ++i)
+#pragma unroll
+                for (int j = i; j < NTP; ++j, ++q) racc[REG ? q : 0] = __builtin_fma(d[i], d[j], racc[REG ? q : 0]);
+            __builtin_amdgcn_sched_barrier(0);   // one converted row at a time: converting ahead costs registers, not time
+        }
+    };
+    // SIDE: a[t] and s of one block from the lane's centred rows xc(t) and the mean that was subtracted
+    auto side_block = [&](const f32x4 &mean, auto xc) {
+        float s = mean.x * mean.x;
+        s = __builtin_fmaf(mean.y, mean.y, s);
+        s = __builtin_fmaf(mean.z, mean.z, s);
+        s = __builtin_fmaf(mean.w, mean.w, s);
+        s = side_wave_sum(s);
+        float mine = (lane == NTP) ? s : 0.f;
+#pragma unroll
+        for (int t = 0; t < NTP; ++t) {
+            if (t < NT) {
+                const f32x4 x = xc(t);
+                float a = x.x * mean.x;
+                a = __builtin_fmaf(x.y, mean.y, a);
+                a = __builtin_fmaf(x.z, mean.z, a);
+                a = __builtin_fmaf(x.w, mean.w, a);
+                a = side_wave_sum(a);
+                mine = (lane == t) ? a : mine;
+            }
+        }
+        side += (double)mine;
+    };
 
     // The loads of the next block (or next two, SVDQ_PREFETCH2) are in flight while a block is computed.
     constexpr int AHEAD = SVDQ_PREFETCH2 ? 2 : 1;
@@ -171,6 +242,14 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
 
     // the MFMA phase over the strip of one block (ends with the barrier that frees the strip)
     auto compute = [&]() {
+        if constexpr (REG) {   // gather / walk: the strip only transposes, every lane takes rows 4l..4l+3 back
+            f32x4 xr[NTP];
+#pragma unroll
+            for (int t = 0; t < NTP; ++t) xr[t] = *reinterpret_cast<const f32x4 *>(X + t * XS + 4 * lane);
+            accumulate(xr);
+            wave_sync();
+            return;
+        }
         f32x4 acc[NACC];
 #pragma unroll
         for (int i = 0; i < NACC; ++i) acc[i] = zero4();
@@ -178,49 +257,27 @@ __device__ __forceinline__ void gram_unit(float *X, int uidx, const SvdqParam *_
 
         if constexpr (Q64) {
             const int kq = lane >> 4, bq = (lane >> 2) & 3, xq = lane & 3;
-            if constexpr (TQ == 1) {
-                // one tile: block b takes rows 16b..16b+15 of every 64-row group; A and B are the same value
-                const float *pa = X + xq * XS + 16 * bq + 4 * kq;
-UNROLL_N(4)
-                for (int j = 0; j < 4; ++j) {
-                    const f32x4 a = *reinterpret_cast<const f32x4 *>(pa + 64 * j);
+            const float *pa[NSET], *pb[NSET];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const double ad = (double)a[e];
-                        if (SVDQ_Q64_CHAINS == 2 && (e & 1))
-                            q64b[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad, ad, q64b[0], 0, 0, 0);
-                        else
-                            q64[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(ad, ad, q64[0], 0, 0, 0);
-                    }
-                }
-            } else {
-                const float *pa[NSET], *pb[NSET];
+            for (int st = 0; st < NSET; ++st) {
+                int ti, tj;
+                const int q = 4 * st + bq;
+                tile_of(q < NTILE ? q : NTILE - 1, ti, tj);   // spare blocks repeat the last tile, unused
+                pa[st] = X + (4 * ti + xq) * XS + 4 * kq;
+                pb[st] = X + (4 * tj + xq) * XS + 4 * kq;
+            }
+UNROLL_N(SVDQ_UNROLL_GRAM)
+            for (int j = 0; j < 16; ++j) {
 #pragma unroll
                 for (int st = 0; st < NSET; ++st) {
-                    int ti, tj;
-                    if constexpr (TQ == 2) {
-                        ti = bq >> 1;
-                        tj = bq & 1;
-                    } else {
-                        const int q = 4 * st + bq;
-                        tile_of(q < NTILE ? q : NTILE - 1, ti, tj);   // spare blocks repeat the last tile, unused
-                    }
-                    pa[st] = X + (4 * ti + xq) * XS + 4 * kq;
-                    pb[st] = X + (4 * tj + xq) * XS + 4 * kq;
-                }
-UNROLL_N(SVDQ_UNROLL_GRAM)
-                for (int j = 0; j < 16; ++j) {
+                    const f32x4 a = *reinterpret_cast<const f32x4 *>(pa[st] + 16 * j);
+                    const f32x4 b = *reinterpret_cast<const f32x4 *>(pb[st] + 16 * j);
 #pragma unroll
-                    for (int st = 0; st < NSET; ++st) {
-                        const f32x4 a = *reinterpret_cast<const f32x4 *>(pa[st] + 16 * j);
-                        const f32x4 b = *reinterpret_cast<const f32x4 *>(pb[st] + 16 * j);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            if (SVDQ_Q64_CHAINS == 2 && (e & 1))
-                                q64b[st] = __builtin_amdgcn_mfma_f64_4x4x4f64((double)a[e], (double)b[e], q64b[st], 0, 0, 0);
-                            else
-                                q64[st] = __builtin_amdgcn_mfma_f64_4x4x4f64((double)a[e], (double)b[e], q64[st], 0, 0, 0);
-                        }
+                    for (int e = 0; e < 4; ++e) {
+                        if (SVDQ_Q64_CHAINS == 2 && (e & 1))
+                            q64b[st] = __builtin_amdgcn_mfma_f64_4x4x4f64((double)a[e], (double)b[e], q64b[st], 0, 0, 0);
+                        else
+                            q64[st] = __builtin_amdgcn_mfma_f64_4x4x4f64((double)a[e], (double)b[e], q64[st], 0, 0, 0);
                     }
                 }
             }
@@ -232,16 +289,8 @@ UNROLL_N(SVDQ_UNROLL_GRAM)
             for (int j = 0; j < 8; ++j) {
                 f32x4 a = *reinterpret_cast<const f32x4 *>(xr + 32 * j);
                 if (!valid) a = zero4();
-                if constexpr (F64) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const double ad = (double)a[e];
-                        accq[e % QC] = mfma4d(ad, ad, accq[e % QC]);
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[0] = mfma4(a[e], a[e], acc[0]);
-                }
+                for (int e = 0; e < 4; ++e) acc[0] = mfma4(a[e], a[e], acc[0]);   // fp32 products only: F64 is REG here
             }
         } else {
             const bool v0ok = c < NTP;
@@ -357,6 +406,40 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
             if (have) walk_load<NTP, SUB>(v0, vb, mk, bp, gbase, gmask, src, src_end, lane);
             more = have || fill > 0;
         }
+    } else if constexpr (REG && !GATHER) {
+        // straight from the load registers; two sets, so that the next block is in flight while one is summed
+        f32x4 v1[NTP];
+        f32x4 vb1 = zero4();
+        auto take = [&](f32x4 (&v)[NTP], const f32x4 &b) {
+            if constexpr (SUB) {
+#pragma unroll
+                for (int t = 0; t < NTP; ++t) v[t] = v[t] - b;
+            }
+            const f32x4 mean = row_mean<NTP>(v, NT, center);
+#pragma unroll
+            for (int t = 0; t < NTP; ++t) v[t] = (t < NT) ? (v[t] - mean) : zero4();
+            if constexpr (SIDE) side_block(mean, [&](int t) { return v[t]; });
+            accumulate(v);
+        };
+        // the loads of a set are issued where they stand, after the last use of the set they refill: hoisted into the
+        // sums before them they would need a third set of registers
+        auto refill = [&](f32x4 (&v)[NTP], f32x4 &b, int64_t rb) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (rb < r_end) {
+                load_block<NTP, TIN>(v, bp, rb, D, lane);
+                if constexpr (SUB) b = load_base<TIN>(gbase, rb, D, lane);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // set 0 holds the even blocks of the unit, set 1 the odd ones: summed, then refilled at once two blocks on
+        refill(v1, vb1, r_begin + SVDQ_BLK_ROWS);
+#pragma nounroll
+        for (int64_t rb = r_begin; rb < r_end; rb += 2 * SVDQ_BLK_ROWS) {
+            take(v0, vb);
+            refill(v0, vb, rb + 2 * SVDQ_BLK_ROWS);
+            if (rb + SVDQ_BLK_ROWS < r_end) take(v1, vb1);
+            refill(v1, vb1, rb + 3 * SVDQ_BLK_ROWS);
+        }
     } else {
         auto do_block = [&](f32x4 (&v)[NTP], int64_t rb) {
             if constexpr (SUB) {
@@ -376,25 +459,7 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
                 }
             }
             if constexpr (SIDE) {   // the lane's own four rows of every task, back from the strip (v is being refilled)
-                float s = mean.x * mean.x;
-                s = __builtin_fmaf(mean.y, mean.y, s);
-                s = __builtin_fmaf(mean.z, mean.z, s);
-                s = __builtin_fmaf(mean.w, mean.w, s);
-                s = side_wave_sum(s);
-                float mine = (lane == NTP) ? s : 0.f;
-#pragma unroll
-                for (int t = 0; t < NTP; ++t) {
-                    if (t < NT) {
-                        const f32x4 xc = *reinterpret_cast<const f32x4 *>(X + t * XS + 4 * lane);
-                        float a = xc.x * mean.x;
-                        a = __builtin_fmaf(xc.y, mean.y, a);
-                        a = __builtin_fmaf(xc.z, mean.z, a);
-                        a = __builtin_fmaf(xc.w, mean.w, a);
-                        a = side_wave_sum(a);
-                        mine = (lane == t) ? a : mine;
-                    }
-                }
-                side += (double)mine;
+                side_block(mean, [&](int t) { return *reinterpret_cast<const f32x4 *>(X + t * XS + 4 * lane); });
             }
             compute();
         };
@@ -423,39 +488,60 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
 
     // One fp64 partial per slot, dense [NT][NT].  Lane (c,g) holds D[4g+e][c] (fp32 MFMA) or D[g+4e][c] (fp64 MFMA).
     const int NN = NT * NT;
+    if constexpr (REG) {
+        // The 64 lane sums of an entry meet in LDS, R entries a round: lane (v, q) = (lane / PER, lane % PER) adds the
+        // values of lanes q, PER + q, ... of entry v in turn, the PER partial sums meet in a butterfly.  Rows of
+        // 64 + PER doubles: the lanes of one read touch different banks.
+        constexpr int R = 2 * NTP, PER = 64 / R, S = 64 + PER;
+        static_assert(2 * R * S <= gram_lds_floats<NTP, F64>(), "a reduction round must fit the kernel's LDS");
+        double *red = reinterpret_cast<double *>(X);
+        const int rv = lane / PER, rq = lane % PER;
+        double *dst = gram_part + (size_t)uidx * PACK * NN;
+#pragma unroll
+        for (int r0 = 0; r0 < NRACC; r0 += R) {
+            wave_sync();
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if (r0 + i < NRACC) red[i * S + lane] = racc[r0 + i];
+            wave_sync();
+            double x = red[rv * S + rq];
+#pragma unroll
+            for (int k = 1; k < R; ++k) x += red[rv * S + k * PER + rq];
+#pragma unroll
+            for (int off = 1; off < PER; off <<= 1) x += __shfl_xor(x, off);
+            int ei = 0, ej = r0 + rv, rowlen = NTP;   // entry number -> (ei <= ej), row-major over the upper triangle
+            while (ej >= rowlen && rowlen > 0) {
+                ej -= rowlen;
+                --rowlen;
+                ++ei;
+            }
+            ej += ei;
+            if (rq == 0 && r0 + rv < NRACC && ej < NT) {   // ei <= ej
+                dst[ei * NT + ej] = x;
+                dst[ej * NT + ei] = x;
+                dst[NN + ei * NT + ej] = 0.0;
+                dst[NN + ej * NT + ei] = 0.0;
+            }
+        }
+        return;
+    }
     if constexpr (Q64 && SVDQ_Q64_CHAINS == 2) {
 #pragma unroll
         for (int st = 0; st < NSET; ++st) q64[st] += q64b[st];
     }
-    if constexpr (Q64) {   // everything in the unit's first slot; N <= 8 has a second slot per unit: zeros
+    if constexpr (Q64) {
         const int i = lane >> 4, bq = (lane >> 2) & 3, jq = lane & 3;
         double *dst = gram_part + (size_t)uidx * PACK * NN;
-        if constexpr (TQ == 1) {
-            double x = q64[0];
-            x += __shfl_xor(x, 4);
-            x += __shfl_xor(x, 8);
-            if (bq == 0 && i < NT && jq < NT) {
-                dst[i * NT + jq] = x;
-                dst[NN + i * NT + jq] = 0.0;
-            }
-        } else if constexpr (TQ == 2) {
-            const int m = 4 * (bq >> 1) + i, n = 4 * (bq & 1) + jq;
-            if (m < NT && n < NT) {
-                dst[m * NT + n] = q64[0];
-                dst[NN + m * NT + n] = 0.0;
-            }
-        } else {
 #pragma unroll
-            for (int st = 0; st < NSET; ++st) {
-                const int q = 4 * st + bq;
-                if (q < NTILE) {
-                    int ti, tj;
-                    tile_of(q, ti, tj);
-                    const int m = 4 * ti + i, n = 4 * tj + jq;
-                    if (m < NT && n < NT) {
-                        dst[m * NT + n] = q64[st];
-                        if (ti != tj) dst[n * NT + m] = q64[st];
-                    }
+        for (int st = 0; st < NSET; ++st) {
+            const int q = 4 * st + bq;
+            if (q < NTILE) {
+                int ti, tj;
+                tile_of(q, ti, tj);
+                const int m = 4 * ti + i, n = 4 * tj + jq;
+                if (m < NT && n < NT) {
+                    dst[m * NT + n] = q64[st];
+                    if (ti != tj) dst[n * NT + m] = q64[st];
                 }
             }
         }
@@ -504,16 +590,24 @@ UNROLL_N(SVDQ_UNROLL_GRAM_P1)
 }
 
 // second launch bound = waves per SIMD the register allocation must leave room for: the fp64 accumulators would
-// otherwise cost the N <= 8 and the N <= 16 kernels one resident wave each (measured: -9 % bandwidth)
-#ifndef SVDQ_GRAM64_WAVES8
-#define SVDQ_GRAM64_WAVES8 5
-#endif
+// otherwise cost the N <= 16 kernels one resident wave (measured: -9 % bandwidth)
 #ifndef SVDQ_GRAM64_WAVES16
 #define SVDQ_GRAM64_WAVES16 3
 #endif
+// the register form: 36 fp64 accumulators, one converted row and two sets of load registers need two waves' share of
+// the register file at N = 5..8 (see the notes above gram_registers); the 10 accumulators of N <= 4 leave room for 4-5
+#ifndef SVDQ_GRAM_REG_WAVES
+#define SVDQ_GRAM_REG_WAVES 2
+#endif
+template <int NTP, int MODE, bool F64>
+__host__ __device__ constexpr int gram_waves() {
+    if (gram_registers<NTP, F64>()) return SVDQ_GRAM_REG_WAVES;
+    if (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) return SVDQ_GRAM64_WAVES16;
+    return 1;
+}
 SVDQ_STAMP_DECL(svdq_stamps_gram)
 template <int NTP, int MODE, bool F64, bool FULL, typename TIN>
-__global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) ? (NTP <= 8 ? SVDQ_GRAM64_WAVES8 : SVDQ_GRAM64_WAVES16) : 1) void k_gram(const SvdqParam *__restrict__ params,
+__global__ __launch_bounds__(64, (gram_waves<NTP, MODE, F64>())) void k_gram(const SvdqParam *__restrict__ params,
                                              const SvdqUnit *__restrict__ units,
                                              const float *const *__restrict__ ptrs,
                                              const int64_t *__restrict__ rows_dev, int NT, int center,
@@ -522,7 +616,7 @@ __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) 
                                              const int32_t *__restrict__ only,
                                              const void *const *__restrict__ aux2, int order,
                                              const int64_t *__restrict__ ustart) {
-    __shared__ __attribute__((aligned(16))) float X[NTP * XS];
+    __shared__ __attribute__((aligned(16))) float X[gram_lds_floats<NTP, F64>()];
     SVDQ_STAMP_BEGIN();
     const int uidx = unit0 + unit_of_block((int)blockIdx.x, (int)gridDim.x, order);
     gram_unit<NTP, MODE, F64, FULL, TIN>(X, uidx, params, units, ptrs, rows_dev, NT, center, gram_part, aux, only, aux2, ustart);
@@ -532,14 +626,14 @@ __global__ __launch_bounds__(64, (F64 && (MODE == 0 || MODE == 4) && NTP <= 16) 
 // k_gram with the side sums of the task-Gram by-product (gram_unit, SIDE).  A kernel of its own, so that k_gram's
 // instantiations stay what they were; same launch bounds.
 template <int NTP, int MODE, bool F64, bool FULL, typename TIN>
-__global__ __launch_bounds__(64, (F64 && MODE == 0 && NTP <= 16) ? (NTP <= 8 ? SVDQ_GRAM64_WAVES8 : SVDQ_GRAM64_WAVES16) : 1) void k_gram_side(const SvdqParam *__restrict__ params,
+__global__ __launch_bounds__(64, (gram_waves<NTP, MODE, F64>())) void k_gram_side(const SvdqParam *__restrict__ params,
                                              const SvdqUnit *__restrict__ units,
                                              const float *const *__restrict__ ptrs,
                                              const int64_t *__restrict__ rows_dev, int NT, int center,
                                              double *__restrict__ gram_part, int unit0,
                                              const void *const *__restrict__ aux2, int order,
                                              double *__restrict__ side_part) {
-    __shared__ __attribute__((aligned(16))) float X[NTP * XS];
+    __shared__ __attribute__((aligned(16))) float X[gram_lds_floats<NTP, F64>()];
     const int uidx = unit0 + unit_of_block((int)blockIdx.x, (int)gridDim.x, order);
     gram_unit<NTP, MODE, F64, FULL, TIN, true>(X, uidx, params, units, ptrs, rows_dev, NT, center, gram_part, nullptr,
                                                 nullptr, aux2, nullptr, side_part);

@@ -25,6 +25,8 @@
 //   for the next 16 rows; the two diagonal 8x8 blocks of D are two independent partial sums.
 //
 // Accumulation: fp32 inside a block (64 MFMA k-steps), fp64 across blocks and units.
+// Pass 1 with exact products at N <= 8 takes neither the strip nor the MFMA: the lane that loaded rows 4l..4l+3 sums
+// their outer products in fp64 registers (svdq_gram.hip, "register form").
 
 #pragma once
 // SVDQ_UNIT_STAMPS (diagnostic builds only, tools/unit_timeline.py): every work unit of the two streaming passes records
