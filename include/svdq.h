@@ -1008,6 +1008,55 @@ int svdq_plan_dare_merge(const svdq_plan *plan, const int64_t *rows_dev, const v
                          const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/, void *state_dev,
                          void *work_dev, void *stream);
 
+/* ---- TALL masks and the consensus merge of a store (Wang et al. 2024: "Localizing Task Information for Improved Model
+ *      Merging and Compression") in ONE streaming pass over the basis.  The package reads TALL_mask_{n}task files
+ *      (load_tall_mask_file, combine_tall_masks_packed, --mask-dir) that were made from the fine-tuned checkpoints; this
+ *      entry point makes them from what the store reconstructs, and merges by the consensus of the masks:
+ *        inputs   T tasks in sorted-name order, store task index g = 0 .. T-1 (the index among the MERGED tasks where a
+ *                 subset is merged); v_t[d] = the value svdq_task_reconstruct writes for task t at row d of a parameter,
+ *                 bit for bit.  A task that lacks a parameter contributes nothing on its rows and its mask bits there
+ *                 are 0.  lambda_g fp32, finite and >= 0 (lambdas_dev [T]); min_agree = k, an integer in [0, T].
+ *        sum      S starts at +0; for the tasks that have the parameter, in ascending g: S = S + v_g, every sum rounded
+ *                 in fp32.
+ *        mask     R_g = S - v_g (one fp32 subtraction); m_g = |v_g| > lambda_g * |R_g|, the product rounded once, the
+ *                 comparison STRICT.  The paper writes ">="; the comparison here is ">" by decision (to the best of our
+ *                 knowledge what the authors' published code does -- not verified here), and strict makes a row where
+ *                 every value is zero inactive.  Consequences: lambda_g = 0 marks every non-zero value; with T = 1 the
+ *                 mask is v != 0.
+ *        consensus  c = the number of set masks at the row; the row is kept iff c >= min_agree, so min_agree = 0 keeps
+ *                 everything (plain task arithmetic); m = kept ? S : +0.
+ *        apply    out = base + scaling * m (one product, one sum, each rounded; without base the product)
+ *        streams  one per store task (mask_ptrs_dev [T]), in numpy.packbits order: stream bit i is bit 7 - (i & 7) of
+ *                 byte i >> 3.  Row d of parameter p is stream bit bit_base[p] + d; bit_base_dev int64 [P] is the
+ *                 caller's table of arbitrary non-negative bit offsets.  A stream is written in 32-bit words: it starts
+ *                 on a 4-byte boundary and spans every word its bits touch (4 * ceil(bits / 32) bytes).  The caller
+ *                 zeroes the streams before the first plan of the store; bits of rows the store does not cover stay 0.
+ *                 Words wholly inside a block's bit range are stored, the partial first and last word of the range are
+ *                 OR'ed in atomically: parameters, plans and work units may share words, in any order.
+ *      By-products, uint64 words in state_dev (svdq_tall_work_bytes(T) bytes, zeroed by the caller, shared by all plans
+ *      of the store): active [T] set bits per task | agree [T + 1] rows with c = 0 .. T.  Integer atomics, one flush per
+ *      work unit.  No result depends on the order the units run in: two calls give identical bits.  Non-finite store
+ *      values are outside the definition, as for TIES and DARE.
+ *   out_ptrs_dev  NULL (masks only) or [P]; a NULL entry skips that parameter's output, never its mask bits or counts.
+ *   mask_ptrs_dev NULL (merge only) or [T].
+ *   slot_task_dev, task_map_dev, n_out, n_tasks, rows_dev, small_dev, basis_dev, mean_dev, base_ptrs_dev: as for
+ *                 svdq_plan_ties_merge (live slots in ASCENDING store order: slot order is the order of the sum).
+ *                 work_dev: svdq_task_reconstruct_work_bytes(plan, n_out) bytes.
+ *   errors        SVDQ_EINVAL before anything is launched: a NULL plan, buffer or table (bit_base_dev and lambdas_dev
+ *                 included); out_ptrs_dev and mask_ptrs_dev both NULL; n_out or n_tasks outside [1, SVDQ_MAX_TASKS];
+ *                 min_agree outside [0, n_tasks]; a missing mean on a centred plan.
+ *   Allocates nothing, copies nothing to the host, synchronises nothing.  Works on plans filled by any compress route and
+ *   on plans filled by svdq_plan_import. */
+int64_t svdq_tall_work_bytes(int32_t n_tasks);
+int svdq_plan_tall_consensus(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                             const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                             const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks,
+                             const int64_t *bit_base_dev /*[P]*/, const float *lambdas_dev /*[T]*/, int32_t min_agree,
+                             float scaling, const void *base_ptrs_dev /*NULL or [P]*/,
+                             const void *out_ptrs_dev /*NULL or [P]*/,
+                             const void *mask_ptrs_dev /*NULL or [T] uint32-aligned streams*/, void *state_dev,
+                             void *work_dev, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

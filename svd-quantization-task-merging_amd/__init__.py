@@ -23,7 +23,8 @@ from .mask_loader import (combine_masks, compute_union_mask, compute_intersectio
                           combine_tall_masks_packed)
 from .merge import (dequantize_and_average, reconstruct_from_coefficients, merge_parameter, merge_all_parameters,
                     apply_merged_deltas, merge_with_clustering, reconstruct_task_vectors,
-                    reconstruct_task_vectors_masked, ties_merge_parameters, dare_merge_parameters)
+                    reconstruct_task_vectors_masked, ties_merge_parameters, dare_merge_parameters,
+                    consensus_merge_parameters, tall_masks_from_store)
 from .weighting import (load_performance_metrics, compute_uniform_weights, compute_performance_weights,
                         compute_cluster_weights, compute_weights, apply_weights_to_tensors, get_weight_statistics)
 from .clustering import (cluster_tasks, task_gram, cluster_from_gram, cluster_statistics_from_gram, flatten_task_vectors,
@@ -38,7 +39,8 @@ from .storage import (save_basis, load_basis, save_compressed_coefficients, load
                       load_all_artifacts, save_merged_model, reconstruct_from_artifacts,
                       reload_merged_model_from_artifacts, reconstruct_tasks_from_artifacts,
                       reconstruct_tasks_from_artifacts_masked, add_tasks_to_artifacts, remerge_from_artifacts,
-                      consolidate_artifacts, ties_merge_from_artifacts, dare_merge_from_artifacts)
+                      consolidate_artifacts, ties_merge_from_artifacts, dare_merge_from_artifacts,
+                      consensus_merge_from_artifacts)
 from .task_vector_loader import (load_checkpoint, compute_task_vector, compute_task_vectors, load_task_vectors,
                                  get_parameter_names, organize_by_parameter, flatten_task_deltas,
                                  get_task_checkpoint_paths)

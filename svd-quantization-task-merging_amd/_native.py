@@ -180,6 +180,10 @@ SIGNATURES = {
     "svdq_plan_dare_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                        c_int32, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_float, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "svdq_tall_work_bytes": (c_int64, [c_int32]),
+    "svdq_plan_tall_consensus": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
     "svdq_mask_expand": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "svdq_hbm_probe": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
 }

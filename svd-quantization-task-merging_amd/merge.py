@@ -894,3 +894,183 @@ def dare_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
                 res = later[name].to(res.device) + res
             out[name] = res.cpu() if wants_cpu(device) else res
     return (out, stats) if return_stats else out
+
+
+def _tall_arguments(who, tall_lambda, k, wanted, check_k=True):
+    """(float32 lambdas [T] in the order of ``wanted``, k) of a TALL / consensus call; the named ValueError for what lies
+    outside the definition: a lambda that is no finite number >= 0 (in fp32), a mapping that misses a merged task, a k
+    that is no integer in [0, T] (``check_k=False``: masks only, k is not looked at)."""
+    import math
+    import numpy as np
+    T = len(wanted)
+
+    def number(x, what):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0:
+            raise ValueError(f"{who}: {what} must be a finite number >= 0, got {x!r}")
+        return float(x)
+    if hasattr(tall_lambda, "get"):
+        lam = []
+        for t in wanted:
+            if tall_lambda.get(t) is None:
+                raise ValueError(f"{who}: the tall_lambda of task {t!r} is missing")
+            lam.append(number(tall_lambda.get(t), f"the tall_lambda of task {t!r}"))
+    else:
+        lam = [number(tall_lambda, "tall_lambda")] * T
+    with np.errstate(over="ignore"):
+        lam32 = np.asarray(lam, dtype=np.float64).astype(np.float32)
+    if not np.isfinite(lam32).all():
+        raise ValueError(f"{who}: a tall_lambda is not finite in fp32: {lam32.tolist()}")
+    if check_k and (isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= T):
+        raise ValueError(f"{who}: k must be an integer in [0, {T}] (the merged tasks), got {k!r}")
+    return lam32, k
+
+
+def _tall_run(who, compressed_all, bases, original_shapes, tall_lambda, k, scaling, tasks, base_state_dict,
+              reference_state_dict, remove_keys, want_merge, want_masks, device):
+    """The launches behind ``consensus_merge_parameters`` and ``tall_masks_from_store``: (merged or None, masks or None,
+    stats).  Every refusal is raised before device work."""
+    import numpy as np
+    known = []
+    for per_task in compressed_all.values():
+        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
+                  if t not in known]
+    for t in (tasks if tasks is not None else []):
+        if t not in known:
+            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    wanted = sorted(set(known if tasks is None else tasks))
+    T = len(wanted)
+    if not 1 <= T <= nat.MAX_TASKS:
+        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
+    lam32, k = _tall_arguments(who, tall_lambda, k, wanted, check_k=want_merge)
+    names = sorted(compressed_all.keys())
+    jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
+                                  "the consensus merge" if want_merge else "the TALL mask")      # before device work
+    # the streams' layout: the sorted keys of the reference minus remove_keys, each at the bit after the one before it
+    bit_base, total_bits = {}, 0
+    if want_masks:
+        skip = set(remove_keys or [])
+        if reference_state_dict is None:
+            sizes = {n: rows[n] for n in names if n not in skip}
+        else:
+            sizes = {key: int(x.numel()) for key, x in reference_state_dict.items() if key not in skip}
+        for name in names:
+            if name not in sizes:
+                raise ValueError(f"{who}: parameter {name!r} of the store has no place in the mask streams (it is not a "
+                                 f"key of reference_state_dict, or remove_keys names it)")
+            if sizes[name] != rows[name]:
+                raise ValueError(f"{who}: reference_state_dict[{name!r}] has {sizes[name]} elements, the store holds "
+                                 f"{rows[name]} rows for it")
+        for key in sorted(sizes):
+            bit_base[key] = total_bits
+            total_bits += sizes[key]
+    dev = resolve_device(device)
+    D = sum(rows.values())
+    out, later = ({}, {}) if want_merge else (None, {})
+    stats = {"active": {t: 0 for t in wanted}, "agreement": [D] + [0] * T, "rows": D}
+    n_bytes, n_words = (total_bits + 7) // 8, (total_bits + 31) // 32
+    with torch.cuda.device(dev):
+        streams = torch.zeros((T, max(n_words, 1)), dtype=torch.int32, device=dev) if want_masks else None
+        if D > 0:
+            need = int(nat.lib().svdq_tall_work_bytes(T))
+            state = torch.zeros(need // 8, dtype=torch.int64, device=dev)
+            lam_dev = torch.from_numpy(lam32).to(dev)
+            mask_tab = None
+            if want_masks:
+                mask_tab = torch.tensor([streams.data_ptr() + 4 * g * streams.shape[1] for g in range(T)],
+                                        dtype=torch.int64, device=dev)
+            keep = []
+            for batch, entries in jobs.values():
+                plan = batch.plan
+                P = plan.P
+                n_out = max([len(live[name]) for name in entries.values()] + [1])
+                slot_task = np.zeros((P, n_out), dtype=np.int32)
+                task_map = np.full((P, n_out), -1, dtype=np.int32)
+                out_tab = np.zeros(P, dtype=np.int64)
+                base_tab = np.zeros(P, dtype=np.int64)
+                bits = np.zeros(P, dtype=np.int64)
+                for i, name in entries.items():
+                    for j, (g, pq) in enumerate(live[name]):
+                        task_map[i, j], slot_task[i, j] = g, pq
+                    bits[i] = bit_base.get(name, 0)
+                    if not want_merge:
+                        continue
+                    if rows[name] <= 0:
+                        out[name] = torch.zeros(original_shapes[name], device=plan.device)
+                        continue
+                    res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
+                    out_tab[i] = res.data_ptr()
+                    b = base_state_dict.get(name) if base_state_dict is not None else None
+                    if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
+                        keep.append(prepare_vector(b, plan.device))
+                        base_tab[i] = keep[-1].data_ptr()
+                    elif b is not None:
+                        later[name] = b
+                rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+                plan.tall_consensus(torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device),
+                                    T, torch.from_numpy(bits).to(plan.device), lam_dev, state,
+                                    out_table=torch.from_numpy(out_tab).to(plan.device) if want_merge else None,
+                                    mask_table=mask_tab, min_agree=k if want_merge else 0, scaling=scaling,
+                                    base_table=torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None,
+                                    rows_dev=rows_dev)
+            host = state.cpu().numpy()
+            stats["active"] = {t: int(host[g]) for g, t in enumerate(wanted)}
+            stats["agreement"] = [int(x) for x in host[T:2 * T + 1]]
+        if want_merge:
+            for name in names:
+                if D == 0:
+                    out[name] = torch.zeros(original_shapes[name], device=dev)
+                res = out[name].view(original_shapes[name])
+                if name in later:
+                    res = later[name].to(res.device) + res
+                out[name] = res.cpu() if wants_cpu(device) else res
+        masks = None
+        if want_masks:
+            masks = {}
+            for g, t in enumerate(wanted):
+                m = streams[g].view(torch.uint8)[:n_bytes]
+                masks[t] = m.cpu() if wants_cpu(device) else m
+    return out, masks, stats
+
+
+def consensus_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                               original_shapes: Dict[str, torch.Size], config, tall_lambda=0.4, k: int = 2,
+                               scaling: float = 1.0, tasks=None,
+                               base_state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                               reference_state_dict: Optional[Dict[str, torch.Tensor]] = None, remove_keys=None,
+                               return_masks: bool = False, device: str = "cuda", return_stats: bool = False):
+    """TALL masks and the consensus merge (Wang et al. 2024) of what a store reconstructs, in one pass over the basis,
+    without a task model ever being written (the contract is at svdq_plan_tall_consensus in
+    include/svdq.h).  With v_t what ``reconstruct_task_vectors`` returns for task t and the tasks in sorted-name order:
+    S = the fp32 sum of the values task by task; task t's mask is ``|v_t| > lambda_t * |S - v_t|`` (strict); a row is kept
+    iff at least ``k`` masks are set there; the result is ``scaling * (kept ? S : 0)`` per parameter,
+    ``base + scaling * ...`` for the parameters ``base_state_dict`` holds.  ``k=0`` is task arithmetic.  A task that lacks
+    a parameter contributes nothing on its rows, and its mask is 0 there.
+
+    ``tall_lambda``: a number or {task: number} naming every merged task, finite and >= 0; ``k``: an integer in
+    [0, merged tasks] -- neither is clamped, a value outside raises a ValueError.  ``tasks``: the names to merge (None =
+    all).  Takes dictionaries backed by a fused run or by ``adopt_artifacts`` and refuses what ``dare_merge_parameters``
+    refuses, under its own name.  Outputs are fp32.
+
+    ``return_masks`` adds {task: uint8 tensor}: the masks bit-packed as ``numpy.packbits`` packs them, over the sorted
+    keys of ``reference_state_dict`` minus ``remove_keys`` (default: the store's own parameters) -- the streams a
+    TALL_mask_{T}task file holds.  Keys of the reference that the store lacks occupy zero bits; a store parameter without
+    a place in the reference, or with another element count there, raises a ValueError.
+
+    Returns {param: tensor}, then the masks with ``return_masks``, then {"active": {task: set bits}, "agreement": [rows
+    with 0 .. T set masks], "rows": D} with ``return_stats``.  The same arguments give the same bits on every call."""
+    out, masks, stats = _tall_run("consensus_merge_parameters", compressed_all, bases, original_shapes, tall_lambda, k,
+                                  scaling, tasks, base_state_dict, reference_state_dict, remove_keys, True,
+                                  bool(return_masks), device)
+    res = (out,) + ((masks,) if return_masks else ()) + ((stats,) if return_stats else ())
+    return res if len(res) > 1 else out
+
+
+def tall_masks_from_store(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                          original_shapes: Dict[str, torch.Size], config, tall_lambda=0.4, tasks=None,
+                          reference_state_dict: Optional[Dict[str, torch.Tensor]] = None, remove_keys=None,
+                          device: str = "cuda", return_stats: bool = False):
+    """The TALL masks of ``consensus_merge_parameters`` alone -- a launch that writes the packed streams and no merged
+    tensor: {task: uint8 tensor}, with ``return_stats`` also the statistics.  The arguments are that function's."""
+    _, masks, stats = _tall_run("tall_masks_from_store", compressed_all, bases, original_shapes, tall_lambda, None, 1.0,
+                                tasks, None, reference_state_dict, remove_keys, False, True, device)
+    return (masks, stats) if return_stats else masks

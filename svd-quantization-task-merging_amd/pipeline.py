@@ -958,6 +958,48 @@ class CompressPlan:
                                                 float(keep_scale), float(scaling), _ptr(base_table), _ptr(out_table),
                                                 _ptr(state), _ptr(self._task_work), _stream_ptr()), who)
 
+    # ---- TALL masks and the consensus merge (svdq_tall.hip)
+    def tall_consensus(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, bit_base: torch.Tensor,
+                       lambdas: torch.Tensor, state: torch.Tensor, out_table: Optional[torch.Tensor] = None,
+                       mask_table: Optional[torch.Tensor] = None, min_agree: int = 2, scaling: float = 1.0,
+                       base_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None) -> None:
+        """Sum, masks, consensus and apply for every parameter of the plan in one pass over the basis
+        (svdq_plan_tall_consensus; the definition is at that name in include/svdq.h).  ``slot_task`` / ``task_map``: as
+        for ``ties_merge``; ``bit_base`` int64 device tensor [P], the stream bit of every parameter's row 0; ``lambdas``
+        float32 device tensor [n_tasks]; ``state`` int64 device tensor of svdq_tall_work_bytes(n_tasks) bytes, zeroed by
+        the caller, which receives active [T] | agree [T + 1]; ``out_table`` int64 [P] fp32 outputs (None = masks only; a
+        0 entry skips that output alone); ``mask_table`` int64 [n_tasks], the addresses of the tasks' packed streams,
+        4-byte aligned, whole 32-bit words, zeroed by the caller (None = merge only); a row is kept iff at least
+        ``min_agree`` masks are set; ``base_table``: as for ``ties_merge``.  Asynchronous on the current stream."""
+        who = "svdq_plan_tall_consensus"
+        n_out = self._ties_tables(who, slot_task, task_map)
+        n_tasks = int(n_tasks)
+        need = int(self.lib.svdq_tall_work_bytes(n_tasks))
+        if need <= 0:
+            raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
+        if not (isinstance(bit_base, torch.Tensor) and bit_base.is_cuda and bit_base.dtype is torch.int64
+                and bit_base.is_contiguous() and bit_base.numel() == self.P):
+            raise ValueError(f"{who}: bit_base must be a contiguous int64 device tensor of {self.P} entries")
+        if not (isinstance(lambdas, torch.Tensor) and lambdas.is_cuda and lambdas.dtype is torch.float32
+                and lambdas.is_contiguous() and lambdas.numel() == n_tasks):
+            raise ValueError(f"{who}: lambdas must be a contiguous float32 device tensor of {n_tasks} entries")
+        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype is torch.int64
+                and state.is_contiguous() and state.numel() * 8 >= need):
+            raise ValueError(f"{who}: state must be a contiguous int64 device tensor of at least {need} bytes")
+        if out_table is None and mask_table is None:
+            raise ValueError(f"{who}: out_table and mask_table are both None: nothing to write")
+        for name, tab, count in (("out_table", out_table, self.P), ("mask_table", mask_table, n_tasks)):
+            if tab is not None and not (isinstance(tab, torch.Tensor) and tab.is_cuda and tab.dtype is torch.int64
+                                        and tab.is_contiguous() and tab.numel() == count):
+                raise ValueError(f"{who}: {name} must be a contiguous int64 device tensor of {count} entries")
+        if isinstance(min_agree, bool) or not isinstance(min_agree, int) or not 0 <= min_agree <= n_tasks:
+            raise ValueError(f"{who}: min_agree must be an integer in [0, {n_tasks}], got {min_agree!r}")
+        nat.check(self.lib.svdq_plan_tall_consensus(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                    _ptr(self.mean), _ptr(slot_task), _ptr(task_map), n_out, n_tasks,
+                                                    _ptr(bit_base), _ptr(lambdas), int(min_agree), float(scaling),
+                                                    _ptr(base_table), _ptr(out_table), _ptr(mask_table), _ptr(state),
+                                                    _ptr(self._task_work), _stream_ptr()), who)
+
     def diagnostics_masked(self, table, mask_table: torch.Tensor, unit_start: torch.Tensor, rows_dev: torch.Tensor,
                            add_mean: bool = False) -> torch.Tensor:
         """``diagnostics`` for a plan of masked regions: ``table`` names the UNMASKED task deltas, the selection

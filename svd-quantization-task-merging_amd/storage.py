@@ -598,6 +598,55 @@ def dare_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: s
     return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
 
 
+def consensus_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None,
+                                   mask_output_path: str = None, tall_lambda=0.4, k: int = 2, scaling: float = 1.0,
+                                   tasks=None, remove_keys=None, device: str = "cuda") -> Dict[str, Any]:
+    """TALL masks and the consensus merge of a stored artifact set (``merge.consensus_merge_parameters``, which see for
+    the definition): load_all_artifacts -> adopt_artifacts -> one launch per plan with the base inside it -> the base's
+    other tensors cloned (as apply_merged_deltas does) -> optional save.  ``mask_output_path`` receives
+    ``numpy.savez(path, **{task: packed mask})`` over the sorted keys of the base minus ``remove_keys`` -- named
+    TALL_mask_{T}task.npz it is what ``load_tall_mask_file``, ``combine_tall_masks_packed`` and ``--mask-dir`` read, with
+    the base as the reference state dict.  Masks are not stored (reload.py:204-205): a masked run's store is refused with
+    a ValueError naming the parameter.  ``base_model_path``: a path or a state dict; ``tasks``: names (None = every
+    stored task).  The store's files are only read.
+
+    Returns {"merged_state_dict", "masks" ({task: packed uint8 tensor} or None), "stats" (active, agreement, rows),
+    "diagnostics", "config"}."""
+    import numpy as np
+    from .driver import adopt_artifacts
+    from .merge import _tall_arguments, consensus_merge_parameters
+    who = "consensus_merge_parameters"
+    if not hasattr(tall_lambda, "get"):
+        _tall_arguments(who, tall_lambda, None, [None], check_k=False)      # one number for every task: before any file or device work
+    if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+        raise ValueError(f"{who}: k must be an integer in [0, merged tasks], got {k!r}")
+    art = load_all_artifacts(artifact_dir, device=device)
+    config, diagnostics = art["config"], art["diagnostics"]
+    if tasks is not None:
+        known = {t for per_task in art["compressed"].values() for t in per_task}
+        for t in tasks:
+            if t not in known:
+                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
+    base = _load_base(base_model_path, device)
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
+              if d.get("original_shape") is not None}
+    covered = {n: b for n, b in base.items() if n in compressed}
+    want_masks = mask_output_path is not None
+    got = consensus_merge_parameters(compressed, bases, shapes, config, tall_lambda=tall_lambda, k=k, scaling=scaling,
+                                     tasks=tasks, base_state_dict=covered,
+                                     reference_state_dict=base if want_masks else None, remove_keys=remove_keys,
+                                     return_masks=want_masks, device=device, return_stats=True)
+    merged, masks, stats = got if want_masks else (got[0], None, got[1])
+    out = {n: (merged[n] if n in merged else b.clone()) for n, b in base.items()}
+    if output_path:
+        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    if want_masks:
+        with open(mask_output_path, "wb") as f:      # a file object: numpy appends no suffix to the caller's name
+            np.savez(f, **{t: m.cpu().numpy() for t, m in masks.items()})
+    return {"merged_state_dict": out, "masks": masks, "stats": stats, "diagnostics": diagnostics, "config": config}
+
+
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
     """Reference reload.py:60-139: a pre-saved merged_state_dict.pt in the artifact directory wins; otherwise the
     merged model is rebuilt from bases + coefficients + the base model named in the stored config."""
