@@ -1057,6 +1057,69 @@ int svdq_plan_tall_consensus(const svdq_plan *plan, const int64_t *rows_dev, con
                              const void *mask_ptrs_dev /*NULL or [T] uint32-aligned streams*/, void *state_dev,
                              void *work_dev, void *stream);
 
+/* ---- the EMR merge of a store (Huang et al. 2024: "EMR-Merging: Tuning-Free High-Performance Model Merging"): Elect one
+ *      task vector tau_uni, a 1-bit Mask per task and one Rescaler per task in ONE streaming pass over the basis
+ *      (svdq_plan_emr_elect), and serve task t's model base + lambda_t * (M_t (.) tau_uni) in one streaming launch over
+ *      the whole model (svdq_emr_apply).  No task model is written by the first; the second reads tau_uni, 1 bit per row
+ *      and the base.  The definition follows the paper's equations; where the paper is silent the line says DECISION.
+ *        inputs   T tasks in sorted-name order, store task index g = 0 .. T-1, as for svdq_plan_tall_consensus;
+ *                 v_g[d] = the value svdq_task_reconstruct writes for task g at row d, bit for bit.  A task that lacks a
+ *                 parameter contributes nothing on its rows and its mask bits there are 0.  Non-finite store values are
+ *                 outside the definition, as for TIES, DARE and TALL.
+ *        sum      S starts at +0; for the tasks that have the parameter, in ascending g: S = S + v_g, every sum rounded
+ *                 in fp32 (the sum of svdq_plan_tall_consensus).
+ *        elect    gamma = +1 if S > 0, -1 if S < 0, 0 if S == 0.  eps = the maximum of |v_g| over the tasks that have the
+ *                 row and AGREE (v_g > 0 for gamma = +1, v_g < 0 for gamma = -1); eps = 0 with gamma = 0.  tau_uni = +0
+ *                 when gamma = 0 (DECISION: a row whose values cancel exactly elects nothing), else copysign(eps, gamma).
+ *                 A maximum is exact: tau_uni depends on no order.  fp32 addition is monotone, so S > 0 implies some
+ *                 v_g > 0: eps > 0 whenever gamma != 0.
+ *        mask     M_g[d] = the task has the row && v_g * gamma > 0 (the sign equals gamma and v_g != 0) -- the paper's
+ *                 v_g (.) tau_uni > 0, since eps > 0 there.  A row with S == 0 is in no mask.
+ *        rescale  over ALL rows of the store (every plan): A_g = sum |v_g[d]| over the rows the task has,
+ *                 B_g = sum M_g[d] * eps[d]; every term a non-negative fp32 value converted to fp64 exactly, the sums
+ *                 fp64.  lambda_g = A_g / B_g in fp64 (the caller's division); lambda_g = 1.0 when B_g == 0 (DECISION:
+ *                 the mask then selects nothing that is non-zero, the value is immaterial).
+ *        apply    out[d] = base[d] + lambda32 * (M_g[d] ? tau_uni[d] : +0), one product, one sum, each rounded in fp32;
+ *                 without a base the product.  lambda32 is a float the CALLER passes (by default float32(lambda_g)).
+ *        streams  one per store task (mask_ptrs_dev [T]), in exactly the layout of svdq_plan_tall_consensus: stream bit i
+ *                 is bit 7 - (i & 7) of byte i >> 3; row d of parameter p is stream bit bit_base[p] + d; whole 32-bit
+ *                 words are stored, the partial first and last word of a block's bit range are OR'ed in atomically; a
+ *                 stream starts on a 4-byte boundary, spans 4 * ceil(bits / 32) bytes and is zeroed by the caller.
+ *        sums     state_dev: double A [T] | double B [T] (svdq_emr_state_bytes(T) bytes, zeroed by the caller before the
+ *                 first plan of the store, shared by all plans).  DETERMINISTIC, the sums included: no floating-point
+ *                 atomics.  Every work unit adds its lanes' fp64 partials in a fixed order and STORES [2][T] doubles at
+ *                 its own slot of a per-plan table in work_dev; a one-block kernel then adds the units in ascending
+ *                 order -- as 1024 / 2T contiguous runs of units, the runs added in ascending order -- into state_dev.
+ *                 Plans are added in call order on the one stream.  The same arguments give the same bits on every call.
+ *   svdq_emr_state_bytes(T)                  [2][T] doubles, rounded up to 256 bytes; 0 for T outside [1, SVDQ_MAX_TASKS].
+ *   svdq_emr_work_bytes(plan, n_out, T)      the coefficient scratch of svdq_task_reconstruct_work_bytes(plan, n_out)
+ *                                            plus the per-unit table; 0 for a NULL plan or a count outside the range.
+ *   svdq_plan_emr_elect   uni_ptrs_dev [P] fp32 outputs of rows[p] elements, the table required (a NULL entry skips that
+ *                 parameter's tau_uni, never its mask bits or sums); mask_ptrs_dev [T] required.  One mode: there is no
+ *                 mask-only or vector-only variant.  slot_task_dev, task_map_dev, n_out, n_tasks, rows_dev, small_dev,
+ *                 basis_dev, mean_dev, bit_base_dev: as for svdq_plan_tall_consensus (live slots in ASCENDING store order).
+ *   svdq_emr_apply        one task's model for the n_params parameters of the tables, in ONE launch: rows_dev int64 [P],
+ *                 bit_base_dev int64 [P], uni_ptrs_dev [P] (what svdq_plan_emr_elect wrote), mask_stream_dev the task's
+ *                 stream, base_ptrs_dev NULL or [P] with NULL entries allowed, out_ptrs_dev [P] fp32 outputs (a NULL
+ *                 entry, or a NULL tau_uni, skips the parameter).  out may alias base.  16-byte loads and stores where a
+ *                 parameter's pointers are 16-byte aligned, 4-byte ones otherwise.  n_params <= 7679 (the prefix table of
+ *                 the rows lives in LDS).
+ *   errors        SVDQ_EINVAL before anything is launched: a NULL plan, buffer or table; n_out or n_tasks outside
+ *                 [1, SVDQ_MAX_TASKS]; a missing mean on a centred plan; n_params outside [1, 7679]; a non-finite lambda32.
+ *   Allocate nothing, copy nothing to the host, synchronise nothing.  Work on plans filled by any compress route and on
+ *   plans filled by svdq_plan_import. */
+int64_t svdq_emr_state_bytes(int32_t n_tasks);
+int64_t svdq_emr_work_bytes(const svdq_plan *plan, int32_t n_out, int32_t n_tasks);
+int svdq_plan_emr_elect(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                        const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                        const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks,
+                        const int64_t *bit_base_dev /*[P]*/, const void *uni_ptrs_dev /*[P], required*/,
+                        const void *mask_ptrs_dev /*[T] uint32-aligned streams, required*/, void *state_dev,
+                        void *work_dev, void *stream);
+int svdq_emr_apply(int32_t n_params, const int64_t *rows_dev /*[P]*/, const int64_t *bit_base_dev /*[P]*/,
+                   const void *uni_ptrs_dev /*[P]*/, const void *mask_stream_dev, float lambda32,
+                   const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/, void *stream);
+
 /* ---- measurement aid (no reference counterpart; SURVEY.md section 8d asks for "a measured device-copy ceiling on
  *      the box" beside the 8 TB/s specification): plain streaming kernels with the access shape of the two passes.
  *      mode 0: read `bytes` from src_dev (dst_dev receives one float per 256 KiB read); mode 1: copy `bytes`;

@@ -1074,3 +1074,205 @@ def tall_masks_from_store(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
     _, masks, stats = _tall_run("tall_masks_from_store", compressed_all, bases, original_shapes, tall_lambda, None, 1.0,
                                 tasks, None, reference_state_dict, remove_keys, False, True, device)
     return (masks, stats) if return_stats else masks
+
+
+def _emr_layout(who, names, rows, reference_state_dict, remove_keys):
+    """({key: first stream bit}, total bits) of the EMR mask streams: the layout ``_tall_run`` gives the TALL streams --
+    the sorted keys of the reference minus ``remove_keys`` (default: ``names``), each at the bit after the one before it."""
+    skip = set(remove_keys or [])
+    if reference_state_dict is None:
+        sizes = {n: rows[n] for n in names if n not in skip}
+    else:
+        sizes = {key: int(x.numel()) for key, x in reference_state_dict.items() if key not in skip}
+    for name in names:
+        if name not in sizes:
+            raise ValueError(f"{who}: parameter {name!r} of the store has no place in the mask streams (it is not a "
+                             f"key of reference_state_dict, or remove_keys names it)")
+        if sizes[name] != rows[name]:
+            raise ValueError(f"{who}: reference_state_dict[{name!r}] has {sizes[name]} elements, the store holds "
+                             f"{rows[name]} rows for it")
+    bit_base, total_bits = {}, 0
+    for key in sorted(sizes):
+        bit_base[key] = total_bits
+        total_bits += sizes[key]
+    return bit_base, total_bits
+
+
+def _popcount_rows(words: torch.Tensor) -> torch.Tensor:
+    """Set bits per row of an int32 device tensor [T, W] (int64 [T]); the streams hold 1 / 32 of a model's rows."""
+    x = words.to(torch.int64) & 0xffffffff
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    x = (x + (x >> 4)) & 0x0f0f0f0f
+    return (((x * 0x01010101) >> 24) & 0xff).sum(dim=1)
+
+
+def emr_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                         original_shapes: Dict[str, torch.Size], config, tasks=None,
+                         reference_state_dict: Optional[Dict[str, torch.Tensor]] = None, remove_keys=None,
+                         device: str = "cuda", return_stats: bool = False):
+    """The EMR merge (Huang et al. 2024) of what a store reconstructs, in one pass over the basis, without a task model
+    ever being written (the contract is at svdq_plan_emr_elect in include/svdq.h).  With v_t what
+    ``reconstruct_task_vectors`` returns for task t and the tasks in sorted-name order: S = the fp32 sum of the values task
+    by task, gamma its sign; ``tau_uni = copysign(max |v_t| over the tasks whose sign is gamma, gamma)`` (+0 where S == 0);
+    task t's mask is ``v_t * gamma > 0``; its rescaler is ``sum |v_t| / sum (mask_t ? |tau_uni| : 0)`` over all rows, the
+    sums in fp64 (1.0 where the second sum is 0).  Task t's model is then ``base + rescaler_t * (mask_t ? tau_uni : 0)``
+    (``emr_task_state_dict``).  A task that lacks a parameter contributes nothing on its rows, and its mask is 0 there.
+    Nothing is tuned.
+
+    ``tasks``: the names to merge (None = all).  Takes dictionaries backed by a fused run or by ``adopt_artifacts`` and
+    refuses what ``dare_merge_parameters`` refuses, under its own name.  The masks are bit-packed as ``numpy.packbits``
+    packs them, over the sorted keys of ``reference_state_dict`` minus ``remove_keys`` (default: the store's own
+    parameters) -- the layout of a TALL_mask_{T}task file.  Keys of the reference that the store lacks occupy zero bits; a
+    store parameter without a place in the reference, or with another element count there, raises a ValueError.
+
+    Returns (unified {param: fp32 tensor}, masks {task: packed uint8 tensor}, rescalers {task: float}); with
+    ``return_stats`` also {"abs_sum": {task: A}, "masked_sum": {task: B}, "active": {task: set bits}, "rows": D}.  The
+    same arguments give the same bits on every call, the sums included."""
+    import numpy as np
+    who = "emr_merge_parameters"
+    known = []
+    for per_task in compressed_all.values():
+        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
+                  if t not in known]
+    for t in (tasks if tasks is not None else []):
+        if t not in known:
+            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    wanted = sorted(set(known if tasks is None else tasks))
+    T = len(wanted)
+    if not 1 <= T <= nat.MAX_TASKS:
+        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
+    names = sorted(compressed_all.keys())
+    jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
+                                  "the EMR merge")      # refusals before device work
+    bit_base, total_bits = _emr_layout(who, names, rows, reference_state_dict, remove_keys)
+    dev = resolve_device(device)
+    D = sum(rows.values())
+    n_bytes, n_words = (total_bits + 7) // 8, (total_bits + 31) // 32
+    unified = {}
+    A, B = [0.0] * T, [0.0] * T
+    active = [0] * T
+    with torch.cuda.device(dev):
+        streams = torch.zeros((T, max(n_words, 1)), dtype=torch.int32, device=dev)
+        if D > 0:
+            state = torch.zeros(int(nat.lib().svdq_emr_state_bytes(T)) // 8, dtype=torch.float64, device=dev)
+            mask_tab = torch.tensor([streams.data_ptr() + 4 * g * streams.shape[1] for g in range(T)],
+                                    dtype=torch.int64, device=dev)
+            for batch, entries in jobs.values():
+                plan = batch.plan
+                P = plan.P
+                n_out = max([len(live[name]) for name in entries.values()] + [1])
+                slot_task = np.zeros((P, n_out), dtype=np.int32)
+                task_map = np.full((P, n_out), -1, dtype=np.int32)
+                uni_tab = np.zeros(P, dtype=np.int64)
+                bits = np.zeros(P, dtype=np.int64)
+                for i, name in entries.items():
+                    for j, (g, pq) in enumerate(live[name]):
+                        task_map[i, j], slot_task[i, j] = g, pq
+                    bits[i] = bit_base[name]
+                    if rows[name] <= 0:
+                        continue
+                    res = unified[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
+                    uni_tab[i] = res.data_ptr()
+                rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+                plan.emr_elect(torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device), T,
+                               torch.from_numpy(bits).to(plan.device), torch.from_numpy(uni_tab).to(plan.device), mask_tab,
+                               state, rows_dev=rows_dev)
+            host = state.cpu().numpy()
+            A, B = [float(x) for x in host[:T]], [float(x) for x in host[T:2 * T]]
+            if return_stats:
+                active = [int(x) for x in _popcount_rows(streams).cpu().tolist()]
+        for name in names:
+            if name not in unified:
+                unified[name] = torch.zeros(rows[name], dtype=torch.float32, device=dev)
+            res = unified[name].view(original_shapes[name])
+            unified[name] = res.cpu() if wants_cpu(device) else res
+        masks = {}
+        for g, t in enumerate(wanted):
+            m = streams[g].view(torch.uint8)[:n_bytes]
+            masks[t] = m.cpu() if wants_cpu(device) else m
+    rescalers = {t: (A[g] / B[g] if B[g] != 0.0 else 1.0) for g, t in enumerate(wanted)}
+    if not return_stats:
+        return unified, masks, rescalers
+    stats = {"abs_sum": dict(zip(wanted, A)), "masked_sum": dict(zip(wanted, B)), "active": dict(zip(wanted, active)),
+             "rows": D}
+    return unified, masks, rescalers, stats
+
+
+def emr_task_state_dict(unified: Dict[str, torch.Tensor], masks: Dict[str, torch.Tensor], rescalers: Dict[str, float],
+                        task: str, base_state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                        reference_state_dict: Optional[Dict[str, torch.Tensor]] = None, remove_keys=None, rescale=None,
+                        device: str = "cuda") -> Dict[str, torch.Tensor]:
+    """Task ``task``'s model from what ``emr_merge_parameters`` returned, in ONE launch over the whole model
+    (svdq_emr_apply): ``out = base + lambda * (mask ? tau_uni : +0)`` per parameter of ``unified``, the product and the
+    sum rounded in fp32, ``lambda = float32(rescalers[task])`` or ``float32(rescale)`` when that is given.  Without
+    ``base_state_dict`` (or for a parameter it lacks) the product alone: the task vector EMR serves.  A base that is a
+    contiguous fp32 tensor of the parameter's size is added inside the launch; any other base is added afterwards in its
+    own arithmetic (``base.to(device) + product``), as ``consensus_merge_parameters`` does.  ``reference_state_dict`` /
+    ``remove_keys``: the layout of the mask streams, the ones ``emr_merge_parameters`` was given.  Outputs are fp32, in
+    the shapes of ``unified``; keys of the base that ``unified`` lacks are not returned."""
+    import math
+    import numpy as np
+    who = "emr_task_state_dict"
+    if task not in masks:
+        raise ValueError(f"{who}: unknown task {task!r}: the masks hold {sorted(masks)}")
+    lam = rescale if rescale is not None else rescalers.get(task)
+    if lam is None:
+        raise ValueError(f"{who}: the rescaler of task {task!r} is missing")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(lam):
+        raise ValueError(f"{who}: the rescaler of task {task!r} must be a finite number, got {lam!r}")
+    with np.errstate(over="ignore"):
+        lam32 = float(np.float32(lam))
+    if not math.isfinite(lam32):
+        raise ValueError(f"{who}: the rescaler of task {task!r} is not finite in fp32: {lam!r}")
+    names = sorted(unified.keys())
+    rows = {n: int(unified[n].numel()) for n in names}
+    bit_base, total_bits = _emr_layout(who, names, rows, reference_state_dict, remove_keys)
+    n_bytes, n_words = (total_bits + 7) // 8, (total_bits + 31) // 32
+    stream = masks[task]
+    if not (isinstance(stream, torch.Tensor) and stream.dtype is torch.uint8 and stream.dim() == 1
+            and stream.numel() == n_bytes):
+        raise ValueError(f"{who}: the mask of task {task!r} must be a uint8 tensor of {n_bytes} bytes "
+                         f"({total_bits} bits), got {tuple(stream.shape) if isinstance(stream, torch.Tensor) else stream!r}")
+    if len(names) > 7679:
+        raise ValueError(f"{who}: at most 7679 parameters per call, got {len(names)}")
+    dev = resolve_device(device)
+    out, later, keep = {}, {}, []
+    if not names:
+        return out
+    with torch.cuda.device(dev):
+        # the kernel reads whole 32-bit words: the stream goes into a buffer that has them
+        words = torch.zeros(4 * max(n_words, 1), dtype=torch.uint8, device=dev)
+        words[:n_bytes] = stream.to(dev)
+        P = len(names)
+        rows_tab = np.zeros(P, dtype=np.int64)
+        bits = np.zeros(P, dtype=np.int64)
+        uni_tab = np.zeros(P, dtype=np.int64)
+        base_tab = np.zeros(P, dtype=np.int64)
+        out_tab = np.zeros(P, dtype=np.int64)
+        for i, name in enumerate(names):
+            rows_tab[i], bits[i] = rows[name], bit_base[name]
+            if rows[name] <= 0:
+                out[name] = torch.zeros(unified[name].shape, dtype=torch.float32, device=dev)
+                continue
+            keep.append(prepare_vector(unified[name], dev))
+            uni_tab[i] = keep[-1].data_ptr()
+            res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=dev)
+            out_tab[i] = res.data_ptr()
+            b = base_state_dict.get(name) if base_state_dict is not None else None
+            if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
+                keep.append(prepare_vector(b, dev))
+                base_tab[i] = keep[-1].data_ptr()
+            elif b is not None:
+                later[name] = b
+        tabs = [torch.from_numpy(x).to(dev) for x in (rows_tab, bits, uni_tab, out_tab)]
+        base_dev = torch.from_numpy(base_tab).to(dev) if base_tab.any() else None
+        if out_tab.any():
+            nat.check(nat.lib().svdq_emr_apply(P, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(words), lam32,
+                                               _ptr(base_dev), _ptr(tabs[3]), _stream_ptr()), "svdq_emr_apply")
+        for name in names:
+            res = out[name].view(unified[name].shape)
+            if name in later:
+                res = later[name].to(res.device) + res
+            out[name] = res.cpu() if wants_cpu(device) else res
+    return out

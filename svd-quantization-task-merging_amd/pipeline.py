@@ -1000,6 +1000,42 @@ class CompressPlan:
                                                     _ptr(base_table), _ptr(out_table), _ptr(mask_table), _ptr(state),
                                                     _ptr(self._task_work), _stream_ptr()), who)
 
+    # ---- the EMR merge: elected vector, task masks, rescaler sums (svdq_emr.hip)
+    def emr_elect(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, bit_base: torch.Tensor,
+                  uni_table: torch.Tensor, mask_table: torch.Tensor, state: torch.Tensor,
+                  rows_dev: Optional[torch.Tensor] = None) -> None:
+        """Elect, mask and the rescalers' sums for every parameter of the plan in one pass over the basis
+        (svdq_plan_emr_elect; the definition is at that name in include/svdq.h).  ``slot_task`` / ``task_map``: as for
+        ``ties_merge``; ``bit_base`` int64 device tensor [P], the stream bit of every parameter's row 0; ``uni_table``
+        int64 [P], the fp32 outputs that receive tau_uni (a 0 entry skips that output alone); ``mask_table`` int64
+        [n_tasks], the addresses of the tasks' packed streams, 4-byte aligned, whole 32-bit words, zeroed by the caller;
+        ``state`` float64 device tensor of svdq_emr_state_bytes(n_tasks) bytes, zeroed by the caller before the store's
+        first plan, which receives A [T] | B [T].  Asynchronous on the current stream."""
+        who = "svdq_plan_emr_elect"
+        n_out = self._ties_tables(who, slot_task, task_map)
+        n_tasks = int(n_tasks)
+        need = int(self.lib.svdq_emr_state_bytes(n_tasks))
+        if need <= 0:
+            raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
+        if not (isinstance(bit_base, torch.Tensor) and bit_base.is_cuda and bit_base.dtype is torch.int64
+                and bit_base.is_contiguous() and bit_base.numel() == self.P):
+            raise ValueError(f"{who}: bit_base must be a contiguous int64 device tensor of {self.P} entries")
+        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype is torch.float64
+                and state.is_contiguous() and state.numel() * 8 >= need):
+            raise ValueError(f"{who}: state must be a contiguous float64 device tensor of at least {need} bytes")
+        for name, tab, count in (("uni_table", uni_table, self.P), ("mask_table", mask_table, n_tasks)):
+            if not (isinstance(tab, torch.Tensor) and tab.is_cuda and tab.dtype is torch.int64
+                    and tab.is_contiguous() and tab.numel() == count):
+                raise ValueError(f"{who}: {name} must be a contiguous int64 device tensor of {count} entries")
+        work = getattr(self, "_emr_work", None)
+        need = int(self.lib.svdq_emr_work_bytes(self._h, n_out, n_tasks))
+        if work is None or work.numel() < need:
+            work = self._emr_work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        nat.check(self.lib.svdq_plan_emr_elect(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                               _ptr(self.mean), _ptr(slot_task), _ptr(task_map), n_out, n_tasks,
+                                               _ptr(bit_base), _ptr(uni_table), _ptr(mask_table), _ptr(state), _ptr(work),
+                                               _stream_ptr()), who)
+
     def diagnostics_masked(self, table, mask_table: torch.Tensor, unit_start: torch.Tensor, rows_dev: torch.Tensor,
                            add_mean: bool = False) -> torch.Tensor:
         """``diagnostics`` for a plan of masked regions: ``table`` names the UNMASKED task deltas, the selection

@@ -647,6 +647,96 @@ def consensus_merge_from_artifacts(artifact_dir: str, base_model_path, output_pa
     return {"merged_state_dict": out, "masks": masks, "stats": stats, "diagnostics": diagnostics, "config": config}
 
 
+EMR_UNIFIED_FILE, EMR_RESCALER_FILE = "emr_unified.pt", "emr_rescalers.json"
+
+
+def save_emr_merge(output_dir: str, unified: Dict[str, torch.Tensor], masks: Dict[str, torch.Tensor],
+                   rescalers: Dict[str, float], stats: Optional[Dict[str, Any]] = None) -> Dict[str, str]:
+    """The three files of an EMR merge (``merge.emr_merge_parameters``): emr_unified.pt ({param: fp32 tensor}),
+    EMR_mask_{T}task.npz (``numpy.savez(file, **{task: packed mask})``, the container of a TALL_mask_{T}task.npz:
+    ``load_tall_mask_file`` reads it back, with the unified tensors as the reference state dict) and emr_rescalers.json
+    ({"tasks", "rescalers", "mask_file"} and the statistics when given; Python writes a float so that it reads back
+    exactly).  Returns {"unified", "masks", "rescalers"}: the paths."""
+    import numpy as np
+    os.makedirs(output_dir, exist_ok=True)
+    tasks = sorted(masks)
+    paths = {"unified": os.path.join(output_dir, EMR_UNIFIED_FILE),
+             "masks": os.path.join(output_dir, f"EMR_mask_{len(tasks)}task.npz"),
+             "rescalers": os.path.join(output_dir, EMR_RESCALER_FILE)}
+    torch.save({n: v.detach().cpu() for n, v in unified.items()}, paths["unified"])
+    with open(paths["masks"], "wb") as f:      # a file object: numpy appends no suffix to the name
+        np.savez(f, **{t: masks[t].detach().cpu().numpy() for t in tasks})
+    record = {"tasks": tasks, "rescalers": {t: float(rescalers[t]) for t in tasks},
+              "mask_file": os.path.basename(paths["masks"])}
+    if stats is not None:
+        record.update({"abs_sum": {t: float(stats["abs_sum"][t]) for t in tasks},
+                       "masked_sum": {t: float(stats["masked_sum"][t]) for t in tasks},
+                       "active": {t: int(stats["active"][t]) for t in tasks}, "rows": int(stats["rows"])})
+    with open(paths["rescalers"], "w") as f:
+        json.dump(record, f, indent=2)
+    return paths
+
+
+def load_emr_merge(output_dir: str, device: str = "cpu"):
+    """(unified, masks {task: packed uint8 tensor}, rescalers, record) from the files ``save_emr_merge`` wrote; both
+    loaders execute nothing from the files."""
+    import numpy as np
+    with open(os.path.join(output_dir, EMR_RESCALER_FILE)) as f:
+        record = json.load(f)
+    unified = torch.load(os.path.join(output_dir, EMR_UNIFIED_FILE), map_location=device, weights_only=True)
+    with np.load(os.path.join(output_dir, record["mask_file"]), allow_pickle=False) as z:
+        masks = {t: torch.from_numpy(np.ascontiguousarray(z[t])).reshape(-1) for t in z.files}
+    return unified, masks, {t: float(x) for t, x in record["rescalers"].items()}, record
+
+
+def emr_from_artifacts(artifact_dir: str, output_dir: str, tasks=None, device: str = "cuda") -> Dict[str, Any]:
+    """The EMR merge of a stored artifact set (``merge.emr_merge_parameters``, which see for the definition):
+    load_all_artifacts -> adopt_artifacts -> one launch per plan -> ``save_emr_merge`` into ``output_dir``.  The mask
+    streams run over the store's own parameters in sorted order.  Masks are not stored (reload.py:204-205): a masked
+    run's store is refused with a ValueError naming the parameter.  ``tasks``: names (None = every stored task).  The
+    store's files are only read.
+
+    Returns {"unified", "masks", "rescalers", "stats" (abs_sum, masked_sum, active, rows), "paths", "diagnostics",
+    "config"}."""
+    from .driver import adopt_artifacts
+    from .merge import emr_merge_parameters
+    art = load_all_artifacts(artifact_dir, device=device)
+    config, diagnostics = art["config"], art["diagnostics"]
+    if tasks is not None:
+        known = {t for per_task in art["compressed"].values() for t in per_task}
+        for t in tasks:
+            if t not in known:
+                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
+              if d.get("original_shape") is not None}
+    unified, masks, rescalers, stats = emr_merge_parameters(compressed, bases, shapes, config, tasks=tasks,
+                                                            device=device, return_stats=True)
+    paths = save_emr_merge(output_dir, unified, masks, rescalers, stats)
+    return {"unified": unified, "masks": masks, "rescalers": rescalers, "stats": stats, "paths": paths,
+            "diagnostics": diagnostics, "config": config}
+
+
+def emr_task_model_from_files(output_dir: str, task: str, base_model_path, output_path: str = None, rescale=None,
+                              device: str = "cuda") -> Dict[str, Any]:
+    """Task ``task``'s model from the files of ``emr_from_artifacts`` and a base model: ``load_emr_merge`` -> one launch
+    (``merge.emr_task_state_dict``, the base inside it) -> the base's other tensors cloned (as apply_merged_deltas does)
+    -> optional save.  ``base_model_path``: a path or a state dict; ``rescale`` overrides the stored scalar.
+
+    Returns {"state_dict", "rescaler"}."""
+    from .merge import emr_task_state_dict
+    unified, masks, rescalers, _ = load_emr_merge(output_dir, device="cpu")
+    if task not in masks or task not in rescalers:
+        raise ValueError(f"unknown task {task!r}: {output_dir} holds {sorted(masks)}")
+    base = _load_base(base_model_path, device)
+    covered = {n: b for n, b in base.items() if n in unified}
+    got = emr_task_state_dict(unified, masks, rescalers, task, base_state_dict=covered, rescale=rescale, device=device)
+    out = {n: (got[n] if n in got else b.clone()) for n, b in base.items()}
+    if output_path:
+        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    return {"state_dict": out, "rescaler": float(rescalers[task] if rescale is None else rescale)}
+
+
 def reload_merged_model_from_artifacts(artifact_dir: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
     """Reference reload.py:60-139: a pre-saved merged_state_dict.pt in the artifact directory wins; otherwise the
     merged model is rebuilt from bases + coefficients + the base model named in the stored config."""
