@@ -12,47 +12,10 @@
 // The state table (uint64 words; svdq_dare_work_bytes): kept [T], the values kept per store task.  Integer counts added
 // by atomics, one flush per unit: no result depends on the order the units arrive in.
 //
-// k_dare_coeff, dare_live_mask and dare_stream are COPIES of k_ties_coeff, ties_live_mask and ties_stream
-// (svdq_ties.hip), kept here so that svdq_ties.hip is compiled from the text it had (the rule of DESIGN.md section 27:
-// share through a header only when every instantiation keeps its resource usage; not tried here -- the kernel of a
-// translation unit that is not touched cannot move).  A change to one of the three belongs in both files.
+// The coefficient kernel, the live mask, the argument check and the dispatcher are those of svdq_store_values.h.
 
-#include "svdq_common.h"
-#include "svdq_dispatch.h"
-#include "svdq_merge_stream.h"
 #include "svdq_philox.h"
-#include "svdq_small_view.h"
-#include "svdq_store_pass.h"
-
-typedef unsigned long long dare_u64;
-
-// ------------------------------------------------------------------------------------ coefficients (copy of k_ties_coeff)
-// cbar [P][n_out][N]: slot j of parameter p holds the coefficients of plan task slot_task[p][j] exactly as k_task_coeff
-// (svdq_merge.hip) leaves them (0 + c * 1, rounded as there); a slot whose task_map entry is < 0 holds zeros.
-__global__ __launch_bounds__(64) void k_dare_coeff(int NT, int stages, int n_out, const int32_t *__restrict__ slot_task,
-                                                   const int32_t *__restrict__ task_map,
-                                                   const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
-                                                   const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
-                                                   const float *__restrict__ scale, const float *__restrict__ zp,
-                                                   float *__restrict__ cbar) {
-    const int p = blockIdx.x, i = threadIdx.x, n = NT;
-    const int k = k_in[p], r = r_in[p];
-    if (i >= n) return;
-    for (int s = 0; s < n_out; ++s) {
-        const int t = slot_task[(size_t)p * n_out + s];
-        float acc = 0.f;
-        if (i < r && task_map[(size_t)p * n_out + s] >= 0 && (unsigned)t < (unsigned)n)
-            acc = __fadd_rn(acc, __fmul_rn(task_coeff(p, t, i, n, k, stages, chigh, codes, scale, zp), 1.f));
-        cbar[((size_t)p * n_out + s) * n + i] = acc;
-    }
-}
-
-// bit j: slot j of the parameter is a live task of the store (wave-uniform; copy of ties_live_mask)
-__device__ __forceinline__ unsigned dare_live_mask(const int32_t *__restrict__ st, const int32_t *__restrict__ tm,
-                                                   int n_out, int n, int T, int lane) {
-    const int j = lane < n_out ? lane : 0;
-    return (unsigned)__ballot(lane < n_out && (unsigned)tm[j] < (unsigned)T && (unsigned)st[j] < (unsigned)n);
-}
+#include "svdq_store_values.h"
 
 // ------------------------------------------------------------------------------------ draw, rescale, combine, apply
 // LDS beyond the streaming carve: W [nop] the weights of the slots' store tasks (0 on a slot that is no live task), KC [nop]
@@ -69,7 +32,7 @@ __global__ __launch_bounds__(64) void k_dare_merge(const SvdqParam *__restrict__
                                                    const float *__restrict__ weights, uint32_t key0, uint32_t key1,
                                                    uint32_t thr, float keep_scale, float scaling,
                                                    const float *const *__restrict__ base_ptrs,
-                                                   float *const *__restrict__ out_ptrs, dare_u64 *__restrict__ state) {
+                                                   float *const *__restrict__ out_ptrs, store_u64 *__restrict__ state) {
     using Geo = StreamGeom<U16, RPL>;
     using L = StreamLds<U16, RPL, false>;
     using TU = typename Geo::T;
@@ -90,7 +53,7 @@ __global__ __launch_bounds__(64) void k_dare_merge(const SvdqParam *__restrict__
     mg_gfloat_w *gout = (mg_gfloat_w *)out_ptrs[p];
     if (!gout) return;
     const int32_t *tm = task_map + (size_t)p * n_out;
-    const unsigned live = dare_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
+    const unsigned live = store_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
     const int k = uv.k, nl = uv.nl;
     const int64_t g_first = row_base[p];      // the global row of the parameter's row 0
     const bool divide = keep_scale != 0.f && keep_scale != 1.f;      // v / 1 is v: task arithmetic divides nothing
@@ -180,7 +143,7 @@ __global__ __launch_bounds__(64) void k_dare_merge(const SvdqParam *__restrict__
     // ---- one flush per unit
     lds_fence();
     for (int j = lane; j < n_out; j += 64)
-        if (((live >> j) & 1u) && KC[j]) atomicAdd(&state[tm[j]], (dare_u64)KC[j]);
+        if (((live >> j) & 1u) && KC[j]) atomicAdd(&state[tm[j]], (store_u64)KC[j]);
 }
 
 // ------------------------------------------------------------------------------------ entry points
@@ -189,42 +152,13 @@ extern "C" int64_t svdq_dare_work_bytes(int32_t n_tasks) {
     return svdq_align_up((int64_t)n_tasks * 8, 256);
 }
 
-// the live tasks' coefficients, then `launch` with the compiled-in basis type, task group and rows per lane (copy of
-// ties_stream)
-template <typename F>
-static int dare_stream(const char *who, const svdq_plan *pl, const void *small, const int32_t *slot_task,
-                       const int32_t *task_map, int n_out, float *cbar, hipStream_t st, F &&launch) {
-    const SmallView sv = small_view(pl->small, small);
-    hipLaunchKernelGGL(k_dare_coeff, dim3(pl->n_params), dim3(64), 0, st, pl->n_tasks, pl->cfg.rtvq_stages, n_out,
-                       slot_task, task_map, sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, cbar);
-    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
-    const int rpl = pl->n_tasks <= 16 ? 4 : 2;
-    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
-        return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
-            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
-                launch(f16_c, tg_c, rpl_c, sv, (n_out + tg - 1) / tg * tg);
-                return true;
-            });
-        });
-    });
-    return svdq_launch_status(ok, who);
-}
-
 extern "C" int svdq_plan_dare_merge(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
                                     const float *mean, const int32_t *slot_task, const int32_t *task_map, int32_t n_out,
                                     int32_t n_tasks, const int64_t *row_base, const float *weights, uint64_t seed,
                                     uint32_t drop_threshold, float keep_scale, float scaling, const void *base_ptrs,
                                     const void *out_ptrs, void *state, void *work, void *stream) {
     const char *who = "svdq_plan_dare_merge";
-    if (!pl || !small || !basis || !slot_task || !task_map || !state || !work) {
-        svdq_set_error("%s: plan, small, basis, slot_task, task_map, state and work are required", who);
-        return SVDQ_EINVAL;
-    }
-    if (n_out < 1 || n_out > SVDQ_MAX_TASKS || n_tasks < 1 || n_tasks > SVDQ_MAX_TASKS) {
-        svdq_set_error("%s: n_out and n_tasks must be in [1, %d], got %d and %d", who, SVDQ_MAX_TASKS, n_out, n_tasks);
-        return SVDQ_EINVAL;
-    }
-    if (svdq_refuse_no_mean(who, pl, mean)) return SVDQ_EINVAL;
+    if (int rc = store_args_ok(who, pl, small, basis, mean, slot_task, task_map, n_out, n_tasks, state, work)) return rc;
     if (!row_base || !weights || !out_ptrs) {
         svdq_set_error("%s: row_base, weights and out_ptrs are required", who);
         return SVDQ_EINVAL;
@@ -237,7 +171,7 @@ extern "C" int svdq_plan_dare_merge(const svdq_plan *pl, const int64_t *rows_dev
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
     const uint32_t key0 = (uint32_t)(seed & 0xffffffffull), key1 = (uint32_t)(seed >> 32);
-    return dare_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
+    return store_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
                        [&](auto f16_c, auto tg_c, auto rpl_c, const SmallView &sv, int nop) {
                            constexpr bool F16 = f16_c;
                            constexpr int TG = tg_c, RPL = rpl_c;
@@ -246,6 +180,6 @@ extern "C" int svdq_plan_dare_merge(const svdq_plan *pl, const int64_t *rows_dev
                                               Plain::bytes(n, nop, 2 * nop), st, pl->d_params, pl->d_units, rows_dev, n,
                                               (int)n_out, (int)n_tasks, slot_task, task_map, sv.k, sv.r, bs, mn, cbar,
                                               row_base, weights, key0, key1, drop_threshold, keep_scale, scaling, bp, op,
-                                              reinterpret_cast<dare_u64 *>(state));
+                                              reinterpret_cast<store_u64 *>(state));
                        });
 }

@@ -21,64 +21,28 @@
 // its own slot of the plan's table [n_units][2][T].  k_emr_finish, one block, then adds the units in ascending order -- in 1024 / 2 T
 // contiguous runs of units, one per thread, the runs added in ascending order -- into the store's state [2][T].
 //
-// k_emr_coeff, emr_live_mask and emr_stream are COPIES of k_ties_coeff, ties_live_mask and ties_stream (svdq_ties.hip;
-// svdq_dare.hip and svdq_tall.hip hold the other copies), kept here so that those files are compiled from the text they
-// had (the rule of DESIGN.md section 27).  A change to one belongs in all four files.
+// The coefficient kernel, the live mask, the bit image and its word writer, the argument check and the dispatcher are
+// those of svdq_store_values.h.
 
-#include "svdq_common.h"
-#include "svdq_dispatch.h"
-#include "svdq_merge_stream.h"
-#include "svdq_small_view.h"
-#include "svdq_store_pass.h"
+#include "svdq_store_values.h"
 
 #include <cmath>
 
-typedef unsigned long long emr_u64;
-typedef __attribute__((address_space(1))) uint32_t emr_gu32;
 typedef const __attribute__((address_space(1))) uint32_t emr_gcu32;
 typedef __attribute__((address_space(1))) f32x4 emr_gf32x4_w;
 
-// ------------------------------------------------------------------------------------ coefficients (copy of k_ties_coeff)
-// cbar [P][n_out][N]: slot j of parameter p holds the coefficients of plan task slot_task[p][j] exactly as k_task_coeff
-// (svdq_merge.hip) leaves them (0 + c * 1, rounded as there); a slot whose task_map entry is < 0 holds zeros.
-__global__ __launch_bounds__(64) void k_emr_coeff(int NT, int stages, int n_out, const int32_t *__restrict__ slot_task,
-                                                  const int32_t *__restrict__ task_map,
-                                                  const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
-                                                  const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
-                                                  const float *__restrict__ scale, const float *__restrict__ zp,
-                                                  float *__restrict__ cbar) {
-    const int p = blockIdx.x, i = threadIdx.x, n = NT;
-    const int k = k_in[p], r = r_in[p];
-    if (i >= n) return;
-    for (int s = 0; s < n_out; ++s) {
-        const int t = slot_task[(size_t)p * n_out + s];
-        float acc = 0.f;
-        if (i < r && task_map[(size_t)p * n_out + s] >= 0 && (unsigned)t < (unsigned)n)
-            acc = __fadd_rn(acc, __fmul_rn(task_coeff(p, t, i, n, k, stages, chigh, codes, scale, zp), 1.f));
-        cbar[((size_t)p * n_out + s) * n + i] = acc;
-    }
-}
-
-// bit j: slot j of the parameter is a live task of the store (wave-uniform; copy of ties_live_mask)
-__device__ __forceinline__ unsigned emr_live_mask(const int32_t *__restrict__ st, const int32_t *__restrict__ tm,
-                                                  int n_out, int n, int T, int lane) {
-    const int j = lane < n_out ? lane : 0;
-    return (unsigned)__ballot(lane < n_out && (unsigned)tm[j] < (unsigned)T && (unsigned)st[j] < (unsigned)n);
-}
-
 // ------------------------------------------------------------------------------------ the LDS beyond the streaming carve
-// IMG [nop][IW] the block's agree bits per slot, laid out as TallLds lays them out: word 0 and word IW - 1 stay 0, words
-// 1 .. RB / 32 hold rows 0 .. RB - 1, least significant bit first | SLOT [T] the slot of every store task, -1 = the
+// IMG [nop][IW] the block's agree bits per slot (MaskImage) | SLOT [T] the slot of every store task, -1 = the
 // parameter has none | one word of alignment slack | AB, the fp64 partials of A (w = 0) and B (w = 1).  Up to CELLS slots:
 // [2][nop][64], lane l's own cell of slot j at [(w * nop + j) * 64 + l] (8 KB at 8 slots: the VGPRs, not the LDS, bound
 // the waves per SIMD).  Above: [2][nop], one cell per slot that lane 0 adds the wave's sum of a block to -- per-lane cells
 // (24 KB at 24 slots) left one wave per SIMD where k_tall_consensus runs four, and the kernel took 2.7 times its time.
-template <int RPL> struct EmrLds {
-    static constexpr int IW = 2 * RPL + 2;      // words of one slot's image
-    static constexpr int NW = 2 * RPL + 1;      // stream words a block's bit range can touch
+template <int RPL> struct EmrLds : MaskImage<RPL> {
     static constexpr int CELLS = 8;             // slots up to which every lane keeps its own cells
     __host__ __device__ static constexpr int ab_doubles(int nop) { return nop <= CELLS ? 2 * nop * 64 : 2 * nop; }
-    __host__ __device__ static constexpr int words(int nop, int T) { return nop * IW + T + 1 + 2 * ab_doubles(nop); }
+    __host__ __device__ static constexpr int words(int nop, int T) {
+        return nop * MaskImage<RPL>::IW + T + 1 + 2 * ab_doubles(nop);
+    }
 };
 
 // the sum of a wave's 64 values by the xor butterfly (32, 16, .. 1): both partners of a step add the same two numbers, so
@@ -101,7 +65,7 @@ __global__ __launch_bounds__(64) void k_emr_elect(
     using L = StreamLds<U16, RPL, false>;
     using X = EmrLds<RPL>;
     using TU = typename Geo::T;
-    constexpr int ES = Geo::ES, RB = Geo::RB, IW = X::IW, NW = X::NW;
+    constexpr int ES = Geo::ES, RB = Geo::RB, IW = X::IW;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const int lane = threadIdx.x, n = NT;
     const int nop = (n_out + TG - 1) / TG * TG;
@@ -122,7 +86,7 @@ __global__ __launch_bounds__(64) void k_emr_elect(
     }
     mg_gfloat_w *gout = (mg_gfloat_w *)uni_ptrs[p];      // NULL: the parameter's masks and sums only
     const int32_t *tm = task_map + (size_t)p * n_out;
-    const unsigned live = emr_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
+    const unsigned live = store_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
     const int k = uv.k, nl = uv.nl;
     const int64_t bit_first = bit_base[p];      // the stream bit of the parameter's row 0
     stage_coeffs(C, cbar + (size_t)p * n_out * n, n, n_out, nop, lane);
@@ -199,7 +163,7 @@ __global__ __launch_bounds__(64) void k_emr_elect(
                     const bool in = 64 * m + lane < rows_blk;
                     const bool set = (ssum[m] > 0.f && x > 0.f) || (ssum[m] < 0.f && x < 0.f);
                     if (set && ax > eps[m]) eps[m] = ax;
-                    const emr_u64 bal = __ballot(set && in);
+                    const store_u64 bal = __ballot(set && in);
                     if (lane < 2) IMG[(g0 + s) * IW + 1 + 2 * m + lane] = (unsigned)(bal >> (32 * lane));
                     if (in) a += (double)ax;
                 }
@@ -234,28 +198,8 @@ __global__ __launch_bounds__(64) void k_emr_elect(
             const float res = ssum[m] < 0.f ? -eps[m] : eps[m];
             if (64 * m + lane < rows_blk && gout) gout[rb + 64 * m + lane] = res;
         }
-        // ---- the block's stream words (as in k_tall_consensus)
-        {
-            const int64_t b0 = bit_first + rb, b1 = b0 + rows_blk;      // the block's bit range [b0, b1)
-            const int64_t w0 = b0 >> 5;
-            const int sh = (int)(b0 & 31);
-            const int nw = (int)(((b1 - 1) >> 5) - w0) + 1;      // <= NW
-            for (int e = lane; e < nop * NW; e += 64) {
-                const int j = e / NW, wi = e % NW;
-                if (j >= n_out || !((live >> j) & 1u) || wi >= nw) continue;
-                // stream bits 32 (w0 + wi) + i, i = 0 .. 31, are rows 32 wi + i - sh of the block
-                const emr_u64 pair = ((emr_u64)IMG[j * IW + wi + 1] << 32) | IMG[j * IW + wi];
-                const unsigned x = (unsigned)(pair >> (32 - sh));
-                // bit i -> bit 7 - (i & 7) of byte i >> 3 of a little-endian word
-                const unsigned word = __builtin_bswap32(__brev(x));
-                emr_gu32 *dst = (emr_gu32 *)mask_ptrs[tm[j]] + (w0 + wi);
-                const bool whole = 32 * (w0 + wi) >= b0 && 32 * (w0 + wi) + 32 <= b1;
-                if (whole)
-                    *dst = word;
-                else if (word)
-                    __hip_atomic_fetch_or(dst, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        // ---- the block's stream words
+        store_mask_words<RPL>(IMG, live, tm, n_out, nop, mask_ptrs, bit_first + rb, rows_blk, lane);
         lds_fence();      // the basis rows and the bit image are rewritten next
     }
     // ---- the unit's sums: lane e = (sum w, store task g) adds the 64 cells of the task's slot, cell e first, or takes
@@ -362,7 +306,7 @@ __global__ __launch_bounds__(EMR_APPLY_THREADS) void k_emr_apply(int P, const in
                 const int bl = (int)(Bw & 31) + 4 * lane;      // the lane's first bit, counted from bit 0 of word w0
                 const unsigned wl = (unsigned)__shfl((int)word, bl >> 5, 64);
                 const unsigned wh = (unsigned)__shfl((int)word, (bl >> 5) + 1, 64);
-                const unsigned bits = (unsigned)(((((emr_u64)wh) << 32) | wl) >> (bl & 31)) & 15u;
+                const unsigned bits = (unsigned)(((((store_u64)wh) << 32) | wl) >> (bl & 31)) & 15u;
                 const int64_t r = rw + 4 * lane;
                 if (r >= b) continue;
                 if (vec && r >= a && r + 4 <= b) {
@@ -405,41 +349,12 @@ extern "C" int64_t svdq_emr_work_bytes(const svdq_plan *pl, int32_t n_out, int32
     return emr_coeff_bytes(pl, n_out) + svdq_align_up((int64_t)pl->n_units * 2 * n_tasks * 8, 256);
 }
 
-// the live tasks' coefficients, then `launch` with the compiled-in basis type, task group and rows per lane (copy of
-// ties_stream)
-template <typename F>
-static int emr_stream(const char *who, const svdq_plan *pl, const void *small, const int32_t *slot_task,
-                      const int32_t *task_map, int n_out, float *cbar, hipStream_t st, F &&launch) {
-    const SmallView sv = small_view(pl->small, small);
-    hipLaunchKernelGGL(k_emr_coeff, dim3(pl->n_params), dim3(64), 0, st, pl->n_tasks, pl->cfg.rtvq_stages, n_out,
-                       slot_task, task_map, sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, cbar);
-    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
-    const int rpl = pl->n_tasks <= 16 ? 4 : 2;
-    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
-        return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
-            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
-                launch(f16_c, tg_c, rpl_c, sv, (n_out + tg - 1) / tg * tg);
-                return true;
-            });
-        });
-    });
-    return svdq_launch_status(ok, who);
-}
-
 extern "C" int svdq_plan_emr_elect(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
                                    const float *mean, const int32_t *slot_task, const int32_t *task_map, int32_t n_out,
                                    int32_t n_tasks, const int64_t *bit_base, const void *uni_ptrs, const void *mask_ptrs,
                                    void *state, void *work, void *stream) {
     const char *who = "svdq_plan_emr_elect";
-    if (!pl || !small || !basis || !slot_task || !task_map || !state || !work) {
-        svdq_set_error("%s: plan, small, basis, slot_task, task_map, state and work are required", who);
-        return SVDQ_EINVAL;
-    }
-    if (n_out < 1 || n_out > SVDQ_MAX_TASKS || n_tasks < 1 || n_tasks > SVDQ_MAX_TASKS) {
-        svdq_set_error("%s: n_out and n_tasks must be in [1, %d], got %d and %d", who, SVDQ_MAX_TASKS, n_out, n_tasks);
-        return SVDQ_EINVAL;
-    }
-    if (svdq_refuse_no_mean(who, pl, mean)) return SVDQ_EINVAL;
+    if (int rc = store_args_ok(who, pl, small, basis, mean, slot_task, task_map, n_out, n_tasks, state, work)) return rc;
     if (!bit_base || !uni_ptrs || !mask_ptrs) {
         svdq_set_error("%s: bit_base, uni_ptrs and mask_ptrs are required", who);
         return SVDQ_EINVAL;
@@ -452,7 +367,7 @@ extern "C" int svdq_plan_emr_elect(const svdq_plan *pl, const int64_t *rows_dev,
     double *table = reinterpret_cast<double *>(reinterpret_cast<uint8_t *>(work) + emr_coeff_bytes(pl, n_out));
     auto up = reinterpret_cast<float *const *>(uni_ptrs);
     auto mp = reinterpret_cast<uint32_t *const *>(mask_ptrs);
-    const int rc = emr_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
+    const int rc = store_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
                               [&](auto f16_c, auto tg_c, auto rpl_c, const SmallView &sv, int nop) {
                                   constexpr bool F16 = f16_c;
                                   constexpr int TG = tg_c, RPL = rpl_c;

@@ -9,7 +9,8 @@
 // fma_chains + task_value unchanged, so every pass sees the bits reconstruct_task_vectors writes -- and no task model is
 // ever written.
 //
-//   k_ties_coeff        the live tasks' coefficients per parameter, in the order of the store's task list
+//   k_store_coeff       the live tasks' coefficients per parameter, in the order of the store's task list
+//                       (svdq_store_values.hip, launched by store_stream)
 //   k_ties_hist         one digit of the radix selection of tau_t (the j-th smallest |v_t| over the whole store): the
 //                       magnitudes whose upper bits equal the task's prefix so far are counted per digit value in an LDS
 //                       histogram, flushed once per unit into the store's [T][256] table with integer atomics
@@ -20,11 +21,7 @@
 // pattern of tau_t) | rank [T] (1-based from below among the candidates left) | kept [T] | rows with kept values of both
 // signs | rows with nothing kept.  Integer counts only: no result depends on the order the units arrive in.
 
-#include "svdq_common.h"
-#include "svdq_dispatch.h"
-#include "svdq_merge_stream.h"
-#include "svdq_small_view.h"
-#include "svdq_store_pass.h"
+#include "svdq_store_values.h"
 
 #define TIES_BINS 256
 #define TIES_DIGIT_BITS 8
@@ -37,36 +34,6 @@ __host__ __device__ constexpr int64_t ties_conflict_off(int T) { return ties_kep
 __host__ __device__ constexpr int64_t ties_empty_off(int T) { return ties_conflict_off(T) + 1; }
 __host__ __device__ constexpr int64_t ties_words(int T) { return ties_empty_off(T) + 1; }
 
-typedef unsigned long long ties_u64;
-
-// ------------------------------------------------------------------------------------ coefficients
-// cbar [P][n_out][N]: slot j of parameter p holds the coefficients of plan task slot_task[p][j] exactly as k_task_coeff
-// (svdq_merge.hip) leaves them (0 + c * 1, rounded as there); a slot whose task_map entry is < 0 holds zeros.
-__global__ __launch_bounds__(64) void k_ties_coeff(int NT, int stages, int n_out, const int32_t *__restrict__ slot_task,
-                                                   const int32_t *__restrict__ task_map,
-                                                   const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
-                                                   const uint16_t *__restrict__ chigh, const uint8_t *__restrict__ codes,
-                                                   const float *__restrict__ scale, const float *__restrict__ zp,
-                                                   float *__restrict__ cbar) {
-    const int p = blockIdx.x, i = threadIdx.x, n = NT;
-    const int k = k_in[p], r = r_in[p];
-    if (i >= n) return;
-    for (int s = 0; s < n_out; ++s) {
-        const int t = slot_task[(size_t)p * n_out + s];
-        float acc = 0.f;
-        if (i < r && task_map[(size_t)p * n_out + s] >= 0 && (unsigned)t < (unsigned)n)
-            acc = __fadd_rn(acc, __fmul_rn(task_coeff(p, t, i, n, k, stages, chigh, codes, scale, zp), 1.f));
-        cbar[((size_t)p * n_out + s) * n + i] = acc;
-    }
-}
-
-// bit j: slot j of the parameter is a live task of the store (wave-uniform)
-__device__ __forceinline__ unsigned ties_live_mask(const int32_t *__restrict__ st, const int32_t *__restrict__ tm,
-                                                   int n_out, int n, int T, int lane) {
-    const int j = lane < n_out ? lane : 0;
-    return (unsigned)__ballot(lane < n_out && (unsigned)tm[j] < (unsigned)T && (unsigned)st[j] < (unsigned)n);
-}
-
 // ------------------------------------------------------------------------------------ one digit of the selection
 // LDS beyond the streaming carve: H [nop][256] uint32 (a unit has fewer than 2^31 rows).
 template <bool U16, int TG, int RPL>
@@ -76,7 +43,7 @@ __global__ __launch_bounds__(64) void k_ties_hist(const SvdqParam *__restrict__ 
                                                   const int32_t *__restrict__ task_map,
                                                   const int32_t *__restrict__ k_in, const int32_t *__restrict__ r_in,
                                                   const uint8_t *__restrict__ basis, const float *__restrict__ meanbuf,
-                                                  const float *__restrict__ cbar, int digit, ties_u64 *__restrict__ state) {
+                                                  const float *__restrict__ cbar, int digit, store_u64 *__restrict__ state) {
     using G = StreamGeom<U16, RPL>;
     using L = StreamLds<U16, RPL, false>;
     using TU = typename G::T;
@@ -94,7 +61,7 @@ __global__ __launch_bounds__(64) void k_ties_hist(const SvdqParam *__restrict__ 
     if (r_end > uv.D) r_end = uv.D;
     if (r_begin >= r_end) return;
     const int32_t *tm = task_map + (size_t)p * n_out;
-    const unsigned live = ties_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
+    const unsigned live = store_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
     if (!live) return;
     const int k = uv.k, nl = uv.nl;
     stage_coeffs(C, cbar + (size_t)p * n_out * n, n, n_out, nop, lane);
@@ -137,7 +104,7 @@ __global__ __launch_bounds__(64) void k_ties_hist(const SvdqParam *__restrict__ 
                     const bool in = 64 * m + lane < rows_blk && ((mag ^ prefix) & upper) == 0u;
                     const unsigned d = (mag >> shift) & (TIES_BINS - 1);
                     // the rows of a wave mostly share the upper digits: one LDS add for the wave when they all do
-                    const ties_u64 act = __ballot(in);
+                    const store_u64 act = __ballot(in);
                     if (!act) continue;      // wave-uniform
                     const unsigned dl = (unsigned)__shfl((int)d, (int)__ffsll((long long)act) - 1);
                     if (__ballot(in && d != dl) == 0) {
@@ -154,29 +121,29 @@ __global__ __launch_bounds__(64) void k_ties_hist(const SvdqParam *__restrict__ 
     for (int e = lane; e < nop * TIES_BINS; e += 64) {
         const int j = e / TIES_BINS;
         if (j < n_out && ((live >> j) & 1u) && H[e])
-            atomicAdd(&state[(size_t)tm[j] * TIES_BINS + (e % TIES_BINS)], (ties_u64)H[e]);
+            atomicAdd(&state[(size_t)tm[j] * TIES_BINS + (e % TIES_BINS)], (store_u64)H[e]);
     }
 }
 
 // ------------------------------------------------------------------------------------ the digit's bin per task
 // rank0: the wanted rank j (1-based from below) over all D rows, set at digit 0.  zeros [T]: the rows of the parameters
 // a task lacks -- implicit values 0, in bin 0 of every digit while the prefix is all zero.
-__global__ __launch_bounds__(64) void k_ties_select_step(ties_u64 *__restrict__ state, int T, int digit, int64_t rank0,
+__global__ __launch_bounds__(64) void k_ties_select_step(store_u64 *__restrict__ state, int T, int digit, int64_t rank0,
                                                          const int64_t *__restrict__ zeros) {
     const int t = threadIdx.x;
     if (t >= T) return;
-    ties_u64 *h = state + (size_t)t * TIES_BINS;
+    store_u64 *h = state + (size_t)t * TIES_BINS;
     const unsigned prefix = digit ? (unsigned)state[ties_prefix_off(T) + t] : 0u;
-    const ties_u64 rank = digit ? state[ties_rank_off(T) + t] : (ties_u64)rank0;
-    const ties_u64 z = (zeros && prefix == 0u) ? (ties_u64)zeros[t] : 0ull;
-    ties_u64 total = z;
+    const store_u64 rank = digit ? state[ties_rank_off(T) + t] : (store_u64)rank0;
+    const store_u64 z = (zeros && prefix == 0u) ? (store_u64)zeros[t] : 0ull;
+    store_u64 total = z;
     for (int b = 0; b < TIES_BINS; ++b) total += h[b];
     // from the top: the rank counted from above among the candidates
-    ties_u64 rtop = total >= rank ? total - rank + 1 : 1, above = 0;
+    store_u64 rtop = total >= rank ? total - rank + 1 : 1, above = 0;
     int pick = 0;
-    ties_u64 inbin = h[0] + z;
+    store_u64 inbin = h[0] + z;
     for (int b = TIES_BINS - 1; b >= 0; --b) {
-        const ties_u64 c = h[b] + (b == 0 ? z : 0ull);
+        const store_u64 c = h[b] + (b == 0 ? z : 0ull);
         if (above + c >= rtop) {
             pick = b;
             inbin = c;
@@ -185,7 +152,7 @@ __global__ __launch_bounds__(64) void k_ties_select_step(ties_u64 *__restrict__ 
         above += c;
     }
     const int shift = 32 - TIES_DIGIT_BITS * (digit + 1);
-    state[ties_prefix_off(T) + t] = (ties_u64)(prefix | ((unsigned)pick << shift));
+    state[ties_prefix_off(T) + t] = (store_u64)(prefix | ((unsigned)pick << shift));
     state[ties_rank_off(T) + t] = inbin - (rtop - above) + 1;      // from below inside the bin
     for (int b = 0; b < TIES_BINS; ++b) h[b] = 0ull;
 }
@@ -201,7 +168,7 @@ __global__ __launch_bounds__(64) void k_ties_merge(const SvdqParam *__restrict__
                                                    const uint8_t *__restrict__ basis, const float *__restrict__ meanbuf,
                                                    const float *__restrict__ cbar, int merge_sum, float scaling,
                                                    const float *const *__restrict__ base_ptrs,
-                                                   float *const *__restrict__ out_ptrs, ties_u64 *__restrict__ state) {
+                                                   float *const *__restrict__ out_ptrs, store_u64 *__restrict__ state) {
     using G = StreamGeom<U16, RPL>;
     using L = StreamLds<U16, RPL, false>;
     using TU = typename G::T;
@@ -222,7 +189,7 @@ __global__ __launch_bounds__(64) void k_ties_merge(const SvdqParam *__restrict__
     mg_gfloat_w *gout = (mg_gfloat_w *)out_ptrs[p];
     if (!gout) return;
     const int32_t *tm = task_map + (size_t)p * n_out;
-    const unsigned live = ties_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
+    const unsigned live = store_live_mask(slot_task + (size_t)p * n_out, tm, n_out, n, T, lane);
     const int k = uv.k, nl = uv.nl;
     stage_coeffs(C, cbar + (size_t)p * n_out * n, n, n_out, nop, lane);
     for (int j = lane; j < nop; j += 64) {
@@ -234,7 +201,7 @@ __global__ __launch_bounds__(64) void k_ties_merge(const SvdqParam *__restrict__
     for (int j = 0; j < n_out; ++j)
         if (((live >> j) & 1u) && tm[j] == lane) lacks = false;
     const bool zero_kept = lacks && (unsigned)state[ties_prefix_off(T) + (lane < T ? lane : 0)] == 0u;
-    if (zero_kept) atomicAdd(&state[ties_kept_off(T) + lane], (ties_u64)(r_end - r_begin));
+    if (zero_kept) atomicAdd(&state[ties_kept_off(T) + lane], (store_u64)(r_end - r_begin));
     const bool any_zero_kept = __ballot(zero_kept) != 0;
     unsigned n_conflict = 0, n_empty = 0;      // wave-uniform
 
@@ -290,7 +257,7 @@ __global__ __launch_bounds__(64) void k_ties_merge(const SvdqParam *__restrict__
                 for (int m = 0; m < RPL; ++m) {
                     const bool kept = (kb[m] >> s) & 1u;
                     if (kept) ssum[m] = __fadd_rn(ssum[m], v[m][s]);
-                    const ties_u64 bal = __ballot(kept && 64 * m + lane < rows_blk);
+                    const store_u64 bal = __ballot(kept && 64 * m + lane < rows_blk);
                     if (bal && lane == 0) KC[g0 + s] += (unsigned)__popcll(bal);
                 }
             }
@@ -337,10 +304,10 @@ __global__ __launch_bounds__(64) void k_ties_merge(const SvdqParam *__restrict__
     // ---- one flush per unit
     lds_fence();
     for (int j = lane; j < n_out; j += 64)
-        if (((live >> j) & 1u) && KC[j]) atomicAdd(&state[ties_kept_off(T) + tm[j]], (ties_u64)KC[j]);
+        if (((live >> j) & 1u) && KC[j]) atomicAdd(&state[ties_kept_off(T) + tm[j]], (store_u64)KC[j]);
     if (lane == 0) {
-        if (n_conflict) atomicAdd(&state[ties_conflict_off(T)], (ties_u64)n_conflict);
-        if (n_empty) atomicAdd(&state[ties_empty_off(T)], (ties_u64)n_empty);
+        if (n_conflict) atomicAdd(&state[ties_conflict_off(T)], (store_u64)n_conflict);
+        if (n_empty) atomicAdd(&state[ties_empty_off(T)], (store_u64)n_empty);
     }
 }
 
@@ -350,45 +317,11 @@ extern "C" int64_t svdq_ties_work_bytes(int32_t n_tasks) {
     return svdq_align_up(ties_words(n_tasks) * 8, 256);
 }
 
-static int ties_args_ok(const char *who, const svdq_plan *pl, const void *small, const void *basis, const float *mean,
-                        const int32_t *slot_task, const int32_t *task_map, int32_t n_out, int32_t n_tasks,
-                        const void *state, const void *work) {
-    if (!pl || !small || !basis || !slot_task || !task_map || !state || !work) {
-        svdq_set_error("%s: plan, small, basis, slot_task, task_map, state and work are required", who);
-        return SVDQ_EINVAL;
-    }
-    if (n_out < 1 || n_out > SVDQ_MAX_TASKS || n_tasks < 1 || n_tasks > SVDQ_MAX_TASKS) {
-        svdq_set_error("%s: n_out and n_tasks must be in [1, %d], got %d and %d", who, SVDQ_MAX_TASKS, n_out, n_tasks);
-        return SVDQ_EINVAL;
-    }
-    return svdq_refuse_no_mean(who, pl, mean) ? SVDQ_EINVAL : SVDQ_OK;
-}
-
-// the live tasks' coefficients, then `launch` with the compiled-in basis type, task group and rows per lane
-template <typename F>
-static int ties_stream(const char *who, const svdq_plan *pl, const void *small, const int32_t *slot_task,
-                       const int32_t *task_map, int n_out, float *cbar, hipStream_t st, F &&launch) {
-    const SmallView sv = small_view(pl->small, small);
-    hipLaunchKernelGGL(k_ties_coeff, dim3(pl->n_params), dim3(64), 0, st, pl->n_tasks, pl->cfg.rtvq_stages, n_out,
-                       slot_task, task_map, sv.k, sv.r, sv.chigh, sv.codes, sv.scale, sv.zp, cbar);
-    const int tg = n_out == 1 ? 1 : (n_out <= 4 ? 4 : 8);      // tasks per pass over a block's LDS image
-    const int rpl = pl->n_tasks <= 16 ? 4 : 2;
-    const bool ok = svdq_dispatch_bool(pl->cfg.fp16 != 0, [&](auto f16_c) {
-        return svdq_dispatch_int<1, 4, 8>(tg, [&](auto tg_c) {
-            return svdq_dispatch_int<4, 2>(rpl, [&](auto rpl_c) {
-                launch(f16_c, tg_c, rpl_c, sv, (n_out + tg - 1) / tg * tg);
-                return true;
-            });
-        });
-    });
-    return svdq_launch_status(ok, who);
-}
-
 extern "C" int svdq_plan_ties_hist(const svdq_plan *pl, const int64_t *rows_dev, const void *small, const void *basis,
                                    const float *mean, const int32_t *slot_task, const int32_t *task_map, int32_t n_out,
                                    int32_t n_tasks, int32_t digit, void *state, void *work, void *stream) {
     const char *who = "svdq_plan_ties_hist";
-    if (int rc = ties_args_ok(who, pl, small, basis, mean, slot_task, task_map, n_out, n_tasks, state, work)) return rc;
+    if (int rc = store_args_ok(who, pl, small, basis, mean, slot_task, task_map, n_out, n_tasks, state, work)) return rc;
     if (digit < 0 || digit >= TIES_DIGITS) {
         svdq_set_error("%s: digit must be in [0, %d), got %d", who, TIES_DIGITS, digit);
         return SVDQ_EINVAL;
@@ -398,7 +331,7 @@ extern "C" int svdq_plan_ties_hist(const svdq_plan *pl, const int64_t *rows_dev,
     const uint8_t *bs = reinterpret_cast<const uint8_t *>(basis);
     const float *mn = pl->cfg.center ? mean : nullptr;
     float *cbar = reinterpret_cast<float *>(work);
-    return ties_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
+    return store_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
                        [&](auto f16_c, auto tg_c, auto rpl_c, const SmallView &sv, int nop) {
                            constexpr bool F16 = f16_c;
                            constexpr int TG = tg_c, RPL = rpl_c;
@@ -406,7 +339,7 @@ extern "C" int svdq_plan_ties_hist(const svdq_plan *pl, const int64_t *rows_dev,
                            hipLaunchKernelGGL((k_ties_hist<F16, TG, RPL>), dim3(pl->n_units), dim3(64),
                                               Plain::bytes(n, nop, nop * TIES_BINS), st, pl->d_params, pl->d_units,
                                               rows_dev, n, (int)n_out, (int)n_tasks, slot_task, task_map, sv.k, sv.r, bs,
-                                              mn, cbar, (int)digit, reinterpret_cast<ties_u64 *>(state));
+                                              mn, cbar, (int)digit, reinterpret_cast<store_u64 *>(state));
                        });
 }
 
@@ -429,7 +362,7 @@ extern "C" int svdq_ties_select_step(void *state, int32_t n_tasks, int32_t digit
         svdq_set_error("%s: rank must be >= 1, got %lld", who, (long long)rank);
         return SVDQ_EINVAL;
     }
-    hipLaunchKernelGGL(k_ties_select_step, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<ties_u64 *>(state),
+    hipLaunchKernelGGL(k_ties_select_step, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<store_u64 *>(state),
                        (int)n_tasks, (int)digit, rank, zeros_dev);
     return hipGetLastError() == hipSuccess ? SVDQ_OK : SVDQ_EHIP;
 }
@@ -439,7 +372,7 @@ extern "C" int svdq_plan_ties_merge(const svdq_plan *pl, const int64_t *rows_dev
                                     int32_t n_tasks, int32_t merge_sum, float scaling, const void *base_ptrs,
                                     const void *out_ptrs, void *state, void *work, void *stream) {
     const char *who = "svdq_plan_ties_merge";
-    if (int rc = ties_args_ok(who, pl, small, basis, mean, slot_task, task_map, n_out, n_tasks, state, work)) return rc;
+    if (int rc = store_args_ok(who, pl, small, basis, mean, slot_task, task_map, n_out, n_tasks, state, work)) return rc;
     if (!out_ptrs) {
         svdq_set_error("%s: out_ptrs is required", who);
         return SVDQ_EINVAL;
@@ -451,7 +384,7 @@ extern "C" int svdq_plan_ties_merge(const svdq_plan *pl, const int64_t *rows_dev
     float *cbar = reinterpret_cast<float *>(work);
     auto bp = reinterpret_cast<const float *const *>(base_ptrs);
     auto op = reinterpret_cast<float *const *>(out_ptrs);
-    return ties_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
+    return store_stream(who, pl, small, slot_task, task_map, (int)n_out, cbar, st,
                        [&](auto f16_c, auto tg_c, auto rpl_c, const SmallView &sv, int nop) {
                            constexpr bool F16 = f16_c;
                            constexpr int TG = tg_c, RPL = rpl_c;
@@ -459,6 +392,6 @@ extern "C" int svdq_plan_ties_merge(const svdq_plan *pl, const int64_t *rows_dev
                            hipLaunchKernelGGL((k_ties_merge<F16, TG, RPL>), dim3(pl->n_units), dim3(64),
                                               Plain::bytes(n, nop, 2 * nop), st, pl->d_params, pl->d_units, rows_dev, n,
                                               (int)n_out, (int)n_tasks, slot_task, task_map, sv.k, sv.r, bs, mn, cbar,
-                                              merge_sum ? 1 : 0, scaling, bp, op, reinterpret_cast<ties_u64 *>(state));
+                                              merge_sum ? 1 : 0, scaling, bp, op, reinterpret_cast<store_u64 *>(state));
                        });
 }

@@ -540,14 +540,9 @@ def reconstruct_task_vectors_masked(compressed_all: Dict[str, Dict[str, Dict]], 
     task) afterwards -- when ``masks[name]`` is the tensor the run compressed with, or, for adopted plans
     (``adopt_artifacts(..., masks=masks)``), a mask that selects exactly the stored rows; any other masked parameter
     keeps the compacted route.  Same bits either way."""
-    known = []
-    for per_task in compressed_all.values():
-        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
-                  if t not in known]
-    wanted = list(known) if tasks is None else list(tasks)
-    for t in wanted:
-        if t not in known:
-            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    wanted = None if tasks is None else list(tasks)      # the caller's order, repeats included
+    known, _ = _store_tasks(compressed_all, wanted)
+    wanted = list(known) if wanted is None else wanted
     dev = resolve_device(device)
     masks = masks or {}
     quantizer = RTVQQuantizer(num_bits=config.svd_low_bits, num_stages=config.svd_rtvq_stages)
@@ -639,6 +634,102 @@ def merge_with_clustering(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
     return merge_cluster_results(per_cluster, performance, device)
 
 
+def _store_tasks(compressed_all, tasks, who=None):
+    """(known, wanted): the task names of a store in first-seen order, and -- for the merge ``who`` -- the names it
+    merges: ``tasks`` (None = all) distinct and sorted, between 1 and MAX_TASKS of them.  ``who=None``: no merge,
+    ``wanted`` is None.  A name of ``tasks`` the store lacks raises the ValueError that lists what it holds."""
+    known = []
+    for per_task in compressed_all.values():
+        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
+                  if t not in known]
+    for t in (tasks if tasks is not None else []):
+        if t not in known:
+            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
+    if who is None:
+        return known, None
+    wanted = sorted(set(known if tasks is None else tasks))
+    if not 1 <= len(wanted) <= nat.MAX_TASKS:
+        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {len(wanted)}")
+    return known, wanted
+
+
+def _is_number(x, nonneg: bool = False) -> bool:
+    """A finite int or float, no bool; with ``nonneg`` also >= 0."""
+    import math
+    return (not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x) and not (nonneg and x < 0))
+
+
+def _as_fp32(values):
+    """(``values`` rounded to a float32 array, whether every entry stayed finite)."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        v32 = np.asarray(values, dtype=np.float64).astype(np.float32)
+    return v32, bool(np.isfinite(v32).all())
+
+
+def _slot_tables(P, entries, live, offsets=None):
+    """The host tables of one plan for a pass over every task's own values (pure numpy): slot_task [P][n_out] the plan
+    task of every slot, task_map [P][n_out] its store task (-1 = the slot is empty) -- per parameter the pairs of
+    ``live`` (``_ties_jobs``) in store order, n_out the most any parameter of ``entries`` has, at least 1 -- and an
+    int64 column [P] of ``offsets[name]`` (0 without: DARE's first global row, the first bit of a mask stream)."""
+    import numpy as np
+    n_out = max([len(live[name]) for name in entries.values()] + [1])
+    slot_task = np.zeros((P, n_out), dtype=np.int32)
+    task_map = np.full((P, n_out), -1, dtype=np.int32)
+    column = np.zeros(P, dtype=np.int64)
+    for i, name in entries.items():
+        for j, (g, q) in enumerate(live[name]):
+            task_map[i, j], slot_task[i, j] = g, q
+        if offsets is not None:
+            column[i] = offsets.get(name, 0)
+    return slot_task, task_map, column
+
+
+def _stage_base(name, count, base_state_dict, device, keep, later) -> int:
+    """The address of ``base_state_dict[name]`` for a launch to add: a fp32 base of ``count`` elements, made a contiguous
+    device vector that ``keep`` holds.  0 without a base, and for any other base -- that one goes to ``later``, to be
+    added to the result in its own arithmetic (``_finish_output``)."""
+    b = base_state_dict.get(name) if base_state_dict is not None else None
+    if b is not None and b.dtype is torch.float32 and b.numel() == count:
+        keep.append(prepare_vector(b, device))
+        return keep[-1].data_ptr()
+    if b is not None:
+        later[name] = b
+    return 0
+
+
+def _plan_outputs(plan, entries, rows, original_shapes, base_state_dict, out, later):
+    """The device side of one plan's launch: a fresh fp32 output per parameter of ``entries`` into ``out`` (zeros in its
+    shape for a parameter without rows; ``out=None``: no outputs at all), the bases staged (``_stage_base``).  Returns
+    (out_tab or None, base_tab or None, rows_dev, the tensors the launch needs kept alive)."""
+    import numpy as np
+    P = plan.P
+    rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+    if out is None:
+        return None, None, rows_dev, []
+    out_tab = np.zeros(P, dtype=np.int64)
+    base_tab = np.zeros(P, dtype=np.int64)
+    keep = []
+    for i, name in entries.items():
+        if rows[name] <= 0:
+            out[name] = torch.zeros(original_shapes[name], device=plan.device)
+            continue
+        res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
+        out_tab[i] = res.data_ptr()
+        base_tab[i] = _stage_base(name, rows[name], base_state_dict, plan.device, keep, later)
+    return (torch.from_numpy(out_tab).to(plan.device),
+            torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None, rows_dev, keep)
+
+
+def _finish_output(res, shape, name, later, device):
+    """A launch's flat output as the caller gets it: in ``shape``, plus the base that could not go into the launch, on
+    the CPU when ``device`` asks for it."""
+    res = res.view(shape)
+    if name in later:
+        res = later[name].to(res.device) + res
+    return res.cpu() if wants_cpu(device) else res
+
+
 def _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who="ties_merge_parameters", what="the TIES merge"):
     """The plans behind a TIES (or DARE: ``who`` / ``what`` name the caller in the messages) merge: {id(plan): (batch,
     {entry index: name})}, the rows of every parameter and, per parameter, the (store task, plan task) pairs of the
@@ -690,17 +781,8 @@ def ties_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
         raise ValueError(f"density must be in (0, 1], got {density!r}")
     if merge_func not in ("mean", "sum"):
         raise ValueError(f"merge_func must be 'mean' or 'sum', got {merge_func!r}")
-    known = []
-    for per_task in compressed_all.values():
-        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
-                  if t not in known]
-    for t in (tasks if tasks is not None else []):
-        if t not in known:
-            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
-    wanted = sorted(set(known if tasks is None else tasks))
+    _, wanted = _store_tasks(compressed_all, tasks, "ties_merge_parameters")
     T = len(wanted)
-    if not 1 <= T <= nat.MAX_TASKS:
-        raise ValueError(f"ties_merge_parameters: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
     names = sorted(compressed_all.keys())
     jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes)      # refusals before device work
     dev = resolve_device(device)
@@ -719,30 +801,12 @@ def ties_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
         calls, keep = [], []
         for batch, entries in jobs.values():
             plan = batch.plan
-            P = plan.P
-            n_out = max([len(live[name]) for name in entries.values()] + [1])
-            slot_task = np.zeros((P, n_out), dtype=np.int32)
-            task_map = np.full((P, n_out), -1, dtype=np.int32)
-            out_tab = np.zeros(P, dtype=np.int64)
-            base_tab = np.zeros(P, dtype=np.int64)
-            for i, name in entries.items():
-                for j, (g, q) in enumerate(live[name]):
-                    task_map[i, j], slot_task[i, j] = g, q
-                if rows[name] <= 0:
-                    out[name] = torch.zeros(original_shapes[name], device=plan.device)
-                    continue
-                res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
-                out_tab[i] = res.data_ptr()
-                b = base_state_dict.get(name) if base_state_dict is not None else None
-                if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
-                    keep.append(prepare_vector(b, plan.device))
-                    base_tab[i] = keep[-1].data_ptr()
-                elif b is not None:
-                    later[name] = b
-            rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+            slot_task, task_map, _ = _slot_tables(plan.P, entries, live)
+            out_tab, base_tab, rows_dev, kept = _plan_outputs(plan, entries, rows, original_shapes, base_state_dict, out,
+                                                              later)
+            keep += kept
             calls.append((plan, torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device),
-                          rows_dev, torch.from_numpy(out_tab).to(plan.device),
-                          torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None))
+                          rows_dev, out_tab, base_tab))
         state = ties_thresholds([c[:4] for c in calls], T, rank, torch.from_numpy(zeros).to(dev), device=dev)
         for plan, slot_task, task_map, rows_dev, out_tab, base_tab in calls:
             plan.ties_merge(slot_task, task_map, T, state.table, out_tab, merge_func=merge_func, scaling=scaling,
@@ -754,10 +818,7 @@ def ties_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
             stats["kept"] = {t: int(host[2 * T + g]) for g, t in enumerate(wanted)}
             stats["sign_conflict_rows"], stats["empty_rows"] = int(host[3 * T]), int(host[3 * T + 1])
         for name in names:
-            res = out[name].view(original_shapes[name])
-            if name in later:
-                res = later[name].to(res.device) + res
-            out[name] = res.cpu() if wants_cpu(device) else res
+            out[name] = _finish_output(out[name], original_shapes[name], name, later, device)
     return (out, stats) if return_stats else out
 
 
@@ -802,17 +863,8 @@ def dare_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
     import numpy as np
     who = "dare_merge_parameters"
     thr, q = _dare_arguments(drop_rate, seed)
-    known = []
-    for per_task in compressed_all.values():
-        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
-                  if t not in known]
-    for t in (tasks if tasks is not None else []):
-        if t not in known:
-            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
-    wanted = sorted(set(known if tasks is None else tasks))
+    _, wanted = _store_tasks(compressed_all, tasks, who)
     T = len(wanted)
-    if not 1 <= T <= nat.MAX_TASKS:
-        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
     if weights is None:
         w64 = [1.0] * T
     else:
@@ -823,7 +875,7 @@ def dare_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
             w = weights.get(t)
             if w is None:
                 raise ValueError(f"{who}: the weight of task {t!r} is missing")
-            if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w):
+            if not _is_number(w):
                 raise ValueError(f"{who}: the weight of task {t!r} is not a finite number: {w!r}")
             w64.append(float(w))
     if normalize:
@@ -831,9 +883,8 @@ def dare_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
         if not (math.isfinite(total) and total != 0.0):
             raise ValueError(f"{who}: normalize=True needs weights with a non-zero sum, got {total!r}")
         w64 = [w / total for w in w64]
-    with np.errstate(over="ignore"):
-        w32 = np.asarray(w64, dtype=np.float64).astype(np.float32)
-    if not np.isfinite(w32).all():
+    w32, ok = _as_fp32(w64)
+    if not ok:
         raise ValueError(f"{who}: a weight is not finite in fp32: {w32.tolist()}")
     names = sorted(compressed_all.keys())
     jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
@@ -856,43 +907,19 @@ def dare_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
         keep = []
         for batch, entries in jobs.values():
             plan = batch.plan
-            P = plan.P
-            n_out = max([len(live[name]) for name in entries.values()] + [1])
-            slot_task = np.zeros((P, n_out), dtype=np.int32)
-            task_map = np.full((P, n_out), -1, dtype=np.int32)
-            out_tab = np.zeros(P, dtype=np.int64)
-            base_tab = np.zeros(P, dtype=np.int64)
-            base_rows = np.zeros(P, dtype=np.int64)
-            for i, name in entries.items():
-                for j, (g, pq) in enumerate(live[name]):
-                    task_map[i, j], slot_task[i, j] = g, pq
-                base_rows[i] = row_base[name]
-                if rows[name] <= 0:
-                    out[name] = torch.zeros(original_shapes[name], device=plan.device)
-                    continue
-                res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
-                out_tab[i] = res.data_ptr()
-                b = base_state_dict.get(name) if base_state_dict is not None else None
-                if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
-                    keep.append(prepare_vector(b, plan.device))
-                    base_tab[i] = keep[-1].data_ptr()
-                elif b is not None:
-                    later[name] = b
-            rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+            slot_task, task_map, base_rows = _slot_tables(plan.P, entries, live, row_base)
+            out_tab, base_tab, rows_dev, kept = _plan_outputs(plan, entries, rows, original_shapes, base_state_dict, out,
+                                                              later)
+            keep += kept
             plan.dare_merge(torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device), T,
-                            torch.from_numpy(base_rows).to(plan.device), w_dev, state,
-                            torch.from_numpy(out_tab).to(plan.device), seed=seed, drop_threshold=thr,
-                            keep_scale=q if rescale else 0.0, scaling=scaling,
-                            base_table=torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None,
+                            torch.from_numpy(base_rows).to(plan.device), w_dev, state, out_tab, seed=seed,
+                            drop_threshold=thr, keep_scale=q if rescale else 0.0, scaling=scaling, base_table=base_tab,
                             rows_dev=rows_dev)
         if return_stats:
             host = state.cpu().numpy()
             stats["kept"] = {t: int(host[g]) for g, t in enumerate(wanted)}
         for name in names:
-            res = out[name].view(original_shapes[name])
-            if name in later:
-                res = later[name].to(res.device) + res
-            out[name] = res.cpu() if wants_cpu(device) else res
+            out[name] = _finish_output(out[name], original_shapes[name], name, later, device)
     return (out, stats) if return_stats else out
 
 
@@ -900,12 +927,10 @@ def _tall_arguments(who, tall_lambda, k, wanted, check_k=True):
     """(float32 lambdas [T] in the order of ``wanted``, k) of a TALL / consensus call; the named ValueError for what lies
     outside the definition: a lambda that is no finite number >= 0 (in fp32), a mapping that misses a merged task, a k
     that is no integer in [0, T] (``check_k=False``: masks only, k is not looked at)."""
-    import math
-    import numpy as np
     T = len(wanted)
 
     def number(x, what):
-        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0:
+        if not _is_number(x, nonneg=True):
             raise ValueError(f"{who}: {what} must be a finite number >= 0, got {x!r}")
         return float(x)
     if hasattr(tall_lambda, "get"):
@@ -916,9 +941,8 @@ def _tall_arguments(who, tall_lambda, k, wanted, check_k=True):
             lam.append(number(tall_lambda.get(t), f"the tall_lambda of task {t!r}"))
     else:
         lam = [number(tall_lambda, "tall_lambda")] * T
-    with np.errstate(over="ignore"):
-        lam32 = np.asarray(lam, dtype=np.float64).astype(np.float32)
-    if not np.isfinite(lam32).all():
+    lam32, ok = _as_fp32(lam)
+    if not ok:
         raise ValueError(f"{who}: a tall_lambda is not finite in fp32: {lam32.tolist()}")
     if check_k and (isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= T):
         raise ValueError(f"{who}: k must be an integer in [0, {T}] (the merged tasks), got {k!r}")
@@ -929,89 +953,35 @@ def _tall_run(who, compressed_all, bases, original_shapes, tall_lambda, k, scali
               reference_state_dict, remove_keys, want_merge, want_masks, device):
     """The launches behind ``consensus_merge_parameters`` and ``tall_masks_from_store``: (merged or None, masks or None,
     stats).  Every refusal is raised before device work."""
-    import numpy as np
-    known = []
-    for per_task in compressed_all.values():
-        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
-                  if t not in known]
-    for t in (tasks if tasks is not None else []):
-        if t not in known:
-            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
-    wanted = sorted(set(known if tasks is None else tasks))
+    _, wanted = _store_tasks(compressed_all, tasks, who)
     T = len(wanted)
-    if not 1 <= T <= nat.MAX_TASKS:
-        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
     lam32, k = _tall_arguments(who, tall_lambda, k, wanted, check_k=want_merge)
     names = sorted(compressed_all.keys())
     jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
                                   "the consensus merge" if want_merge else "the TALL mask")      # before device work
-    # the streams' layout: the sorted keys of the reference minus remove_keys, each at the bit after the one before it
-    bit_base, total_bits = {}, 0
-    if want_masks:
-        skip = set(remove_keys or [])
-        if reference_state_dict is None:
-            sizes = {n: rows[n] for n in names if n not in skip}
-        else:
-            sizes = {key: int(x.numel()) for key, x in reference_state_dict.items() if key not in skip}
-        for name in names:
-            if name not in sizes:
-                raise ValueError(f"{who}: parameter {name!r} of the store has no place in the mask streams (it is not a "
-                                 f"key of reference_state_dict, or remove_keys names it)")
-            if sizes[name] != rows[name]:
-                raise ValueError(f"{who}: reference_state_dict[{name!r}] has {sizes[name]} elements, the store holds "
-                                 f"{rows[name]} rows for it")
-        for key in sorted(sizes):
-            bit_base[key] = total_bits
-            total_bits += sizes[key]
+    bit_base, total_bits = (_mask_stream_layout(who, names, rows, reference_state_dict, remove_keys) if want_masks
+                            else ({}, 0))
     dev = resolve_device(device)
     D = sum(rows.values())
     out, later = ({}, {}) if want_merge else (None, {})
     stats = {"active": {t: 0 for t in wanted}, "agreement": [D] + [0] * T, "rows": D}
-    n_bytes, n_words = (total_bits + 7) // 8, (total_bits + 31) // 32
     with torch.cuda.device(dev):
-        streams = torch.zeros((T, max(n_words, 1)), dtype=torch.int32, device=dev) if want_masks else None
+        streams, mask_tab = _new_mask_streams(T, total_bits, dev) if want_masks else (None, None)
         if D > 0:
             need = int(nat.lib().svdq_tall_work_bytes(T))
             state = torch.zeros(need // 8, dtype=torch.int64, device=dev)
             lam_dev = torch.from_numpy(lam32).to(dev)
-            mask_tab = None
-            if want_masks:
-                mask_tab = torch.tensor([streams.data_ptr() + 4 * g * streams.shape[1] for g in range(T)],
-                                        dtype=torch.int64, device=dev)
             keep = []
             for batch, entries in jobs.values():
                 plan = batch.plan
-                P = plan.P
-                n_out = max([len(live[name]) for name in entries.values()] + [1])
-                slot_task = np.zeros((P, n_out), dtype=np.int32)
-                task_map = np.full((P, n_out), -1, dtype=np.int32)
-                out_tab = np.zeros(P, dtype=np.int64)
-                base_tab = np.zeros(P, dtype=np.int64)
-                bits = np.zeros(P, dtype=np.int64)
-                for i, name in entries.items():
-                    for j, (g, pq) in enumerate(live[name]):
-                        task_map[i, j], slot_task[i, j] = g, pq
-                    bits[i] = bit_base.get(name, 0)
-                    if not want_merge:
-                        continue
-                    if rows[name] <= 0:
-                        out[name] = torch.zeros(original_shapes[name], device=plan.device)
-                        continue
-                    res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
-                    out_tab[i] = res.data_ptr()
-                    b = base_state_dict.get(name) if base_state_dict is not None else None
-                    if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
-                        keep.append(prepare_vector(b, plan.device))
-                        base_tab[i] = keep[-1].data_ptr()
-                    elif b is not None:
-                        later[name] = b
-                rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+                slot_task, task_map, bits = _slot_tables(plan.P, entries, live, bit_base)
+                out_tab, base_tab, rows_dev, kept = _plan_outputs(plan, entries, rows, original_shapes, base_state_dict,
+                                                                  out, later)
+                keep += kept
                 plan.tall_consensus(torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device),
-                                    T, torch.from_numpy(bits).to(plan.device), lam_dev, state,
-                                    out_table=torch.from_numpy(out_tab).to(plan.device) if want_merge else None,
+                                    T, torch.from_numpy(bits).to(plan.device), lam_dev, state, out_table=out_tab,
                                     mask_table=mask_tab, min_agree=k if want_merge else 0, scaling=scaling,
-                                    base_table=torch.from_numpy(base_tab).to(plan.device) if base_tab.any() else None,
-                                    rows_dev=rows_dev)
+                                    base_table=base_tab, rows_dev=rows_dev)
             host = state.cpu().numpy()
             stats["active"] = {t: int(host[g]) for g, t in enumerate(wanted)}
             stats["agreement"] = [int(x) for x in host[T:2 * T + 1]]
@@ -1019,16 +989,8 @@ def _tall_run(who, compressed_all, bases, original_shapes, tall_lambda, k, scali
             for name in names:
                 if D == 0:
                     out[name] = torch.zeros(original_shapes[name], device=dev)
-                res = out[name].view(original_shapes[name])
-                if name in later:
-                    res = later[name].to(res.device) + res
-                out[name] = res.cpu() if wants_cpu(device) else res
-        masks = None
-        if want_masks:
-            masks = {}
-            for g, t in enumerate(wanted):
-                m = streams[g].view(torch.uint8)[:n_bytes]
-                masks[t] = m.cpu() if wants_cpu(device) else m
+                out[name] = _finish_output(out[name], original_shapes[name], name, later, device)
+        masks = _packed_masks(streams, wanted, total_bits, device) if want_masks else None
     return out, masks, stats
 
 
@@ -1076,9 +1038,10 @@ def tall_masks_from_store(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
     return (masks, stats) if return_stats else masks
 
 
-def _emr_layout(who, names, rows, reference_state_dict, remove_keys):
-    """({key: first stream bit}, total bits) of the EMR mask streams: the layout ``_tall_run`` gives the TALL streams --
-    the sorted keys of the reference minus ``remove_keys`` (default: ``names``), each at the bit after the one before it."""
+def _mask_stream_layout(who, names, rows, reference_state_dict, remove_keys):
+    """({key: first stream bit}, total bits) of the packed mask streams, TALL's and EMR's: the sorted keys of the
+    reference minus ``remove_keys`` (default: ``names``), each at the bit after the one before it.  A parameter of
+    ``names`` without a place in them, or with another element count there, raises the named ValueError."""
     skip = set(remove_keys or [])
     if reference_state_dict is None:
         sizes = {n: rows[n] for n in names if n not in skip}
@@ -1096,6 +1059,22 @@ def _emr_layout(who, names, rows, reference_state_dict, remove_keys):
         bit_base[key] = total_bits
         total_bits += sizes[key]
     return bit_base, total_bits
+
+
+def _new_mask_streams(T, total_bits, dev):
+    """(zeroed int32 streams [T, words], the device table of their T addresses): whole 32-bit words, at least one."""
+    streams = torch.zeros((T, max((total_bits + 31) // 32, 1)), dtype=torch.int32, device=dev)
+    table = torch.tensor([streams.data_ptr() + 4 * g * streams.shape[1] for g in range(T)], dtype=torch.int64, device=dev)
+    return streams, table
+
+
+def _packed_masks(streams, wanted, total_bits, device):
+    """{task: packed uint8 [ceil(total_bits / 8)]} out of the stream tensor, row g for ``wanted[g]``."""
+    masks = {}
+    for g, t in enumerate(wanted):
+        m = streams[g].view(torch.uint8)[:(total_bits + 7) // 8]
+        masks[t] = m.cpu() if wants_cpu(device) else m
+    return masks
 
 
 def _popcount_rows(words: torch.Tensor) -> torch.Tensor:
@@ -1129,68 +1108,37 @@ def emr_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict
     Returns (unified {param: fp32 tensor}, masks {task: packed uint8 tensor}, rescalers {task: float}); with
     ``return_stats`` also {"abs_sum": {task: A}, "masked_sum": {task: B}, "active": {task: set bits}, "rows": D}.  The
     same arguments give the same bits on every call, the sums included."""
-    import numpy as np
     who = "emr_merge_parameters"
-    known = []
-    for per_task in compressed_all.values():
-        known += [t for t in (per_task._meta["have"] if getattr(per_task, "_meta", None) else per_task.keys())
-                  if t not in known]
-    for t in (tasks if tasks is not None else []):
-        if t not in known:
-            raise ValueError(f"unknown task {t!r}: the artifacts hold {known}")
-    wanted = sorted(set(known if tasks is None else tasks))
+    _, wanted = _store_tasks(compressed_all, tasks, who)
     T = len(wanted)
-    if not 1 <= T <= nat.MAX_TASKS:
-        raise ValueError(f"{who}: between 1 and {nat.MAX_TASKS} tasks can be merged, got {T}")
     names = sorted(compressed_all.keys())
     jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
                                   "the EMR merge")      # refusals before device work
-    bit_base, total_bits = _emr_layout(who, names, rows, reference_state_dict, remove_keys)
+    bit_base, total_bits = _mask_stream_layout(who, names, rows, reference_state_dict, remove_keys)
     dev = resolve_device(device)
     D = sum(rows.values())
-    n_bytes, n_words = (total_bits + 7) // 8, (total_bits + 31) // 32
     unified = {}
     A, B = [0.0] * T, [0.0] * T
     active = [0] * T
     with torch.cuda.device(dev):
-        streams = torch.zeros((T, max(n_words, 1)), dtype=torch.int32, device=dev)
+        streams, mask_tab = _new_mask_streams(T, total_bits, dev)
         if D > 0:
             state = torch.zeros(int(nat.lib().svdq_emr_state_bytes(T)) // 8, dtype=torch.float64, device=dev)
-            mask_tab = torch.tensor([streams.data_ptr() + 4 * g * streams.shape[1] for g in range(T)],
-                                    dtype=torch.int64, device=dev)
             for batch, entries in jobs.values():
                 plan = batch.plan
-                P = plan.P
-                n_out = max([len(live[name]) for name in entries.values()] + [1])
-                slot_task = np.zeros((P, n_out), dtype=np.int32)
-                task_map = np.full((P, n_out), -1, dtype=np.int32)
-                uni_tab = np.zeros(P, dtype=np.int64)
-                bits = np.zeros(P, dtype=np.int64)
-                for i, name in entries.items():
-                    for j, (g, pq) in enumerate(live[name]):
-                        task_map[i, j], slot_task[i, j] = g, pq
-                    bits[i] = bit_base[name]
-                    if rows[name] <= 0:
-                        continue
-                    res = unified[name] = torch.empty(rows[name], dtype=torch.float32, device=plan.device)
-                    uni_tab[i] = res.data_ptr()
-                rows_dev = plan.small[plan.layout.rows_off:plan.layout.rows_off + 8 * P].view(torch.int64)
+                slot_task, task_map, bits = _slot_tables(plan.P, entries, live, bit_base)
+                uni_tab, _, rows_dev, _ = _plan_outputs(plan, entries, rows, original_shapes, None, unified, {})
                 plan.emr_elect(torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device), T,
-                               torch.from_numpy(bits).to(plan.device), torch.from_numpy(uni_tab).to(plan.device), mask_tab,
-                               state, rows_dev=rows_dev)
+                               torch.from_numpy(bits).to(plan.device), uni_tab, mask_tab, state, rows_dev=rows_dev)
             host = state.cpu().numpy()
             A, B = [float(x) for x in host[:T]], [float(x) for x in host[T:2 * T]]
             if return_stats:
                 active = [int(x) for x in _popcount_rows(streams).cpu().tolist()]
         for name in names:
-            if name not in unified:
+            if name not in unified:      # a store without rows: no launch
                 unified[name] = torch.zeros(rows[name], dtype=torch.float32, device=dev)
-            res = unified[name].view(original_shapes[name])
-            unified[name] = res.cpu() if wants_cpu(device) else res
-        masks = {}
-        for g, t in enumerate(wanted):
-            m = streams[g].view(torch.uint8)[:n_bytes]
-            masks[t] = m.cpu() if wants_cpu(device) else m
+            unified[name] = _finish_output(unified[name], original_shapes[name], name, {}, device)
+        masks = _packed_masks(streams, wanted, total_bits, device)
     rescalers = {t: (A[g] / B[g] if B[g] != 0.0 else 1.0) for g, t in enumerate(wanted)}
     if not return_stats:
         return unified, masks, rescalers
@@ -1219,15 +1167,15 @@ def emr_task_state_dict(unified: Dict[str, torch.Tensor], masks: Dict[str, torch
     lam = rescale if rescale is not None else rescalers.get(task)
     if lam is None:
         raise ValueError(f"{who}: the rescaler of task {task!r} is missing")
-    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(lam):
+    if not _is_number(lam):
         raise ValueError(f"{who}: the rescaler of task {task!r} must be a finite number, got {lam!r}")
-    with np.errstate(over="ignore"):
-        lam32 = float(np.float32(lam))
-    if not math.isfinite(lam32):
+    lam32, ok = _as_fp32(lam)
+    if not ok:
         raise ValueError(f"{who}: the rescaler of task {task!r} is not finite in fp32: {lam!r}")
+    lam32 = float(lam32)
     names = sorted(unified.keys())
     rows = {n: int(unified[n].numel()) for n in names}
-    bit_base, total_bits = _emr_layout(who, names, rows, reference_state_dict, remove_keys)
+    bit_base, total_bits = _mask_stream_layout(who, names, rows, reference_state_dict, remove_keys)
     n_bytes, n_words = (total_bits + 7) // 8, (total_bits + 31) // 32
     stream = masks[task]
     if not (isinstance(stream, torch.Tensor) and stream.dtype is torch.uint8 and stream.dim() == 1
@@ -1259,20 +1207,12 @@ def emr_task_state_dict(unified: Dict[str, torch.Tensor], masks: Dict[str, torch
             uni_tab[i] = keep[-1].data_ptr()
             res = out[name] = torch.empty(rows[name], dtype=torch.float32, device=dev)
             out_tab[i] = res.data_ptr()
-            b = base_state_dict.get(name) if base_state_dict is not None else None
-            if b is not None and b.dtype is torch.float32 and b.numel() == rows[name]:
-                keep.append(prepare_vector(b, dev))
-                base_tab[i] = keep[-1].data_ptr()
-            elif b is not None:
-                later[name] = b
-        tabs = [torch.from_numpy(x).to(dev) for x in (rows_tab, bits, uni_tab, out_tab)]
+            base_tab[i] = _stage_base(name, rows[name], base_state_dict, dev, keep, later)
+        tabs =[torch.from_numpy(x).to(dev) for x in (rows_tab, bits, uni_tab, out_tab)]
         base_dev = torch.from_numpy(base_tab).to(dev) if base_tab.any() else None
         if out_tab.any():
             nat.check(nat.lib().svdq_emr_apply(P, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(words), lam32,
                                                _ptr(base_dev), _ptr(tabs[3]), _stream_ptr()), "svdq_emr_apply")
         for name in names:
-            res = out[name].view(unified[name].shape)
-            if name in later:
-                res = later[name].to(res.device) + res
-            out[name] = res.cpu() if wants_cpu(device) else res
+            out[name] = _finish_output(out[name], unified[name].shape, name, later, device)
     return out

@@ -100,6 +100,22 @@ def _ptr(t: Optional[torch.Tensor]) -> c_void_p:
     return c_void_p(0 if t is None else t.data_ptr())
 
 
+def _device_tensor_of(t, dtype) -> bool:
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype is dtype and t.is_contiguous()
+
+
+def _need_device_tensor(who: str, name: str, t, dtype, count: int) -> None:
+    """Argument ``name`` of entry point ``who`` is a contiguous ``dtype`` device tensor of ``count`` entries."""
+    if not (_device_tensor_of(t, dtype) and t.numel() == count):
+        raise ValueError(f"{who}: {name} must be a contiguous {str(dtype)[6:]} device tensor of {count} entries")
+
+
+def _need_state(who: str, state, dtype, need: int) -> None:
+    """The ``state`` of entry point ``who`` is a contiguous ``dtype`` device tensor of at least ``need`` bytes."""
+    if not (_device_tensor_of(state, dtype) and state.numel() * state.element_size() >= need):
+        raise ValueError(f"{who}: state must be a contiguous {str(dtype)[6:]} device tensor of at least {need} bytes")
+
+
 class NonFiniteInput(RuntimeError):
     """A task delta of the run held NaN or +-Inf (include/svdq.h, svdq_eig_rank_select: the eigen stage flags the
     parameter with a NaN energy).  ``indices``: the flagged parameters, as indices into the plan."""
@@ -937,15 +953,9 @@ class CompressPlan:
         need = int(self.lib.svdq_dare_work_bytes(n_tasks))
         if need <= 0:
             raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
-        if not (isinstance(row_base, torch.Tensor) and row_base.is_cuda and row_base.dtype is torch.int64
-                and row_base.is_contiguous() and row_base.numel() == self.P):
-            raise ValueError(f"{who}: row_base must be a contiguous int64 device tensor of {self.P} entries")
-        if not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.dtype is torch.float32
-                and weights.is_contiguous() and weights.numel() == n_tasks):
-            raise ValueError(f"{who}: weights must be a contiguous float32 device tensor of {n_tasks} entries")
-        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype is torch.int64
-                and state.is_contiguous() and state.numel() * 8 >= need):
-            raise ValueError(f"{who}: state must be a contiguous int64 device tensor of at least {need} bytes")
+        _need_device_tensor(who, "row_base", row_base, torch.int64, self.P)
+        _need_device_tensor(who, "weights", weights, torch.float32, n_tasks)
+        _need_state(who, state, torch.int64, need)
         if out_table.numel() != self.P:
             raise ValueError(f"{who}: out_table needs {self.P} entries, got {out_table.numel()}")
         if not 0 <= int(seed) < 1 << 64:
@@ -977,21 +987,14 @@ class CompressPlan:
         need = int(self.lib.svdq_tall_work_bytes(n_tasks))
         if need <= 0:
             raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
-        if not (isinstance(bit_base, torch.Tensor) and bit_base.is_cuda and bit_base.dtype is torch.int64
-                and bit_base.is_contiguous() and bit_base.numel() == self.P):
-            raise ValueError(f"{who}: bit_base must be a contiguous int64 device tensor of {self.P} entries")
-        if not (isinstance(lambdas, torch.Tensor) and lambdas.is_cuda and lambdas.dtype is torch.float32
-                and lambdas.is_contiguous() and lambdas.numel() == n_tasks):
-            raise ValueError(f"{who}: lambdas must be a contiguous float32 device tensor of {n_tasks} entries")
-        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype is torch.int64
-                and state.is_contiguous() and state.numel() * 8 >= need):
-            raise ValueError(f"{who}: state must be a contiguous int64 device tensor of at least {need} bytes")
+        _need_device_tensor(who, "bit_base", bit_base, torch.int64, self.P)
+        _need_device_tensor(who, "lambdas", lambdas, torch.float32, n_tasks)
+        _need_state(who, state, torch.int64, need)
         if out_table is None and mask_table is None:
             raise ValueError(f"{who}: out_table and mask_table are both None: nothing to write")
         for name, tab, count in (("out_table", out_table, self.P), ("mask_table", mask_table, n_tasks)):
-            if tab is not None and not (isinstance(tab, torch.Tensor) and tab.is_cuda and tab.dtype is torch.int64
-                                        and tab.is_contiguous() and tab.numel() == count):
-                raise ValueError(f"{who}: {name} must be a contiguous int64 device tensor of {count} entries")
+            if tab is not None:
+                _need_device_tensor(who, name, tab, torch.int64, count)
         if isinstance(min_agree, bool) or not isinstance(min_agree, int) or not 0 <= min_agree <= n_tasks:
             raise ValueError(f"{who}: min_agree must be an integer in [0, {n_tasks}], got {min_agree!r}")
         nat.check(self.lib.svdq_plan_tall_consensus(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
@@ -1017,16 +1020,10 @@ class CompressPlan:
         need = int(self.lib.svdq_emr_state_bytes(n_tasks))
         if need <= 0:
             raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
-        if not (isinstance(bit_base, torch.Tensor) and bit_base.is_cuda and bit_base.dtype is torch.int64
-                and bit_base.is_contiguous() and bit_base.numel() == self.P):
-            raise ValueError(f"{who}: bit_base must be a contiguous int64 device tensor of {self.P} entries")
-        if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype is torch.float64
-                and state.is_contiguous() and state.numel() * 8 >= need):
-            raise ValueError(f"{who}: state must be a contiguous float64 device tensor of at least {need} bytes")
-        for name, tab, count in (("uni_table", uni_table, self.P), ("mask_table", mask_table, n_tasks)):
-            if not (isinstance(tab, torch.Tensor) and tab.is_cuda and tab.dtype is torch.int64
-                    and tab.is_contiguous() and tab.numel() == count):
-                raise ValueError(f"{who}: {name} must be a contiguous int64 device tensor of {count} entries")
+        _need_device_tensor(who, "bit_base", bit_base, torch.int64, self.P)
+        _need_state(who, state, torch.float64, need)
+        _need_device_tensor(who, "uni_table", uni_table, torch.int64, self.P)
+        _need_device_tensor(who, "mask_table", mask_table, torch.int64, n_tasks)
         work = getattr(self, "_emr_work", None)
         need = int(self.lib.svdq_emr_work_bytes(self._h, n_out, n_tasks))
         if work is None or work.numel() < need:

@@ -528,6 +528,40 @@ def remerge_from_artifacts(artifact_dir: str, base_model_path, output_path: str 
             "diagnostics": diagnostics, "config": config}
 
 
+_NO_BASE = object()
+
+
+def _adopted_store(artifact_dir: str, tasks, device, base_model_path=_NO_BASE):
+    """The front of the ``*_from_artifacts`` merges over every task's own values: load_all_artifacts -> the ValueError
+    for a name of ``tasks`` that the store lacks -> the base (``_load_base``; none without ``base_model_path``) ->
+    adopt_artifacts.  Returns (config, diagnostics, bases, compressed, shapes, base or None, the base's tensors that the
+    store covers or None)."""
+    from .driver import adopt_artifacts
+    art = load_all_artifacts(artifact_dir, device=device)
+    config, diagnostics = art["config"], art["diagnostics"]
+    if tasks is not None:
+        known = {t for per_task in art["compressed"].values() for t in per_task}
+        for t in tasks:
+            if t not in known:
+                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
+    base = None if base_model_path is _NO_BASE else _load_base(base_model_path, device)
+    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
+    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
+              if d.get("original_shape") is not None}
+    covered = None if base is None else {n: b for n, b in base.items() if n in compressed}
+    return config, diagnostics, bases, compressed, shapes, base, covered
+
+
+def _merged_over_base(merged: Dict[str, torch.Tensor], base: Dict[str, torch.Tensor], output_path
+                      ) -> Dict[str, torch.Tensor]:
+    """The back of the same: the merged tensors, the base's other tensors cloned (as apply_merged_deltas does), saved on
+    the CPU when a path is given."""
+    out = {n: (merged[n] if n in merged else b.clone()) for n, b in base.items()}
+    if output_path:
+        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    return out
+
+
 def ties_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None, density: float = 0.2,
                               scaling: float = 1.0, merge_func: str = "mean", tasks=None, device: str = "cuda"
                               ) -> Dict[str, Any]:
@@ -538,28 +572,15 @@ def ties_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: s
     ``tasks``: names (None = every stored task).  The store's files are only read.
 
     Returns {"merged_state_dict", "stats" (thresholds, kept counts, row counters, rows), "diagnostics", "config"}."""
-    from .driver import adopt_artifacts
     from .merge import ties_merge_parameters
     if not (isinstance(density, (int, float)) and 0.0 < float(density) <= 1.0):      # before any file or device work
         raise ValueError(f"density must be in (0, 1], got {density!r}")
-    art = load_all_artifacts(artifact_dir, device=device)
-    config, diagnostics = art["config"], art["diagnostics"]
-    if tasks is not None:
-        known = {t for per_task in art["compressed"].values() for t in per_task}
-        for t in tasks:
-            if t not in known:
-                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
-    base = _load_base(base_model_path, device)
-    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
-    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
-              if d.get("original_shape") is not None}
-    covered = {n: b for n, b in base.items() if n in compressed}
+    config, diagnostics, bases, compressed, shapes, base, covered = _adopted_store(artifact_dir, tasks, device,
+                                                                                   base_model_path)
     merged, stats = ties_merge_parameters(compressed, bases, shapes, config, density=density, scaling=scaling,
                                           merge_func=merge_func, tasks=tasks, base_state_dict=covered, device=device,
                                           return_stats=True)
-    out = {n: (merged[n] if n in merged else b.clone()) for n, b in base.items()}
-    if output_path:
-        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    out = _merged_over_base(merged, base, output_path)
     return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
 
 
@@ -574,27 +595,14 @@ def dare_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: s
     store's files are only read.
 
     Returns {"merged_state_dict", "stats" (kept counts, rows, drop threshold), "diagnostics", "config"}."""
-    from .driver import adopt_artifacts
     from .merge import _dare_arguments, dare_merge_parameters
     _dare_arguments(drop_rate, seed)      # before any file or device work
-    art = load_all_artifacts(artifact_dir, device=device)
-    config, diagnostics = art["config"], art["diagnostics"]
-    if tasks is not None:
-        known = {t for per_task in art["compressed"].values() for t in per_task}
-        for t in tasks:
-            if t not in known:
-                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
-    base = _load_base(base_model_path, device)
-    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
-    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
-              if d.get("original_shape") is not None}
-    covered = {n: b for n, b in base.items() if n in compressed}
+    config, diagnostics, bases, compressed, shapes, base, covered = _adopted_store(artifact_dir, tasks, device,
+                                                                                   base_model_path)
     merged, stats = dare_merge_parameters(compressed, bases, shapes, config, drop_rate=drop_rate, seed=seed,
                                           rescale=rescale, weights=weights, normalize=normalize, scaling=scaling,
                                           tasks=tasks, base_state_dict=covered, device=device, return_stats=True)
-    out = {n: (merged[n] if n in merged else b.clone()) for n, b in base.items()}
-    if output_path:
-        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    out = _merged_over_base(merged, base, output_path)
     return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
 
 
@@ -613,34 +621,21 @@ def consensus_merge_from_artifacts(artifact_dir: str, base_model_path, output_pa
     Returns {"merged_state_dict", "masks" ({task: packed uint8 tensor} or None), "stats" (active, agreement, rows),
     "diagnostics", "config"}."""
     import numpy as np
-    from .driver import adopt_artifacts
     from .merge import _tall_arguments, consensus_merge_parameters
     who = "consensus_merge_parameters"
     if not hasattr(tall_lambda, "get"):
         _tall_arguments(who, tall_lambda, None, [None], check_k=False)      # one number for every task: before any file or device work
     if isinstance(k, bool) or not isinstance(k, int) or k < 0:
         raise ValueError(f"{who}: k must be an integer in [0, merged tasks], got {k!r}")
-    art = load_all_artifacts(artifact_dir, device=device)
-    config, diagnostics = art["config"], art["diagnostics"]
-    if tasks is not None:
-        known = {t for per_task in art["compressed"].values() for t in per_task}
-        for t in tasks:
-            if t not in known:
-                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
-    base = _load_base(base_model_path, device)
-    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
-    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
-              if d.get("original_shape") is not None}
-    covered = {n: b for n, b in base.items() if n in compressed}
+    config, diagnostics, bases, compressed, shapes, base, covered = _adopted_store(artifact_dir, tasks, device,
+                                                                                   base_model_path)
     want_masks = mask_output_path is not None
     got = consensus_merge_parameters(compressed, bases, shapes, config, tall_lambda=tall_lambda, k=k, scaling=scaling,
                                      tasks=tasks, base_state_dict=covered,
                                      reference_state_dict=base if want_masks else None, remove_keys=remove_keys,
                                      return_masks=want_masks, device=device, return_stats=True)
     merged, masks, stats = got if want_masks else (got[0], None, got[1])
-    out = {n: (merged[n] if n in merged else b.clone()) for n, b in base.items()}
-    if output_path:
-        torch.save({n: v.cpu() for n, v in out.items()}, output_path)
+    out = _merged_over_base(merged, base, output_path)
     if want_masks:
         with open(mask_output_path, "wb") as f:      # a file object: numpy appends no suffix to the caller's name
             np.savez(f, **{t: m.cpu().numpy() for t, m in masks.items()})
@@ -698,18 +693,8 @@ def emr_from_artifacts(artifact_dir: str, output_dir: str, tasks=None, device: s
 
     Returns {"unified", "masks", "rescalers", "stats" (abs_sum, masked_sum, active, rows), "paths", "diagnostics",
     "config"}."""
-    from .driver import adopt_artifacts
     from .merge import emr_merge_parameters
-    art = load_all_artifacts(artifact_dir, device=device)
-    config, diagnostics = art["config"], art["diagnostics"]
-    if tasks is not None:
-        known = {t for per_task in art["compressed"].values() for t in per_task}
-        for t in tasks:
-            if t not in known:
-                raise ValueError(f"unknown task {t!r}: the artifacts hold {sorted(known)}")
-    bases, compressed = adopt_artifacts(art.pop("bases"), art.pop("compressed"), config, device=device)
-    shapes = {n: torch.Size(d["original_shape"]) for n, d in diagnostics.get("per_parameter", {}).items()
-              if d.get("original_shape") is not None}
+    config, diagnostics, bases, compressed, shapes, _, _ = _adopted_store(artifact_dir, tasks, device)
     unified, masks, rescalers, stats = emr_merge_parameters(compressed, bases, shapes, config, tasks=tasks,
                                                             device=device, return_stats=True)
     paths = save_emr_merge(output_dir, unified, masks, rescalers, stats)
