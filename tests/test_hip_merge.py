@@ -19,6 +19,8 @@ def sq():
 
 
 def test_reconstruct_kernel_vs_oracle(sq):
+    """Five (k, n_low) pairs against the oracle's matmul; the tight anchor of k_reconstruct -- every (k, r), a derived
+    per-element fp64 bound -- is tests/test_hip_artifact_plane.py (check c)."""
     from oracle import svd_hybrid_oracle as orc
     g = torch.Generator().manual_seed(1)
     for D, k, nl, fp16, with_mean in ((100, 2, 2, False, True), (70001, 3, 5, True, True), (4096, 8, 0, True, False),
