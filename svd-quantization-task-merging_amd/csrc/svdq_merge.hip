@@ -25,7 +25,7 @@
 //                        masked regions, apply_mask_to_tensor (mask_loader.py:651-679) inside the pass; minus-base mode =
 //                        fine-tuned and base tensors in, compute_task_vector (task_vector_loader.py:103-141) in registers.
 //
-// Per-row arithmetic is that of k_reconstruct / k_recon_error (svdq_elem.hip): fp32 fma chains from 0 over the columns
+// Per-row arithmetic is that of k_reconstruct / k_recon_error (svdq_basis_ops.hip): fp32 fma chains from 0 over the columns
 // in order, hi + lo, + mean, * scale -- so a parameter's merged rows are the same bits as the per-parameter route's
 // (the diagnostics' sums run in another order: equal to the last digits of the fp64 accumulators).  The four streaming
 // kernels are one program in four arrangements.  Three of them (k_merge_reconstruct, k_task_reconstruct, k_task_expand)

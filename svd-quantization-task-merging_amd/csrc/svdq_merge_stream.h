@@ -284,7 +284,7 @@ __device__ __forceinline__ void walk_rows_of_lane(int (&rl)[RPL], float (&mv)[RP
 }
 
 // hi[m][s] = sum_i Uh[rl[m]][i] C[i][c0 + s], lo likewise over the low part: fp32 fma chains from 0 over the columns in
-// order -- the per-row arithmetic of k_reconstruct (svdq_elem.hip), so every kernel built on this gives the per-parameter
+// order -- the per-row arithmetic of k_reconstruct (svdq_basis_ops.hip), so every kernel built on this gives the per-parameter
 // route's bits.  Columns outermost: one coefficient read serves the lane's rows, the G x RPL chains are independent.
 template <typename T, int G, int RPL>
 __device__ __forceinline__ void fma_chains(float (&hi)[RPL][G], float (&lo)[RPL][G], const T *Uh, const T *Ul,

@@ -62,6 +62,29 @@ class MaskSet:
     def _table(self, tensors):
         return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).to(self.device)
 
+    def _mask_bytes(self, masks):
+        """One mask per parameter as device bool bytes, each of its parameter's size."""
+        mb = [_as_mask_bytes(m, self.device) for m in masks]
+        for q in range(self.Q):
+            if mb[q].numel() != self.numels[q]:
+                raise ValueError(f"Shape mismatch: tensor vs mask for parameter {q}")
+        return mb
+
+    def _packed_streams(self, streams, bit_offsets, strategy: str):
+        """The stream part of a packed-combine state: checked streams on the device, their pointer, length and
+        bit-offset tables."""
+        if strategy not in nat.MASK_STRATEGIES:
+            raise ValueError(f"Unknown mask strategy: {strategy}")
+        if not streams:
+            raise ValueError("Empty mask list")
+        st = [_as_packed_stream(s, self.device) for s in streams]
+        need = max((int(o) + n + 7) // 8 for o, n in zip(bit_offsets, self.numels))
+        if any(s.numel() < need for s in st):
+            raise ValueError("Shape mismatch: a packed mask stream is shorter than the parameters it should cover")
+        return dict(st=st, n=len(st), strategy=nat.MASK_STRATEGIES[strategy], sp=self._table(st),
+                    sb=torch.tensor([s.numel() for s in st], dtype=torch.int64).to(self.device),
+                    bo=torch.tensor([int(o) for o in bit_offsets], dtype=torch.int64).to(self.device))
+
     # prepare_* allocate outputs and upload pointer tables once; run_* only enqueue kernels, so a caller
     # that compresses the same model repeatedly (or a benchmark) pays no host work per call.
     def prepare_combine(self, masks_per_param, strategy: str):
@@ -95,10 +118,10 @@ class MaskSet:
 
     def prepare_compact(self, masks, srcs_per_param, want_false: bool):
         n_src = len(srcs_per_param[0])
-        mb = [_as_mask_bytes(m, self.device) for m in masks]
+        mb = self._mask_bytes(masks)
         srcs = [[prepare_vector(v, self.device) for v in vs] for vs in srcs_per_param]
         for q in range(self.Q):
-            if mb[q].numel() != self.numels[q] or len(srcs[q]) != n_src or any(v.numel() != self.numels[q] for v in srcs[q]):
+            if len(srcs[q]) != n_src or any(v.numel() != self.numels[q] for v in srcs[q]):
                 raise ValueError(f"Shape mismatch: tensor vs mask for parameter {q}")
         dt = [[torch.empty(self.numels[q], dtype=torch.float32, device=self.device) for _ in range(n_src)]
               for q in range(self.Q)]
@@ -119,10 +142,7 @@ class MaskSet:
                                                     _stream_ptr()), "svdq_maskset_compact")
 
     def prepare_indices(self, masks, want_false: bool):
-        mb = [_as_mask_bytes(m, self.device) for m in masks]
-        for q in range(self.Q):
-            if mb[q].numel() != self.numels[q]:
-                raise ValueError(f"Shape mismatch: tensor vs mask for parameter {q}")
+        mb = self._mask_bytes(masks)
         it = [torch.empty(self.numels[q], dtype=torch.int32, device=self.device) for q in range(self.Q)]
         if_ = [torch.empty(self.numels[q], dtype=torch.int32, device=self.device) for q in range(self.Q)] \
             if want_false else None
@@ -158,23 +178,14 @@ class MaskSet:
         task over the flattened state dict -- the form TALL_mask files have): parameter q's elements are bits
         ``bit_offsets[q] + e`` of every stream.  Returns (combined bool-byte masks, idx_true, idx_false | None,
         count_true, count_false | None); run with run_combine_packed_indices()."""
-        if strategy not in nat.MASK_STRATEGIES:
-            raise ValueError(f"Unknown mask strategy: {strategy}")
-        if not streams:
-            raise ValueError("Empty mask list")
-        st = [_as_packed_stream(s, self.device) for s in streams]
-        need = max((int(o) + n + 7) // 8 for o, n in zip(bit_offsets, self.numels))
-        if any(s.numel() < need for s in st):
-            raise ValueError("Shape mismatch: a packed mask stream is shorter than the parameters it should cover")
+        x = self._packed_streams(streams, bit_offsets, strategy)
         outs = [torch.empty(nq, dtype=torch.uint8, device=self.device) for nq in self.numels]
         it = [torch.empty(nq, dtype=torch.int32, device=self.device) for nq in self.numels]
         if_ = [torch.empty(nq, dtype=torch.int32, device=self.device) for nq in self.numels] if want_false else None
         ct = torch.zeros(self.Q, dtype=torch.int64, device=self.device)
         cf = torch.zeros(self.Q, dtype=torch.int64, device=self.device) if want_false else None
-        self._p = dict(st=st, outs=outs, it=it, if_=if_, ct=ct, cf=cf, n=len(st), strategy=nat.MASK_STRATEGIES[strategy],
-                       sp=self._table(st), sb=torch.tensor([s.numel() for s in st], dtype=torch.int64).to(self.device),
-                       bo=torch.tensor([int(o) for o in bit_offsets], dtype=torch.int64).to(self.device),
-                       ot=self._table(outs), tt=self._table(it), ft=self._table(if_) if want_false else None)
+        self._p = dict(x, outs=outs, it=it, if_=if_, ct=ct, cf=cf, ot=self._table(outs), tt=self._table(it),
+                       ft=self._table(if_) if want_false else None)
         return outs, it, if_, ct, cf
 
     def run_combine_packed_indices(self):
@@ -189,10 +200,7 @@ class MaskSet:
     def count_scan(self, masks):
         """mask.sum() / (~mask).sum() of already combined masks (device int64 [Q] each); leaves the tile offsets in
         ``self.work`` for unit_starts()."""
-        mb = [_as_mask_bytes(m, self.device) for m in masks]
-        for q in range(self.Q):
-            if mb[q].numel() != self.numels[q]:
-                raise ValueError(f"Shape mismatch: tensor vs mask for parameter {q}")
+        mb = self._mask_bytes(masks)
         ct = torch.zeros(self.Q, dtype=torch.int64, device=self.device)
         cf = torch.zeros(self.Q, dtype=torch.int64, device=self.device)
         self._s = dict(mb=mb, mt=self._table(mb), ct=ct, cf=cf)
@@ -238,23 +246,12 @@ class MaskSet:
 
     def prepare_combine_packed_starts(self, streams, bit_offsets, strategy: str, plan):
         """The same from bit-packed tall masks (see prepare_combine_packed_indices)."""
-        if strategy not in nat.MASK_STRATEGIES:
-            raise ValueError(f"Unknown mask strategy: {strategy}")
-        if not streams:
-            raise ValueError("Empty mask list")
-        st = [_as_packed_stream(s, self.device) for s in streams]
-        need = max((int(o) + n + 7) // 8 for o, n in zip(bit_offsets, self.numels))
-        if any(s.numel() < need for s in st):
-            raise ValueError("Shape mismatch: a packed mask stream is shorter than the parameters it should cover")
+        x = self._packed_streams(streams, bit_offsets, strategy)
         outs = [torch.empty(nq, dtype=torch.uint8, device=self.device) for nq in self.numels]
         ct = torch.zeros(self.Q, dtype=torch.int64, device=self.device)
         cf = torch.zeros(self.Q, dtype=torch.int64, device=self.device)
         us = torch.empty(int(plan.sizes.n_units), dtype=torch.int64, device=self.device)
-        self._ps = dict(st=st, outs=outs, ct=ct, cf=cf, us=us, plan=plan, n=len(st),
-                        strategy=nat.MASK_STRATEGIES[strategy], sp=self._table(st),
-                        sb=torch.tensor([s.numel() for s in st], dtype=torch.int64).to(self.device),
-                        bo=torch.tensor([int(o) for o in bit_offsets], dtype=torch.int64).to(self.device),
-                        ot=self._table(outs))
+        self._ps = dict(x, outs=outs, ct=ct, cf=cf, us=us, plan=plan, ot=self._table(outs))
         self._s = dict(mb=outs, mt=self._ps["ot"], ct=ct, cf=cf)
         return outs, ct, us
 

@@ -1,5 +1,5 @@
 """
-A numpy model of the mask operators (csrc/svdq_elem.hip; host layer MaskSet in mask_loader.py): what every one of them
+A numpy model of the mask operators (csrc/svdq_mask.hip; host layer MaskSet in mask_loader.py): what every one of them
 has to produce, written with numpy's own selection primitives and nothing from the package under test.  No torch ops,
 no GPU.  tests/test_mask_model_cpu.py anchors it on the masks the reference itself produced (tests/golden/masks.npz);
 tests/test_hip_mask_ops.py compares the kernels with it, integer for integer.

@@ -5,7 +5,7 @@ every parameter sits at another (k, r) and another block / unit edge, against th
   a. svdq_task_reconstruct (k_task_reconstruct): every element within the derived bound of ``task_values``
   b. svdq_merge (k_merge_reconstruct) at every compiled set count: within the bound of ``merged_values``
   c. the bit contracts the project states, over the plane: reconstruct_tasks == merge with the one-hot set ==
-     reconstruct_from_coefficients (k_reconstruct, svdq_elem.hip) on RTVQQuantizer.dequantize -- which puts k_reconstruct
+     reconstruct_from_coefficients (k_reconstruct, svdq_basis_ops.hip) on RTVQQuantizer.dequantize -- which puts k_reconstruct
      itself within the bound of fp64 at every (k, r)
   d. svdq_merge_masked / svdq_task_reconstruct_masked (k_merge_expand, k_task_expand): the bits of torch's boolean
      assignment of the plain route's compacted rows -- a block's first compacted row is anywhere, so both parts of a

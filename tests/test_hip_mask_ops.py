@@ -1,5 +1,5 @@
 """
-GPU tests of the mask operators (csrc/svdq_elem.hip; MaskSet and compute_*_mask in mask_loader.py) against the numpy
+GPU tests of the mask operators (csrc/svdq_mask.hip; MaskSet and compute_*_mask in mask_loader.py) against the numpy
 model of tests/mask_model.py, which shares nothing with the kernels and is itself anchored on the reference's outputs
 (tests/test_mask_model_cpu.py).
 

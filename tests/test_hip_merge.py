@@ -474,7 +474,7 @@ def test_plain_merge_variants_are_the_per_parameter_route(sq, n_tasks, fp16, n_s
     """svdq_merge (k_merge_coeff + k_merge_reconstruct) at every compiled set count (1, 2, 4, 8), both block sizes (256
     rows up to 16 tasks, 128 above) and both basis types, against code outside svdq_merge.hip: every set is ONE task with
     weight 1.0, so its coefficients are that task's own and its rows are merge_parameter's for a one-task dictionary
-    (RTVQQuantizer.dequantize + reconstruct_from_coefficients: k_reconstruct of svdq_elem.hip); the sets are then
+    (RTVQQuantizer.dequantize + reconstruct_from_coefficients: k_reconstruct of svdq_basis_ops.hip); the sets are then
     combined with their shares and added to the base by torch, elementwise in fp32, in the kernel's order -- bit for bit."""
     from oracle import svd_hybrid_oracle as orc
     from svdq_amd.pipeline import CompressPlan, task_artifact
