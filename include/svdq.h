@@ -968,6 +968,70 @@ int svdq_plan_ties_merge(const svdq_plan *plan, const int64_t *rows_dev, const v
                          float scaling, const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/,
                          void *state_dev, void *work_dev, void *stream);
 
+/* ---- the Model Breadcrumbs merge of a store (Davari & Belilovsky 2023: "Model Breadcrumbs: Scaling Multi-Task Model
+ *      Merging with Sparse Masks"), and with it the per-tensor trim: a two-sided magnitude band per weight tensor and
+ *      task, in streaming passes over the basis.  The definition, on what the store reconstructs:
+ *        inputs   T tasks in sorted-name order.  For parameter p with D_p rows and a task t that has p: v_t[d] = the value
+ *                 svdq_task_reconstruct writes for task t at row d, bit for bit (RTVQQuantizer.dequantize rtvq.py:85-103
+ *                 + reconstruct_from_coefficients merge.py:144-194), m = |v_t[d]|.  A task that lacks p contributes
+ *                 nothing to p: ranks are per tensor, so this operator has no implicit zeros.
+ *        counts   Python integers per parameter, computed by the caller: n_keep = int(D_p * density), n_top = int(D_p *
+ *                 gamma), n_bot = D_p - n_keep - n_top; if n_bot < 0: n_top += n_bot, n_bot = 0 (the outlier cut gives
+ *                 way so the density is met).
+ *        band     n_keep == 0: nothing of (p, t) is kept.  Otherwise lo = the (n_bot + 1)-th smallest magnitude of
+ *                 (p, t), hi = the (D_p - n_top)-th smallest; a value is kept iff lo <= m <= hi.  Equal magnitudes at
+ *                 either threshold are all kept, so kept >= n_keep.  density >= 1 keeps everything, whatever gamma is.
+ *        combine  in task order over the kept values, every sum rounded in fp32.  sign_election 0: a = their sum, c =
+ *                 their number.  sign_election != 0: s = their sum, positive iff s >= 0 (s == 0 elects positive, as for
+ *                 svdq_plan_ties_merge); a and c run over the kept values whose sign strictly agrees (v > 0 / v < 0).
+ *                 merge_sum != 0: a; else the mean a / max(c, 1), one fp32 division.
+ *        apply    out = base + scaling * merged (one product, one sum, each rounded; without base the product)
+ *      The paper's method is sign_election 0, sum, density = gamma_paper - beta_paper, gamma = 1 - gamma_paper; the
+ *      per-tensor TIES trim is gamma = 0, sign_election 1, mean.  lo and hi are found EXACTLY by a radix selection on the
+ *      magnitude bits (bits & 0x7fffffff), 8 bits per pass from the top, SVDQ_CRUMBS_DIGITS passes, per plan:
+ *        for digit in 0 .. SVDQ_CRUMBS_DIGITS - 1:
+ *            svdq_plan_crumbs_hist(plan, ..., digit, bounds, state, ...)   once with bounds 3 for n_out <= 16; above
+ *                                                                          twice, bounds 1 then bounds 2
+ *            svdq_plan_crumbs_select_step(plan, T, digit, ranks, state)    once
+ *        svdq_plan_crumbs_merge(plan, ..., state, ...)
+ *      state_dev: ONE table per plan (thresholds never cross parameters) of svdq_crumbs_work_bytes(P, T) bytes, zeroed by
+ *      the caller before digit 0: hist uint32 [P][2][T][256], then uint64 words prefix [P][2][T] (bound 0 = lo, 1 = hi;
+ *      after the last digit the bit pattern of the bound in the low 32 bits; a (p, t) that keeps nothing ends with the
+ *      sentinel band lo = 0xffffffff, hi = 0) | rank [P][2][T] | kept [P][T] | rows with kept values of both signs | rows
+ *      with nothing kept.  Counts are integers added by atomics, one flush per work unit: no result depends on the order
+ *      the units run in, two calls give identical bits.  Histogram counts are 32-bit: a plan with a parameter of 2^32
+ *      rows or more is refused.
+ *   svdq_plan_crumbs_hist  counts, for every live slot and every bound named by `bounds` (1 = lo, 2 = hi, 3 = both), the
+ *                 digit's value of the magnitudes whose bits above `digit` equal that bound's prefix.  Both bounds in one
+ *                 pass need [2][16][256] counters in LDS: bounds 3 is refused for n_out > 16.
+ *   svdq_plan_crumbs_select_step  one small launch, one thread per (parameter, task, bound): the bin that holds the
+ *                 wanted rank (walked from the top), appended to the prefix; the remaining rank; the histograms it read
+ *                 zeroed.  ranks_dev int64 [P][2], read at digit 0: n_bot + 1 and D_p - n_top, or 0 and 0 for a
+ *                 parameter with n_keep == 0.  A (p, t) without counts at digit 0 is no live task of the parameter.
+ *   svdq_plan_crumbs_merge  band, elect, combine, apply for every parameter with a non-NULL output; adds the by-products
+ *                 to the table.
+ *   slot_task_dev, task_map_dev, n_out, n_tasks, rows_dev, small_dev, basis_dev, mean_dev, base_ptrs_dev, out_ptrs_dev,
+ *                 work_dev: as for svdq_plan_ties_merge (live slots in ASCENDING store order).
+ *   errors        SVDQ_EINVAL before anything is launched: a NULL plan, buffer or table; n_out or n_tasks outside
+ *                 [1, SVDQ_MAX_TASKS]; a digit outside [0, SVDQ_CRUMBS_DIGITS); bounds outside {1, 2, 3}; a missing mean
+ *                 on a centred plan; a parameter of 2^32 rows or more.
+ *   Allocates nothing, copies nothing to the host, synchronises nothing.  Works on plans filled by any compress route and
+ *   on plans filled by svdq_plan_import.  Non-finite store values are outside the definition, as for TIES. */
+#define SVDQ_CRUMBS_DIGITS 4
+int64_t svdq_crumbs_work_bytes(int32_t n_params, int32_t n_tasks);
+int svdq_plan_crumbs_hist(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                          const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                          const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks, int32_t digit,
+                          int32_t bounds /*1 lo, 2 hi, 3 both*/, void *state_dev, void *work_dev, void *stream);
+int svdq_plan_crumbs_select_step(const svdq_plan *plan, int32_t n_tasks, int32_t digit,
+                                 const int64_t *ranks_dev /*[P][2]*/, void *state_dev, void *stream);
+int svdq_plan_crumbs_merge(const svdq_plan *plan, const int64_t *rows_dev, const void *small_dev, const void *basis_dev,
+                           const float *mean_dev, const int32_t *slot_task_dev /*[P][n_out]*/,
+                           const int32_t *task_map_dev /*[P][n_out]*/, int32_t n_out, int32_t n_tasks,
+                           int32_t sign_election, int32_t merge_sum, float scaling,
+                           const void *base_ptrs_dev /*NULL or [P]*/, const void *out_ptrs_dev /*[P]*/, void *state_dev,
+                           void *work_dev, void *stream);
+
 /* ---- the drop-and-rescale (DARE) merge of a store, and task arithmetic from a store, in ONE streaming pass over the
  *      basis.  The reference's dispatcher lists "dare" and "task_arithmetic" beside "svd_hybrid" and implements neither
  *      (cli.py answers "not yet implemented"; scripts/main.py keeps that answer); the definition is Yu et al. 2024

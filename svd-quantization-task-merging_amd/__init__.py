@@ -24,7 +24,8 @@ from .mask_loader import (combine_masks, compute_union_mask, compute_intersectio
 from .merge import (dequantize_and_average, reconstruct_from_coefficients, merge_parameter, merge_all_parameters,
                     apply_merged_deltas, merge_with_clustering, reconstruct_task_vectors,
                     reconstruct_task_vectors_masked, ties_merge_parameters, dare_merge_parameters,
-                    consensus_merge_parameters, tall_masks_from_store, emr_merge_parameters, emr_task_state_dict)
+                    consensus_merge_parameters, tall_masks_from_store, emr_merge_parameters, emr_task_state_dict,
+                    breadcrumbs_merge_parameters)
 from .weighting import (load_performance_metrics, compute_uniform_weights, compute_performance_weights,
                         compute_cluster_weights, compute_weights, apply_weights_to_tensors, get_weight_statistics)
 from .clustering import (cluster_tasks, task_gram, cluster_from_gram, cluster_statistics_from_gram, flatten_task_vectors,
@@ -41,15 +42,15 @@ from .storage import (save_basis, load_basis, save_compressed_coefficients, load
                       reconstruct_tasks_from_artifacts_masked, add_tasks_to_artifacts, remerge_from_artifacts,
                       consolidate_artifacts, ties_merge_from_artifacts, dare_merge_from_artifacts,
                       consensus_merge_from_artifacts, emr_from_artifacts, emr_task_model_from_files, save_emr_merge,
-                      load_emr_merge)
+                      load_emr_merge, breadcrumbs_merge_from_artifacts)
 from .task_vector_loader import (load_checkpoint, compute_task_vector, compute_task_vectors, load_task_vectors,
                                  get_parameter_names, organize_by_parameter, flatten_task_deltas,
                                  get_task_checkpoint_paths)
 from .task_vectors import TaskVector, QuantizedTaskVector, QuantizedFinetunedModel, QuantizedBaseAndTaskVector
 from .ingest import ElementwiseBatch, ingest_state_dicts, quantize_state_dict, dequantize_payloads
 from .driver import adopt_artifacts, adopt_bases, build_bases, run_basis_and_compress, run_basis_and_compress_from_checkpoints
-from .pipeline import (CompressPlan, NonFiniteInput, TiesState, compress_batch, nonfinite_parameters, pack_small,
-                       ties_thresholds)
+from .pipeline import (CompressPlan, CrumbsState, NonFiniteInput, TiesState, compress_batch, crumbs_thresholds,
+                       nonfinite_parameters, pack_small, ties_thresholds)
 from . import quantization_utils
 from .quantization_utils import (absmax_quantization, dequantize_absmax, qunatization_error_check,
                                  quantization_error_check_asymmetric)

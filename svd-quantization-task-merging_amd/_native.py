@@ -176,6 +176,13 @@ SIGNATURES = {
     "svdq_ties_select_step": (c_int32, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]),
     "svdq_plan_ties_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                        c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "svdq_crumbs_work_bytes": (c_int64, [c_int32, c_int32]),
+    "svdq_plan_crumbs_hist": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                        c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "svdq_plan_crumbs_select_step": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "svdq_plan_crumbs_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
     "svdq_dare_work_bytes": (c_int64, [c_int32]),
     "svdq_plan_dare_merge": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                        c_int32, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_float, c_void_p,

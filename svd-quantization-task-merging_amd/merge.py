@@ -822,6 +822,115 @@ def ties_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dic
     return (out, stats) if return_stats else out
 
 
+def _crumbs_arguments(density, gamma, scaling, merge_func):
+    """The named ValueError for what lies outside the Breadcrumbs definition; (density, gamma) as floats."""
+    if not _is_number(density) or not 0.0 < float(density) <= 1.0:
+        raise ValueError(f"density must be in (0, 1], got {density!r}")
+    if not _is_number(gamma) or not 0.0 <= float(gamma) < 1.0:
+        raise ValueError(f"gamma must be in [0, 1), got {gamma!r}")
+    if not _is_number(scaling):
+        raise ValueError(f"scaling must be a finite number, got {scaling!r}")
+    if merge_func not in ("mean", "sum"):
+        raise ValueError(f"merge_func must be 'mean' or 'sum', got {merge_func!r}")
+    return float(density), float(gamma)
+
+
+def crumbs_ranks(rows: int, density: float, gamma: float):
+    """(rank of lo, rank of hi), 1-based from below among the ``rows`` magnitudes of one (parameter, task); (0, 0) when
+    nothing is kept.  Python integers: n_keep = int(D * density), n_top = int(D * gamma), n_bot = D - n_keep - n_top, the
+    outlier cut giving way (n_top += n_bot) where n_bot < 0."""
+    D = int(rows)
+    n_keep, n_top = int(D * density), int(D * gamma)
+    n_bot = D - n_keep - n_top
+    if n_bot < 0:
+        n_top, n_bot = n_top + n_bot, 0
+    return (n_bot + 1, D - n_top) if n_keep > 0 else (0, 0)
+
+
+def breadcrumbs_merge_parameters(compressed_all: Dict[str, Dict[str, Dict]], bases: Dict[str, Dict],
+                                 original_shapes: Dict[str, torch.Size], config, density: float = 0.9,
+                                 gamma: float = 0.01, scaling: float = 1.0, sign_election: bool = False,
+                                 merge_func: str = "sum", tasks=None,
+                                 base_state_dict: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda",
+                                 return_stats: bool = False):
+    """The Model Breadcrumbs merge (Davari & Belilovsky 2023) of what a store reconstructs, and the per-tensor trim,
+    without a task model ever being written (the contract is at svdq_plan_crumbs_hist in
+    include/svdq.h).  With v_t what ``reconstruct_task_vectors`` returns for task t and the tasks in sorted-name order,
+    per parameter of D_p rows and per task that has it: n_keep = int(D_p * density), n_top = int(D_p * gamma), n_bot =
+    D_p - n_keep - n_top (where negative, n_top gives way); the value is kept iff lo <= |v| <= hi, lo the (n_bot + 1)-th
+    and hi the (D_p - n_top)-th smallest magnitude of that tensor and task (ties at either are all kept; nothing is kept
+    where n_keep == 0; ``density=1`` keeps everything).  The kept values are added in task order (``merge_func="sum"``)
+    or averaged ("mean"); with ``sign_election`` only those whose sign agrees with the sign of their fp32 sum (>= 0 is
+    positive).  Returns ``scaling * merged`` per parameter, ``base + scaling * merged`` for the parameters
+    ``base_state_dict`` holds.  A task that lacks a parameter contributes nothing to it.
+
+    The paper's method: ``sign_election=False, merge_func="sum"``, ``density = gamma_paper - beta_paper``, ``gamma = 1 -
+    gamma_paper``.  The per-tensor TIES trim: ``gamma=0, sign_election=True, merge_func="mean"``.
+
+    Takes dictionaries backed by a fused run or by ``adopt_artifacts`` and refuses what ``ties_merge_parameters``
+    refuses, under its own name; ``tasks``: the names to merge (None = all).  ``density`` outside (0, 1], ``gamma``
+    outside [0, 1), a ``scaling`` that is not finite or another ``merge_func`` raises a ValueError.
+
+    Returns {param: tensor}; with ``return_stats`` also {"rows": D, "thresholds": {param: {task: (lo, hi) or None}},
+    "kept": {param: {task: int}}, "kept_total": {task: int}, "sign_conflict_rows": int, "empty_rows": int}.  Per plan 4
+    digits of histogram passes find both thresholds of every (parameter, task) exactly, one more pass merges: the only
+    buffers that grow with the model are the outputs.  The same arguments give the same bits on every call."""
+    import numpy as np
+    from .pipeline import crumbs_thresholds
+    who = "breadcrumbs_merge_parameters"
+    density, gamma = _crumbs_arguments(density, gamma, scaling, merge_func)
+    _, wanted = _store_tasks(compressed_all, tasks, who)
+    T = len(wanted)
+    names = sorted(compressed_all.keys())
+    jobs, rows, live = _ties_jobs(names, wanted, compressed_all, bases, original_shapes, who,
+                                  "the Breadcrumbs merge")      # refusals before device work
+    dev = resolve_device(device)
+    D = sum(rows.values())
+    out, later = {}, {}
+    stats = {"rows": D, "thresholds": {}, "kept": {}, "kept_total": {t: 0 for t in wanted}, "sign_conflict_rows": 0,
+             "empty_rows": 0}
+    if D == 0:
+        out = {name: torch.zeros(original_shapes[name], device=dev) for name in names}
+        return (out, stats) if return_stats else out
+    with torch.cuda.device(dev):
+        keep, states = [], []
+        for batch, entries in jobs.values():
+            plan = batch.plan
+            slot_task, task_map, _ = _slot_tables(plan.P, entries, live)
+            out_tab, base_tab, rows_dev, kept = _plan_outputs(plan, entries, rows, original_shapes, base_state_dict, out,
+                                                              later)
+            keep += kept
+            ranks = np.zeros((plan.P, 2), dtype=np.int64)
+            for i, name in entries.items():
+                ranks[i] = crumbs_ranks(rows[name], density, gamma)
+            slot_task, task_map = torch.from_numpy(slot_task).to(plan.device), torch.from_numpy(task_map).to(plan.device)
+            state = crumbs_thresholds(plan, slot_task, task_map, T, torch.from_numpy(ranks).to(plan.device),
+                                      rows_dev=rows_dev)
+            plan.crumbs_merge(slot_task, task_map, T, state.table, out_tab, sign_election=sign_election,
+                              merge_func=merge_func, scaling=scaling, base_table=base_tab, rows_dev=rows_dev)
+            states.append((state, entries))
+        if return_stats:
+            for state, entries in states:
+                P = state.n_params
+                host = state.results.cpu().numpy()
+                band = (host[:2 * P * T] & 0xffffffff).astype(np.uint32).reshape(P, 2, T)
+                band_f = band.view(np.float32)
+                kept_pt = host[4 * P * T:5 * P * T].reshape(P, T)
+                stats["sign_conflict_rows"] += int(host[5 * P * T])
+                stats["empty_rows"] += int(host[5 * P * T + 1])
+                for i, name in entries.items():
+                    th, kp = stats["thresholds"].setdefault(name, {}), stats["kept"].setdefault(name, {})
+                    for g, _ in live[name]:
+                        t = wanted[g]
+                        nothing = band[i, 0, g] > band[i, 1, g]      # the sentinel band
+                        th[t] = None if nothing else (float(band_f[i, 0, g]), float(band_f[i, 1, g]))
+                        kp[t] = int(kept_pt[i, g])
+                        stats["kept_total"][t] += kp[t]
+        for name in names:
+            out[name] = _finish_output(out[name], original_shapes[name], name, later, device)
+    return (out, stats) if return_stats else out
+
+
 def _dare_arguments(drop_rate, seed):
     """(drop threshold, q = float32(1 - drop_rate)) of a DARE merge; the named ValueError for what lies outside the
     definition.  Host arithmetic in double: thr = min(int(drop_rate * 2^32), 2^32 - 1); dropped iff word < thr."""

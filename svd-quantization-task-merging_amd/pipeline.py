@@ -935,6 +935,59 @@ class CompressPlan:
                                                 int(merge_func == "sum"), float(scaling), _ptr(base_table),
                                                 _ptr(out_table), _ptr(state), _ptr(self._task_work), _stream_ptr()), who)
 
+    # ---- the Model Breadcrumbs merge: a two-sided magnitude band per (parameter, task) (svdq_crumbs.hip)
+    def _crumbs_state(self, who: str, n_tasks: int, state) -> int:
+        """``n_tasks`` checked, and ``state`` as the plan's table of svdq_crumbs_work_bytes(P, n_tasks) bytes."""
+        n_tasks = int(n_tasks)
+        need = int(self.lib.svdq_crumbs_work_bytes(self.P, n_tasks))
+        if need <= 0:
+            raise ValueError(f"{who}: n_tasks must be in [1, {nat.MAX_TASKS}], got {n_tasks}")
+        _need_state(who, state, torch.int64, need)
+        return n_tasks
+
+    def crumbs_hist(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, digit: int, bounds: int,
+                    state: torch.Tensor, rows_dev: Optional[torch.Tensor] = None) -> None:
+        """One digit of the radix selection of the band of every (parameter, task) of this plan (svdq_plan_crumbs_hist):
+        for each bound named by ``bounds`` (1 = lo, 2 = hi, 3 = both; 3 needs n_out <= 16) the magnitudes whose upper
+        bits equal that bound's prefix are counted by the digit's value into ``state``, the plan's table
+        (``CrumbsState``).  ``slot_task`` / ``task_map``: as for ``ties_hist``.  Reads the basis once, writes nothing but
+        the table.  Asynchronous on the current stream."""
+        who = "svdq_plan_crumbs_hist"
+        n_out = self._ties_tables(who, slot_task, task_map)
+        n_tasks = self._crumbs_state(who, n_tasks, state)
+        nat.check(self.lib.svdq_plan_crumbs_hist(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                 _ptr(self.mean), _ptr(slot_task), _ptr(task_map), n_out, n_tasks,
+                                                 int(digit), int(bounds), _ptr(state), _ptr(self._task_work),
+                                                 _stream_ptr()), who)
+
+    def crumbs_select(self, n_tasks: int, digit: int, ranks: torch.Tensor, state: torch.Tensor) -> None:
+        """The digit's bin of every (parameter, task, bound) (svdq_plan_crumbs_select_step): appended to the prefix in
+        ``state``, the histograms zeroed for the next digit.  ``ranks`` int64 device tensor [P, 2], read at digit 0: the
+        ranks of lo and hi from below (n_bot + 1, D_p - n_top), 0 and 0 for a parameter that keeps nothing."""
+        who = "svdq_plan_crumbs_select_step"
+        n_tasks = self._crumbs_state(who, n_tasks, state)
+        _need_device_tensor(who, "ranks", ranks, torch.int64, 2 * self.P)
+        nat.check(self.lib.svdq_plan_crumbs_select_step(self._h, n_tasks, int(digit), _ptr(ranks), _ptr(state),
+                                                        _stream_ptr()), who)
+
+    def crumbs_merge(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, state: torch.Tensor,
+                     out_table: torch.Tensor, sign_election: bool = False, merge_func: str = "sum", scaling: float = 1.0,
+                     base_table: Optional[torch.Tensor] = None, rows_dev: Optional[torch.Tensor] = None) -> None:
+        """Band, elect, combine and apply for every parameter of the plan in one pass over the basis
+        (svdq_plan_crumbs_merge), with the bands ``crumbs_thresholds`` left in ``state``: ``out_table`` / ``base_table``
+        as for ``ties_merge``.  Adds the kept counts and the two row counters to ``state``."""
+        who = "svdq_plan_crumbs_merge"
+        if merge_func not in ("mean", "sum"):
+            raise ValueError(f"{who}: merge_func must be 'mean' or 'sum', got {merge_func!r}")
+        n_out = self._ties_tables(who, slot_task, task_map)
+        n_tasks = self._crumbs_state(who, n_tasks, state)
+        _need_device_tensor(who, "out_table", out_table, torch.int64, self.P)
+        nat.check(self.lib.svdq_plan_crumbs_merge(self._h, _ptr(rows_dev), _ptr(self.small), _ptr(self.basis),
+                                                  _ptr(self.mean), _ptr(slot_task), _ptr(task_map), n_out, n_tasks,
+                                                  int(bool(sign_election)), int(merge_func == "sum"), float(scaling),
+                                                  _ptr(base_table), _ptr(out_table), _ptr(state), _ptr(self._task_work),
+                                                  _stream_ptr()), who)
+
     # ---- the drop-and-rescale (DARE) merge and task arithmetic (svdq_dare.hip)
     def dare_merge(self, slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int, row_base: torch.Tensor,
                    weights: torch.Tensor, state: torch.Tensor, out_table: torch.Tensor, seed: int = 0,
@@ -1358,6 +1411,47 @@ def ties_thresholds(jobs, n_tasks: int, rank: int, zeros: Optional[torch.Tensor]
                 plan.ties_hist(slot_task, task_map, n_tasks, digit, state.table, rows_dev=rows_dev)
             nat.check(lib.svdq_ties_select_step(_ptr(state.table), int(n_tasks), digit, int(rank), _ptr(zeros),
                                                 _stream_ptr()), "svdq_ties_select_step")
+    return state
+
+
+CRUMBS_DIGITS = 4      # SVDQ_CRUMBS_DIGITS
+CRUMBS_BOTH_MAX = 16   # task slots up to which one histogram launch counts both bounds (svdq_crumbs.hip)
+
+
+class CrumbsState:
+    """Views of ONE plan's Breadcrumbs state table (include/svdq.h: hist uint32 [P][2][T][256] | prefix [P][2][T] |
+    rank [P][2][T] | kept [P][T] | conflict rows | empty rows, the last four in uint64 words)."""
+
+    def __init__(self, n_params: int, n_tasks: int, device):
+        P, T = int(n_params), int(n_tasks)
+        need = int(nat.lib().svdq_crumbs_work_bytes(P, T))
+        if need <= 0:
+            raise ValueError(f"svdq_crumbs_work_bytes: n_params must be >= 1 and n_tasks in [1, {nat.MAX_TASKS}], got "
+                             f"{P} and {T}")
+        self.n_params, self.n_tasks = P, T
+        self.table = torch.zeros(need // 8, dtype=torch.int64, device=device)
+        at = P * T * 256
+        self.results = self.table[at:at + 5 * P * T + 2]      # everything but the histograms
+        self.thresholds = self.table[at:at + 2 * P * T].view(P, 2, T)      # bit patterns of lo / hi in the low 32 bits
+        self.kept = self.table[at + 4 * P * T:at + 5 * P * T].view(P, T)
+        self.counters = self.table[at + 5 * P * T:at + 5 * P * T + 2]      # rows with both signs kept, with nothing kept
+
+
+def crumbs_thresholds(plan: "CompressPlan", slot_task: torch.Tensor, task_map: torch.Tensor, n_tasks: int,
+                      ranks: torch.Tensor, rows_dev: Optional[torch.Tensor] = None) -> CrumbsState:
+    """The digit loop of the Breadcrumbs band over ONE plan (thresholds never cross parameters): per digit the
+    histograms of both bounds -- one launch with ``bounds=3`` for n_out <= 16, two (``bounds=1``, then ``bounds=2``)
+    above, where both do not fit the LDS -- then one small launch that picks the bin of every (parameter, task, bound).
+    ``slot_task`` / ``task_map`` / ``rows_dev``: the arguments of ``CompressPlan.crumbs_hist``; ``ranks``: int64 device
+    tensor [P, 2] (``CompressPlan.crumbs_select``).  Nothing is read back between the passes; returns the state with
+    ``thresholds`` filled."""
+    state = CrumbsState(plan.P, n_tasks, plan.device)
+    passes = (3,) if int(task_map.shape[1]) <= CRUMBS_BOTH_MAX else (1, 2)
+    with torch.cuda.device(plan.device):
+        for digit in range(CRUMBS_DIGITS):
+            for bounds in passes:
+                plan.crumbs_hist(slot_task, task_map, n_tasks, digit, bounds, state.table, rows_dev=rows_dev)
+            plan.crumbs_select(n_tasks, digit, ranks, state.table)
     return state
 
 

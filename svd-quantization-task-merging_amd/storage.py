@@ -584,6 +584,29 @@ def ties_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: s
     return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
 
 
+def breadcrumbs_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None, density: float = 0.9,
+                                     gamma: float = 0.01, scaling: float = 1.0, sign_election: bool = False,
+                                     merge_func: str = "sum", tasks=None, device: str = "cuda") -> Dict[str, Any]:
+    """The Model Breadcrumbs merge of a stored artifact set, the per-tensor TIES trim with ``gamma=0,
+    sign_election=True, merge_func="mean"`` (``merge.breadcrumbs_merge_parameters``, which see for the definition):
+    load_all_artifacts -> adopt_artifacts -> breadcrumbs_merge_parameters with the base inside the launch -> the base's
+    other tensors cloned (as apply_merged_deltas does) -> optional save.  Masks are not stored (reload.py:204-205): a
+    masked run's store is refused with a ValueError naming the parameter.  ``base_model_path``: a path or a state dict;
+    ``tasks``: names (None = every stored task).  The store's files are only read.
+
+    Returns {"merged_state_dict", "stats" (bands and kept counts per parameter and task, row counters, rows),
+    "diagnostics", "config"}."""
+    from .merge import _crumbs_arguments, breadcrumbs_merge_parameters
+    _crumbs_arguments(density, gamma, scaling, merge_func)      # before any file or device work
+    config, diagnostics, bases, compressed, shapes, base, covered = _adopted_store(artifact_dir, tasks, device,
+                                                                                   base_model_path)
+    merged, stats = breadcrumbs_merge_parameters(compressed, bases, shapes, config, density=density, gamma=gamma,
+                                                 scaling=scaling, sign_election=sign_election, merge_func=merge_func,
+                                                 tasks=tasks, base_state_dict=covered, device=device, return_stats=True)
+    out = _merged_over_base(merged, base, output_path)
+    return {"merged_state_dict": out, "stats": stats, "diagnostics": diagnostics, "config": config}
+
+
 def dare_merge_from_artifacts(artifact_dir: str, base_model_path, output_path: str = None, drop_rate: float = 0.9,
                               seed: int = 0, rescale: bool = True, weights=None, normalize: bool = False,
                               scaling: float = 1.0, tasks=None, device: str = "cuda") -> Dict[str, Any]:
