@@ -41,7 +41,8 @@ def _project(delta, U_high, U_low, mean):
         return torch.zeros(0, device=out_dev), torch.zeros(0, device=out_dev)
     if (k and U_high.shape[0] != D) or (nl and U_low.shape[0] != D):
         raise ValueError(f"Shape mismatch: basis rows vs delta length {D}")
-    fp16 = (U_high.dtype == torch.float16) if k else (U_low.dtype == torch.float16)
+    # fp16 kernels only when every array that has columns is fp16; a mix is lifted to fp32, never rounded down
+    fp16 = k + nl > 0 and all(u.dtype == torch.float16 for u, n in ((U_high, k), (U_low, nl)) if n)
     dt = torch.float16 if fp16 else torch.float32
     uh = U_high.to(device=dev, dtype=dt).contiguous() if k else None
     ul = U_low.to(device=dev, dtype=dt).contiguous() if nl else None

@@ -183,8 +183,7 @@ __global__ __launch_bounds__(ELT_THREADS) void k_recon_error(const T *__restrict
         sx += (double)x * x;
         sr += (double)rec * rec;
         sa += fabs((double)e);
-        mx = fmaxf(mx, fabsf(e));
-        if (e != e) mx = e;  // NaN propagates like torch.max
+        mx = fmaxf(mx, fabsf(e));      // skips a NaN: the finish kernel puts it back from the sum of squares
     }
     __shared__ double r0[ELT_THREADS], r1[ELT_THREADS], r2[ELT_THREADS], r3[ELT_THREADS], r4[ELT_THREADS];
     const int tid = threadIdx.x;
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(ELT_THREADS) void k_recon_error(const T *__restrict
         if (tid < off) {
             r0[tid] += r0[tid + off]; r1[tid] += r1[tid + off]; r2[tid] += r2[tid + off]; r3[tid] += r3[tid + off];
             const double a = r4[tid], b = r4[tid + off];
-            r4[tid] = (a != a) ? a : ((b != b) ? b : (b > a ? b : a));
+            r4[tid] = b > a ? b : a;
         }
         __syncthreads();
     }
@@ -211,8 +210,11 @@ __global__ __launch_bounds__(64) void k_recon_error_finish(const ErrPart *__rest
     for (int b = 0; b < nblk; ++b) {
         se += part[b].se; sx += part[b].sx; sr += part[b].sr; sa += part[b].sa;
         const double v = part[b].mx;
-        mx = (mx != mx) ? mx : ((v != v) ? v : (v > mx ? v : mx));
+        mx = v > mx ? v : mx;
     }
+    // NaN propagates like torch.max: an error element is NaN exactly when the sum of the squares is (a square is
+    // >= 0 or NaN, so the sum cannot cancel to one), whichever row, thread or block it sat in
+    if (se != se) mx = se;
     // the reference works on fp32 tensors: norms are fp32 values
     const float en = (float)sqrt(se), on = (float)sqrt(sx);
     out[0] = (double)en;

@@ -199,21 +199,45 @@ at::Tensor mask_combine(at::TensorList masks, c10::string_view strategy) {
 at::Tensor mask_select(const at::Tensor &x, const at::Tensor &mask, bool invert) {
     TORCH_CHECK_VALUE(x.sizes() == mask.sizes(), "Shape mismatch: tensor ", x.sizes(), " vs mask ", mask.sizes());
     if (x.numel() == 0) return x.flatten();
-    if (x.scalar_type() != at::kFloat) return mask_select(x.to(at::kFloat), mask, invert).to(x.scalar_type());
-    const at::Tensor v = prep(x);
-    const c10::Device dev = v.device();
+    // The kernel moves 4-byte words and computes nothing on them, so the selection is exact for every accepted dtype:
+    // a 4-byte type travels as its own bits, an 8-byte type as its low and high words (two buffers under the one mask),
+    // a narrower type through the fp32 value that holds it exactly.  Anything else is refused by name, never rounded.
+    const at::ScalarType st = x.scalar_type();
+    const bool own_bits = st == at::kFloat || st == at::kInt, two_words = st == at::kLong || st == at::kDouble;
+    const bool widened = st == at::kHalf || st == at::kBFloat16 || st == at::kBool || st == at::kByte || st == at::kChar ||
+                         st == at::kShort;
+    TORCH_CHECK_VALUE(own_bits || two_words || widened, "mask_select: dtype ", c10::toString(st),
+                      " cannot be selected exactly (bool, uint8, int8, int16, int32, int64, float16, bfloat16, float32, "
+                      "float64 can)");
+    if (widened) return mask_select(x.to(at::kFloat), mask, invert).to(st);
+    TORCH_CHECK(x.is_cuda(), "svdq operators take device tensors");
+    const c10::Device dev = x.device();
     c10::DeviceGuard guard(dev);
-    const int64_t numel = v.numel();
+    const int64_t numel = x.numel();
+    std::vector<at::Tensor> src, dst;
+    at::Tensor flat = x.detach().contiguous().view({-1});
+    // a single strided element counts as contiguous and keeps its stride; a view in another element size needs 1
+    if (flat.stride(0) != 1) flat = flat.clone(at::MemoryFormat::Contiguous);
+    if (two_words) {
+        const at::Tensor w = flat.view(at::kFloat).view({numel, 2});
+        // dense copies of the two word columns (a single element would stay the strided view itself: clone it too)
+        for (int64_t h = 0; h < 2; ++h) src.push_back(w.select(1, h).clone(at::MemoryFormat::Contiguous));
+    } else {
+        at::Tensor v = flat.view(at::kFloat);
+        if (reinterpret_cast<uintptr_t>(v.data_ptr()) & 15) v = v.clone();
+        src.push_back(v);
+    }
+    for (size_t h = 0; h < src.size(); ++h) dst.push_back(floats_on(dev, numel));
     at::Tensor mb = mask_bytes(mask.to(dev));
-    at::Tensor dst = floats_on(dev, numel);
     at::Tensor count = at::zeros({1}, at::TensorOptions().dtype(at::kLong).device(dev));
-    at::Tensor stab = table_of({v}, dev), dtab = table_of({dst}, dev);
+    at::Tensor stab = table_of(src, dev), dtab = table_of(dst, dev);
     at::Tensor work = bytes_on(dev, svdq_mask_work_bytes(numel));
-    check(svdq_mask_compact(stab.data_ptr(), dtab.data_ptr(), 1, mb.data_ptr<uint8_t>(), invert ? 1 : 0, numel,
-                            count.data_ptr<int64_t>(), work.data_ptr(), stream_of(dev)),
+    check(svdq_mask_compact(stab.data_ptr(), dtab.data_ptr(), (int32_t)src.size(), mb.data_ptr<uint8_t>(), invert ? 1 : 0,
+                            numel, count.data_ptr<int64_t>(), work.data_ptr(), stream_of(dev)),
           "svdq_mask_compact");
     const int64_t n = count.item<int64_t>();          // the output size of boolean indexing is data dependent
-    return dst.narrow(0, 0, n).clone();
+    if (two_words) return at::stack({dst[0].narrow(0, 0, n), dst[1].narrow(0, 0, n)}, 1).view(st).view({-1});
+    return dst[0].narrow(0, 0, n).clone().view(st);
 }
 
 // ------------------------------------------------------------------------------------------ plans
@@ -319,6 +343,22 @@ std::unique_ptr<Plan> acquire_plan(const PlanKey &key, const c10::Device &dev) {
 
 void release_plan(PlanKey key, std::unique_ptr<Plan> plan) { g_cache.emplace_back(std::move(key), std::move(plan)); }
 
+// A plan out of the cache for the length of one operator call (under g_cache_mu): it goes back on EVERY way out, a
+// refusal raised between the two included -- a plan dropped there would be rebuilt, with a synchronisation, by the
+// next good call of the same key.
+struct PlanLease {
+    PlanKey key;
+    std::unique_ptr<Plan> plan;
+    PlanLease(PlanKey k, const c10::Device &dev) : key(std::move(k)), plan(acquire_plan(key, dev)) {}
+    PlanLease(const PlanLease &) = delete;
+    PlanLease &operator=(const PlanLease &) = delete;
+    ~PlanLease() {
+        if (plan) release_plan(std::move(key), std::move(plan));
+    }
+    Plan *operator->() const { return plan.get(); }
+    Plan &operator*() const { return *plan; }
+};
+
 struct Outputs {
     at::Tensor small, basis, mean;
 };
@@ -346,12 +386,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> compress(at::TensorList deltas, i
     PlanKey key{rows_of(vecs, n_tasks), n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream,
                 in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     Outputs o = alloc_outputs(*plan, center, dev);
     at::Tensor table = table_of(vecs, dev);
     const int rc = svdq_compress(plan->h, table.data_ptr(), nullptr, plan->workspace.data_ptr(), o.small.data_ptr(),
                                  o.basis.data_ptr(), center ? o.mean.data_ptr<float>() : nullptr, stream);
-    release_plan(std::move(key), std::move(plan));
     check(rc, "svdq_compress");
     // inputs and the table are only read by the kernels just enqueued; temporaries are released stream-ordered
     return {o.small, o.basis, o.mean};
@@ -371,7 +410,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_task_gram(at
     PlanKey key{rows_of(vecs, n_tasks), n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream,
                 in_type, true};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     Outputs o = alloc_outputs(*plan, center, dev);
     at::Tensor table = table_of(vecs, dev);
     at::Tensor gram = at::empty({n_tasks, n_tasks}, at::TensorOptions().dtype(at::kDouble).device(dev));
@@ -382,7 +421,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_task_gram(at
         rc = svdq_plan_task_gram(plan->h, plan->workspace.data_ptr(), gram.data_ptr<double>(), stream);
         what = "svdq_plan_task_gram";
     }
-    release_plan(std::move(key), std::move(plan));
     check(rc, what);
     return {o.small, o.basis, o.mean, gram};
 }
@@ -405,13 +443,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> compress_from_base(at::TensorList
     }
     PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     Outputs o = alloc_outputs(*plan, center, dev);
     at::Tensor table = table_of(vecs, dev), btab = table_of(bs, dev);
     const int rc = svdq_compress_from_base(plan->h, table.data_ptr(), btab.data_ptr(), nullptr, plan->workspace.data_ptr(),
                                            o.small.data_ptr(), o.basis.data_ptr(),
                                            center ? o.mean.data_ptr<float>() : nullptr, stream);
-    release_plan(std::move(key), std::move(plan));
     check(rc, "svdq_compress_from_base");
     return {o.small, o.basis, o.mean};
 }
@@ -455,7 +492,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_with_masks(a
     at::Tensor mtab = table_of(mb, dev);
     PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     Outputs o = alloc_outputs(*plan, center, dev);
     at::Tensor table = table_of(vecs, dev);
     int rc;
@@ -481,7 +518,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> compress_with_masks(a
                                       center ? o.mean.data_ptr<float>() : nullptr, stream);
         sync(dev);      // the index lists die with this scope
     }
-    release_plan(std::move(key), std::move(plan));
     check(rc, what);
     return {o.small, o.basis, o.mean, ct};
 }
@@ -539,7 +575,7 @@ std::vector<at::Tensor> merge(const at::Tensor &small, const at::Tensor &basis, 
     const int64_t n_sets = w.dim() == 2 ? w.size(0) : 1;
     PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     check_artifacts("merge", small, basis, mean, plan->sizes, center, dev);
     std::vector<at::Tensor> outs, bs;
     for (int64_t p = 0; p < P; ++p) outs.push_back(floats_on(dev, rows[p]));
@@ -561,7 +597,6 @@ std::vector<at::Tensor> merge(const at::Tensor &small, const at::Tensor &basis, 
                               w.data_ptr<float>(), nullptr, (int32_t)n_sets, 0,
                               n_sets > 1 ? share.data_ptr<float>() : nullptr, nullptr,
                               bs.empty() ? nullptr : btab.data_ptr(), otab.data_ptr(), work.data_ptr(), stream);
-    release_plan(std::move(key), std::move(plan));
     check(rc, "svdq_merge");
     return outs;
 }
@@ -624,7 +659,7 @@ std::vector<at::Tensor> merge_masked(const at::Tensor &small, const at::Tensor &
     } ms_guard{ms, dev};
     PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     check_artifacts("merge_masked", small, basis, mean, plan->sizes, center, dev);
     MaskWalk mw = mask_walk(ms, *plan, masks, rows, dev, stream, "merge_masked");
     std::vector<at::Tensor> outs, bs;
@@ -644,7 +679,6 @@ std::vector<at::Tensor> merge_masked(const at::Tensor &small, const at::Tensor &
                                      nullptr, (int32_t)n_sets, 0, n_sets > 1 ? share.data_ptr<float>() : nullptr, nullptr,
                                      mw.mtab.data_ptr(), mw.us.data_ptr<int64_t>(), fill.data_ptr<int32_t>(),
                                      bs.empty() ? nullptr : btab.data_ptr(), otab.data_ptr(), work.data_ptr(), stream);
-    release_plan(std::move(key), std::move(plan));
     check(rc, "svdq_merge_masked");
     return outs;
 }
@@ -678,7 +712,7 @@ at::Tensor diagnostics(at::TensorList deltas, at::TensorList masks, const at::Te
     } ms_guard{ms, dev};
     PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     check_artifacts("diagnostics", small, basis, mean, plan->sizes, center, dev);
     at::Tensor table = table_of(vecs, dev);
     at::Tensor out = at::empty({P, n_tasks, 6}, at::TensorOptions().dtype(at::kDouble).device(dev));
@@ -699,7 +733,6 @@ at::Tensor diagnostics(at::TensorList deltas, at::TensorList masks, const at::Te
                               basis.data_ptr(), mn, add_mean ? 1 : 0, out.data_ptr<double>(), work.data_ptr(), stream);
         sync(dev);      // the pointer table dies with this scope
     }
-    release_plan(std::move(key), std::move(plan));
     check(rc, "svdq_diagnostics");
     return out;
 }
@@ -726,7 +759,7 @@ at::Tensor diagnostics_from_base(at::TensorList finetuned, at::TensorList base, 
                       "diagnostics_from_base: all tensors must live on one device");
     PlanKey key{rows, n_tasks, max_rank, bits, stages, energy, center, fp16, (int)dev.index(), stream, in_type};
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    std::unique_ptr<Plan> plan = acquire_plan(key, dev);
+    PlanLease plan(std::move(key), dev);
     check_artifacts("diagnostics_from_base", small, basis, mean, plan->sizes, center, dev);
     at::Tensor table = table_of(vecs, dev), btab = table_of(bs, dev);
     at::Tensor out = at::empty({P, n_tasks, 6}, at::TensorOptions().dtype(at::kDouble).device(dev));
@@ -739,7 +772,6 @@ at::Tensor diagnostics_from_base(at::TensorList finetuned, at::TensorList base, 
                                               small.data_ptr(), basis.data_ptr(), mn, add_mean ? 1 : 0,
                                               out.data_ptr<double>(), work.data_ptr(), stream);
     sync(dev);      // the pointer tables die with this scope
-    release_plan(std::move(key), std::move(plan));
     check(rc, "svdq_diagnostics_from_base");
     return out;
 }
@@ -862,7 +894,10 @@ BasisArgs basis_args(const at::Tensor &U_high, const at::Tensor &U_low, const at
     a.k = U_high.size(1);
     a.nl = U_low.size(1);
     TORCH_CHECK_VALUE(a.k + a.nl <= 32, what, ": at most 32 basis columns");
-    a.fp16 = (a.k ? U_high : U_low).scalar_type() == at::kHalf;
+    // fp16 kernels only when every array that has columns is fp16; any other mix is lifted to fp32 (exact from fp16 and
+    // bf16), never rounded down to the other array's type
+    a.fp16 = a.k + a.nl > 0 && (a.k == 0 || U_high.scalar_type() == at::kHalf) &&
+             (a.nl == 0 || U_low.scalar_type() == at::kHalf);
     const auto dt = a.fp16 ? at::kHalf : at::kFloat;
     a.uh = U_high.to(dt).contiguous();
     a.ul = U_low.to(a.dev, dt).contiguous();

@@ -53,7 +53,8 @@ def _fused_error(x: torch.Tensor, U_high, U_low, c_high, c_low, dev) -> Dict[str
     D = x.numel()
     k = U_high.shape[1] if U_high.dim() == 2 else 0
     nl = U_low.shape[1] if U_low.dim() == 2 else 0
-    fp16 = (U_high.dtype == torch.float16) if k else (U_low.dtype == torch.float16)
+    # fp16 kernels only when every array that has columns is fp16; a mix is lifted to fp32, never rounded down
+    fp16 = k + nl > 0 and all(u.dtype == torch.float16 for u, n in ((U_high, k), (U_low, nl)) if n)
     dt = torch.float16 if fp16 else torch.float32
     uh = U_high.to(device=dev, dtype=dt).contiguous() if k else None
     ul = U_low.to(device=dev, dtype=dt).contiguous() if nl else None

@@ -119,6 +119,17 @@ def diag_check(got, x, U_high, U_low, c_high, c_low, what="", mean=None, slack=1
         assert abs(g - w) <= 2e-6 * abs(w) + slack * tol[key] + 1e-30, (what, key, g, w, tol[key])
 
 
+def diag_check_given(got, x, recon, what=""):
+    """The six numbers of a GIVEN reconstruction (diagnostics.py:72-117 on two tensors): there is no chain of products
+    to bound, ``e = x - recon`` rounds once (relative 2^-24 per element, so at most that on each norm, the maximum and
+    the mean) and the norms are reported as fp32 values -- relative 2e-6 holds both."""
+    from oracle import svd_hybrid_oracle as orc
+    want = orc.reconstruction_error(x.reshape(-1).double(), recon.reshape(-1).double())
+    for key in orc.DIAG_KEYS:
+        g, w = float(got[key]), float(want[key])
+        assert abs(g - w) <= 2e-6 * abs(w) + 1e-30, (what, key, g, w)
+
+
 def diag_check_chunked(got, x, U_high, U_low, c_high, c_low, what="", chunk=1 << 24):
     """diag_check for tensors too long for one library call (2^30 rows: a single fp64 matrix-vector product of that
     length is itself suspect): the same formula and the same bound, accumulated over row chunks in fp64."""
